@@ -15,7 +15,10 @@ reference's initialisation window, with an empty covisibility graph (TrackFronte
 fresh run over its frames, tests/test_slam_gpu.py).  One resident recording is read cyclically; frames are in HBM before the
 timed region.  value = frames of all ranks / max-over-ranks time.
 
-Beside it, in the same JSON line (rank 0, N = 1):
+A plain run (`--gpus 1 --steps K --warmup W`) does only what the headline needs: set-up, W warm-up steps, K timed steps, the outputs of
+the last timed step if `--dump-outputs DIR` is given, and the JSON line (`ms_per_step` = milliseconds per timed step).  With `--full`
+the same line also carries (rank 0, N = 1), each measured after the timed region:
+  power              package power and shader clock over the timed region (amdgpu hwmon)
   operating_points   the reference's own schedules on the same network: fixed cadence with ONE window at a time
                      (window_batch=1), the default batch over ONE endless stream (no sequence cuts: every keyframe is tested
                      against all earlier ones), and the maintained configs' OVERLAP mode (kf_every=-1, skip=5, thresh=0.9,
@@ -364,9 +367,10 @@ class PowerSampler:
 
 # ------------------------------------------------------------------------------------------------------------------ legs
 def fixed_cadence_leg(model, slam_cls, cdist, dev, wb, steps, warmup, world=1, rank=0, dist_on=False, emu=0, probe_steps=0, barrier=None,
-                      seq_windows=0, frame_source="host"):
+                      seq_windows=0, frame_source="host", power=True):
     """buffered fixed-cadence schedule (kf_every=10) through the pipelined ShardedTracker; returns dict of results.  seq_windows > 0:
-    the stream is a succession of sequences of that many windows (TrackFrontend.sequence_windows), 0: one endless sequence"""
+    the stream is a succession of sequences of that many windows (TrackFrontend.sequence_windows), 0: one endless sequence.
+    power: sample package power over the timed region"""
     total_steps = warmup + steps
     n_kf = 7 + WIN * wb * world * (total_steps + probe_steps) + 2
     config = {"Tracking": {"motion_filter": {"thresh": 0.9, "skip": 5, "skip_blur": False, "kf_every": KF_EVERY},
@@ -404,7 +408,7 @@ def fixed_cadence_leg(model, slam_cls, cdist, dev, wb, steps, warmup, world=1, r
     for k in runner.stats:
         runner.stats[k] = 0
     up0 = getattr(frames, "bytes_uploaded", 0)
-    sampler = PowerSampler(torch.device(dev).index or 0).start() if (world == 1 and emu <= 1) else None
+    sampler = PowerSampler(torch.device(dev).index or 0).start() if (power and world == 1 and emu <= 1) else None
     tic = time.perf_counter()
     for _ in range(steps):
         t = runner.step(frames, t, KF_EVERY, WIN, intr)
@@ -426,6 +430,48 @@ def tracking_health(slam):
     return {"tracked_keyframes": k, "poses_finite": bool(bad.size == 0), "first_nonfinite_keyframe": (int(bad[0]) if bad.size else None),
             "nonfinite_windows": int(st["nonfinite_windows"]), "steady_windows": int(st["windows"]),
             "log_scale_absmax": round(float(st["log_scale_absmax"]), 4), "log_scale_last": round(float(st["log_scale_last"]), 4)}
+
+
+DUMP_SAMPLE_BYTES = 48 << 20          # per-pixel samples of --dump-outputs; the small per-keyframe arrays come on top (< 64 MB in all)
+
+
+def dump_outputs(out_dir, slam, n_windows, seed=0):
+    """--dump-outputs: what the timed path computed in its LAST step, as the tracker's caller receives it, one float32 .npy per array
+    (edge indices float64): the step's n_windows windows cover keyframes k0..k1-1 (k1 = tracker.t1, k0 shared with the step before) --
+    their c2w poses (t, q_xyzw), world->camera rows and time stamps, the depth maps, the windows' submap pointmaps and confidences, and
+    the covisibility edges with a keyframe of the step as their later end, in insertion order.  The per-pixel arrays are sampled at a
+    fixed set of pixels (numpy seed `seed`, sorted row-major indices) sized to DUMP_SAMPLE_BYTES."""
+    kf = slam.keyframes
+    k1 = int(slam.tracker.t1)
+    k0 = k1 - WIN * n_windows - 1
+    w1 = (k1 - 1) // WIN                  # the window starting at keyframe t0 stores its submap in row t0 // 5
+    w0 = w1 - n_windows
+    nk = k1 - k0
+    h2, w2 = kf.submap_ds.shape[2:4]
+    per_px = 4 * (nk + 6 * n_windows * 4)                        # depth + submap xyz + conf, bytes per sampled pixel
+    P = max(1, min(h2 * w2, DUMP_SAMPLE_BYTES // per_px))
+    rng = np.random.default_rng(seed)
+    pix = torch.from_numpy(np.sort(rng.choice(kf.ht * kf.wd, P, replace=False))).to(kf.depth.device)
+    pix_ds = torch.from_numpy(np.sort(rng.choice(h2 * w2, P, replace=False))).to(kf.depth.device)
+    if kf.depth.is_cuda:
+        torch.cuda.synchronize()
+    ii, jj = slam.graph.edges_absolute()
+    new = np.maximum(ii, jj) > k0
+    arrays = {"pose": kf.pose[k0:k1], "w2c": kf.w2c[k0:k1], "tstamp": kf.tstamp[k0:k1],
+              "depth_sample": kf.depth[k0:k1].reshape(nk, -1)[:, pix],
+              "submap_sample": kf.submap_ds[w0:w1].reshape(n_windows, 6, h2 * w2, 3)[:, :, pix_ds],
+              "conf_sample": kf.conf_ds[w0:w1].reshape(n_windows, 6, h2 * w2)[:, :, pix_ds]}
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = a.detach().float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    for name, a in (("edges_ii", ii[new]), ("edges_jj", jj[new])):
+        a = a.astype(np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    log(f"outputs of the last timed step (keyframes {k0}..{k1 - 1}, {int(new.sum())} edges, {P} sampled pixels) -> {out_dir}: {total / 1e6:.1f} MB")
 
 
 def overlap_mode_leg(model, slam_cls, dev, n_frames=800, lookahead=16, plain_frames=200, deep_frames=2800, deep_lookahead=280, deep_wb=28):
@@ -701,8 +747,12 @@ def launch_ranks(n):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=4)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=4, help="timed steps (>= 1)")
+    ap.add_argument("--warmup", type=int, default=1, help="untimed steps before them")
+    ap.add_argument("--full", action="store_true", help="after the headline: power, roofline, operating points, trajectory parity and CPU "
+                    "baseline (the --no-* options below drop single parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (float32/float64, "
+                    "sampled to < 64 MB; identical inputs from run to run)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-operating-points", action="store_true")
@@ -724,6 +774,8 @@ def main():
     #      the exit code.  Under a launcher (WORLD_SIZE set) --gpus must agree with it: a mislabelled run is refused, never reported.
     if args.gpus < 1:
         raise SystemExit("bench: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench: --steps must be >= 1 and --warmup >= 0")
     backend_env = os.environ.get("CUT3R_DIST_BACKEND", "nccl")
     emu_env = int(os.environ.get("CUT3R_EMULATE_WORLD", "0"))
     if "WORLD_SIZE" not in os.environ:
@@ -787,14 +839,14 @@ def main():
     if emu > 1:
         world = emu                                # after the process-group decisions above: no collective is created
     single = rank == 0 and world == 1 and emu <= 1 and not dist_on
-    probe_steps = args.steps if (single and not args.no_roofline) else 0
+    probe_steps = args.steps if (single and args.full and not args.no_roofline) else 0
     log("fixed-cadence leg: initialisation window, warmup, timed region")
     # weak scaling: every GPU adds 28 windows per step of the same Replica-shaped sequences (per-GPU work fixed: a keyframe is tested
     # against the <= 200 keyframes of its own sequence); --sequence-per-gpu makes the sequences grow with the job instead
     SEQ = max(0, args.sequence_windows) * (world if args.sequence_per_gpu else 1)
     emu_rank = int(os.environ.get("CUT3R_EMULATE_RANK", "0")) % max(1, world) if emu > 1 else rank    # debug: rehearse another rank's load
     leg = fixed_cadence_leg(model, Cut3rSlam, cdist, dev, WB, args.steps, args.warmup, world, emu_rank, dist_on, emu, probe_steps, barrier,
-                            seq_windows=SEQ, frame_source=args.frames)
+                            seq_windows=SEQ, frame_source=args.frames, power=args.full)
     elapsed, slam, runner, frames, t, intr = (leg[k] for k in ("elapsed", "slam", "runner", "frames", "t", "intr"))
     frames_per_step = leg["frames_per_step"]
     leg_h2d = leg["h2d_bytes_per_step"]
@@ -826,6 +878,8 @@ def main():
         np.savez(f"{dump}.rank{rank}.npz", pose=slam.keyframes.pose[:k].numpy(), depth_sum=slam.keyframes.depth[:k - 1].double().sum(dim=(1, 2)).cpu().numpy(),
                  submap_sum=slam.keyframes.submap_ds[:(k - 1) // 5].double().sum(dim=(2, 3, 4)).cpu().numpy(),
                  w2c=slam.keyframes.w2c[:k].cpu().numpy(), ii=ii, jj=jj, k=k)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, slam, WB * world)
 
     roofline, cpu_base, op_points, traj = None, None, None, None
     if probe_steps:
@@ -885,7 +939,7 @@ def main():
                                 e["frac_of_sustained"] = round(e["achieved"] / sus, 4)
                 except Exception as ex:      # a measurement aid: never fails the bench line
                     roofline["sustained_mfma"] = {"error": str(ex)}
-    if single and not args.small and not args.no_operating_points:
+    if single and args.full and not args.small and not args.no_operating_points:
         log("operating points: fixed cadence with one window at a time")
         del leg, runner, slam
         op_points = {}
@@ -945,10 +999,10 @@ def main():
         op_points["loop_closure_on_window_batch_4"] = guarded("loop closure leg, window batch 4", loop_closure_leg, cfg, Cut3rSlam, dev, wb=4)
         log("operating points: GS mapper on a synthetic window (rasteriser forward + backward, pose refinement, mapping)")
         op_points["gs_mapper_synthetic_window"] = guarded("GS mapper leg", synth.gs_mapper_window_leg, H, W, dev)
-    if single and not args.no_trajectory_parity:
+    if single and args.full and not args.no_trajectory_parity:
         log("trajectory parity leg (medium config, GPU vs CPU oracle)")
         traj = guarded("trajectory parity leg", trajectory_parity_leg, dev, None if (args.small or args.no_production_parity) else model, sd)
-    if single and not args.no_cpu_baseline and not args.small:
+    if single and args.full and not args.no_cpu_baseline and not args.small:
         log("cpu baseline (oracle on host cores)")
         cpu_base = guarded("cpu baseline", cpu_baseline, cfg, sd, torch.cat([to_tracking(frames[i:i + 1]) for i in range(2)], 0).cpu())
         log("cpu baseline done")
@@ -972,10 +1026,10 @@ def main():
                                    "6-view recurrent decoder + DPT head per window (windows batched through the decoder), "
                                    "log-depth/pose chaining + covisibility-graph update per keyframe; "
                                    "ViT-L/24 enc, 768/12 dual decoder, DPT head, random init; GS backend off; the reference's own "
-                                   "schedules (one window at a time; overlap mode) are in `operating_points`"
+                                   "schedules (one window at a time; overlap mode) are in `operating_points` (--full)"
                                    + (" [DEBUG --small]" if args.small else ""),
                        "frames_per_step": frames_per_step, "window_views": 6, "window_batch": WB, "sequence_windows": SEQ, "parallelism": f"window-sharded x{world}",
-                       "frame_source": args.frames, "h2d_mb_per_step": round(leg_h2d / 1e6, 2)},
+                       "frame_source": args.frames, "h2d_mb_per_step": round(leg_h2d / 1e6, 2), "full": bool(args.full)},
             "power": leg_power, "roofline": roofline, "cpu_baseline": cpu_base, "operating_points": op_points, "trajectory_parity": traj,
             "ate_rmse_m": (traj or {}).get("fixed_cadence_kf_every_2", {}).get("ate_rmse_m"),
             "ate_rmse_m_production_384x512": (traj or {}).get("production_384x512_kf_every_2", {}).get("ate_rmse_m"),

@@ -211,3 +211,35 @@ def test_power_sampler_is_silent_without_the_hwmon_files(tmp_path):
     out = s.stop()
     assert out is not None and out["package_w_mean"] == 1300.0 and out["sclk_mhz_mean"] == 2000.0 and out["power_cap_w"] == 1400.0
     assert abs(out["frac_of_cap"] - 0.929) < 1e-3 and out["samples"] >= 3
+
+
+def test_dump_outputs_writes_the_last_steps_keyframes_windows_and_edges(tmp_path):
+    """bench.py --dump-outputs: the rows of the last step's windows (two windows of five keyframes after 26 tracked keyframes: keyframes
+    15..25, submap rows 3 and 4), the edges whose later end is one of its new keyframes, float32 / float64 only, the same pixel sample
+    every time"""
+    from types import SimpleNamespace
+    import bench
+    kf = KeyFrame({}, (32, 64), 40, 2, device="cpu", feat_dim=8, patch=16)
+    for k in range(40):
+        kf.depth[k] = float(k)
+        kf.pose[k, 0] = float(k)
+    for w in range(kf.submap_ds.shape[0]):
+        kf.submap_ds[w] = float(w)
+        kf.conf_ds[w] = float(w) + 0.5
+    graph = SimpleNamespace(edges_absolute=lambda: (np.array([1, 16, 3, 24], np.int64), np.array([0, 3, 16, 20], np.int64)))
+    slam = SimpleNamespace(keyframes=kf, graph=graph, tracker=SimpleNamespace(t1=26))
+    outs = []
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), slam, 2)
+        outs.append({f[:-4]: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    a = outs[0]
+    assert sorted(a) == ["conf_sample", "depth_sample", "edges_ii", "edges_jj", "pose", "submap_sample", "tstamp", "w2c"]
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values()) and sum(v.nbytes for v in a.values()) < 64 << 20
+    np.testing.assert_array_equal(a["pose"][:, 0], np.arange(15, 26, dtype=np.float32))
+    assert a["depth_sample"].shape[0] == 11 and (a["depth_sample"] == np.arange(15, 26, dtype=np.float32)[:, None]).all()
+    assert a["submap_sample"].shape[:2] == (2, 6) and a["submap_sample"].shape[-1] == 3
+    assert (a["submap_sample"][0] == 3).all() and (a["submap_sample"][1] == 4).all() and (a["conf_sample"][1] == 4.5).all()
+    np.testing.assert_array_equal(a["edges_ii"], [16, 3, 24])
+    np.testing.assert_array_equal(a["edges_jj"], [3, 16, 20])
+    for k, v in a.items():
+        np.testing.assert_array_equal(v, outs[1][k], err_msg=k)

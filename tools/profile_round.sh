@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp
 HB=$!
 trap "kill $HB 2>/dev/null" EXIT
 MODE=${2:-all}
-COMMON="--no-cpu-baseline --no-operating-points --no-trajectory-parity"
+COMMON="--full --no-cpu-baseline --no-operating-points --no-trajectory-parity"
 if [ "$MODE" != "pmc" ]; then
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --steps 4 --warmup 1 $COMMON > $O/stats_bench.json 2> $O/stats_bench.log
 ST=$(find $O/stats -name "*kernel_stats.csv" | head -1)
