@@ -705,3 +705,66 @@ def transform_submaps(submaps, T):
     lib = _lib.load()
     check(lib.cut3r_transform_submaps(_p(submaps), _p(T), B, per, _stream()), "cut3r_transform_submaps")
     return submaps
+
+
+# ------------------------------------------------------------------------------------------------ TSDF fusion / mesh extraction
+TSDF_MAX_VIEWS = 16
+
+
+def _tsdf_planes(tsdf, weight, color):
+    """(tsdf [Z,Y,X], weight [Z,Y,X], color [3,Z,Y,X]) fp32 contiguous GPU planes -> (X, Y, Z)"""
+    _cuda(tsdf, weight, color)
+    _req(tsdf.dim() == 3 and tsdf.dtype == F32 and tsdf.is_contiguous(), "tsdf: contiguous fp32 [Z,Y,X]")
+    Z, Y, X = tsdf.shape
+    _req(X > 0 and Y > 0 and Z > 0 and X * Y * Z < 2 ** 31, "TSDF grid: dims > 0 and X*Y*Z < 2^31")
+    _req(weight.shape == tsdf.shape and weight.dtype == F32 and weight.is_contiguous(), "weight: contiguous fp32 like tsdf")
+    _req(color.shape == (3, Z, Y, X) and color.dtype == F32 and color.is_contiguous(), "color: contiguous fp32 [3,Z,Y,X]")
+    return X, Y, Z
+
+
+def tsdf_integrate(tsdf, weight, color, origin, voxel, depth, w2c, K, trunc, depth_max, rgb=None, conf=None, conf_ds=1, conf_min=0.0):
+    """in place: fuse B <= 16 views (VoxelBlockGrid.integrate, tsdf_integrate.py:31-62) in one launch.  depth [B,H,W] fp32 metres, w2c
+    [B,12] / K [B,4] fp32 on the GPU, rgb u8 [B,3,H,W] or None, conf fp32 [B,h,w] at stride conf_ds with conf_min, or None."""
+    X, Y, Z = _tsdf_planes(tsdf, weight, color)
+    _cuda(depth, w2c, K, rgb, conf)
+    _req(depth.dim() == 3 and depth.dtype == F32 and depth.is_contiguous(), "depth: contiguous fp32 [B,H,W]")
+    B, H, W = depth.shape
+    _req(1 <= B <= TSDF_MAX_VIEWS, f"tsdf_integrate: 1..{TSDF_MAX_VIEWS} views per launch")
+    _req(H > 0 and W > 0, "depth: empty image")
+    _req(w2c.shape == (B, 12) and w2c.dtype == F32 and w2c.is_contiguous(), "w2c: contiguous fp32 [B,12]")
+    _req(K.shape == (B, 4) and K.dtype == F32 and K.is_contiguous(), "K: contiguous fp32 [B,4]")
+    _req(float(voxel) > 0 and float(trunc) > 0, "voxel size and truncation must be > 0")
+    if rgb is not None:
+        _req(rgb.shape == (B, 3, H, W) and rgb.dtype == torch.uint8 and rgb.is_contiguous(), "rgb: contiguous uint8 [B,3,H,W]")
+    ch = cw = 0
+    if conf is not None:
+        _req(conf.dim() == 3 and conf.shape[0] == B and conf.dtype == F32 and conf.is_contiguous(), "conf: contiguous fp32 [B,h,w]")
+        ch, cw = conf.shape[1:]
+        _req(int(conf_ds) >= 1 and ch > 0 and cw > 0, "conf: stride >= 1, non-empty")
+    lib = _lib.load()
+    check(lib.cut3r_tsdf_integrate(_p(tsdf), _p(weight), _p(color), X, Y, Z, float(origin[0]), float(origin[1]), float(origin[2]),
+                                   float(voxel), _p(depth), _p(rgb), _p(conf), B, H, W, ch, cw, int(conf_ds), float(conf_min), _p(w2c),
+                                   _p(K), float(trunc), float(depth_max), _stream()), "cut3r_tsdf_integrate")
+
+
+def tsdf_extract_mesh(tsdf, weight, color, origin, voxel, weight_threshold=1.0):
+    """marching tetrahedra over the fused planes (VoxelBlockGrid.extract_triangle_mesh, tsdf_integrate.py:83-88): count, scan, one
+    read-back of the two totals, emit -> (vertices fp32 [V,3], colors u8 [V,3], faces int32 [F,3]) on the GPU"""
+    X, Y, Z = _tsdf_planes(tsdf, weight, color)
+    _req(float(voxel) > 0, "voxel size must be > 0")
+    lib = _lib.load()
+    dev = tsdf.device
+    nbytes = lib.cut3r_tsdf_mesh_workspace_bytes(X, Y, Z)
+    _req(nbytes > 0, "TSDF grid too large")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    totals = torch.empty(2, dtype=torch.int64, device=dev)
+    check(lib.cut3r_tsdf_mesh_count(_p(tsdf), _p(weight), X, Y, Z, float(weight_threshold), _p(ws), nbytes, _p(totals), _stream()),
+          "cut3r_tsdf_mesh_count")
+    nv, nf = (int(v) for v in totals.cpu())
+    _req(nv < 2 ** 31, f"mesh of {nv} vertices: int32 face indices cannot address it")
+    verts = torch.empty(nv, 3, dtype=F32, device=dev)
+    cols = torch.empty(nv, 3, dtype=torch.uint8, device=dev)
+    faces = torch.empty(nf, 3, dtype=torch.int32, device=dev)
+    check(lib.cut3r_tsdf_mesh_emit(_p(tsdf), _p(color), X, Y, Z, float(origin[0]), float(origin[1]), float(origin[2]), float(voxel), _p(ws),
+                                   nbytes, _p(verts), _p(cols), _p(faces), nv, nf, _stream()), "cut3r_tsdf_mesh_emit")
+    return verts, cols, faces

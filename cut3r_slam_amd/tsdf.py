@@ -1,0 +1,270 @@
+"""Dense reconstruction: TSDF fusion of depth maps and triangle-mesh extraction on the gfx950 kernels of csrc/tsdf.hip.
+
+The reference makes a mesh after every run (scripts/run_replica.py:40-52 -> tsdf_integrate.py): the keyframe depth and colour renders
+of the Gaussian map go into an Open3D VoxelBlockGrid and `tsdf_mesh_w{w:.1f}.ply` is written per weight threshold.  Here:
+
+  TSDFVolume       a DENSE voxel grid in HBM (fp32 planes tsdf, weight, color[3]: 20 B per voxel; sparse blocks are not built)
+  fuse_keyframes   the tracker's keyframe store (depth, image, w2c, intrinsics, optional confidence gate) -> TSDFVolume
+  fuse_mapper      the reference's source: every mapper keyframe rendered at its refined pose, quantised as the reference's files are
+                   (hislam2/gaussian/utils/eval_utils.py:124-134: depth uint16 at 6553.5 per metre, colour (x*255) truncated to u8)
+  write_ply / read_ply   binary little-endian PLY (x y z float, red green blue uchar, vertex_indices uchar count + int32)
+
+Truncation: tsdf_integrate.py passes no sdf_trunc, so Open3D's default of 8 voxels applies; that is the default here
+(`trunc_voxels=8.0`), a choice, not something pinned by a run of the reference.
+"""
+from __future__ import annotations
+
+import math
+from typing import NamedTuple
+
+import numpy as np
+import torch
+
+from . import ops
+
+DEPTH_SCALE = 6553.5            # tsdf_integrate.py --depth_scale, eval_utils.py:131
+
+
+class Mesh(NamedTuple):
+    vertices: np.ndarray        # float32 [V,3]
+    colors: np.ndarray          # uint8 [V,3]
+    faces: np.ndarray           # int32 [F,3]
+
+
+class TSDFVolume:
+    """Dense TSDF grid: voxel (i, j, k) at origin + voxel_size * (i, j, k), planes [Z,Y,X] (x fastest); tsdf = 1, weight = color = 0 at start."""
+
+    def __init__(self, origin, voxel_size, dims, trunc_voxels=8.0, depth_max=5.0, device="cuda:0"):
+        X, Y, Z = (int(d) for d in dims)
+        if min(X, Y, Z) <= 0 or X * Y * Z >= 2 ** 31:
+            raise ValueError(f"TSDF grid {X}x{Y}x{Z}: dims must be > 0 and X*Y*Z < 2^31")
+        if not voxel_size > 0 or not trunc_voxels > 0:
+            raise ValueError("voxel_size and trunc_voxels must be > 0")
+        self.origin = tuple(float(np.float32(o)) for o in origin)
+        self.voxel_size = float(np.float32(voxel_size))
+        self.dims = (X, Y, Z)
+        self.trunc = float(np.float32(trunc_voxels * self.voxel_size))
+        self.depth_max = float(depth_max)
+        self.device = torch.device(device)
+        self.tsdf = torch.ones(Z, Y, X, dtype=torch.float32, device=self.device)
+        self.weight = torch.zeros(Z, Y, X, dtype=torch.float32, device=self.device)
+        self.color = torch.zeros(3, Z, Y, X, dtype=torch.float32, device=self.device)
+
+    @staticmethod
+    def grid_for(lo, hi, voxel_size, pad, max_voxels=2 ** 30):
+        """(origin, dims) of the grid over [lo - pad, hi + pad]; ValueError naming the memory when it exceeds max_voxels"""
+        lo = np.asarray(lo, np.float64) - pad
+        hi = np.asarray(hi, np.float64) + pad
+        if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(hi >= lo)):
+            raise ValueError(f"TSDF bounds {lo} .. {hi} are not a box")
+        dims = [int(math.ceil((h - l) / voxel_size - 1e-6)) + 1 for l, h in zip(lo, hi)]    # the last centre at >= hi
+        n = dims[0] * dims[1] * dims[2]
+        if n > max_voxels or n >= 2 ** 31:
+            raise ValueError(f"TSDF grid {dims[0]}x{dims[1]}x{dims[2]} = {n} voxels needs {n * 20 / 1e9:.1f} GB at 20 B per voxel "
+                             f"(limit {min(max_voxels, 2 ** 31 - 1)} voxels): raise voxel_size or max_voxels, or tighten the bounds")
+        return tuple(float(v) for v in lo), tuple(dims)
+
+    @classmethod
+    def from_bounds(cls, lo, hi, voxel_size, pad=None, max_voxels=2 ** 30, trunc_voxels=8.0, depth_max=5.0, device="cuda:0"):
+        """the grid covering the box [lo, hi] padded by `pad` (default: the truncation distance)"""
+        pad = trunc_voxels * voxel_size if pad is None else pad
+        origin, dims = cls.grid_for(lo, hi, voxel_size, pad, max_voxels)
+        return cls(origin, voxel_size, dims, trunc_voxels=trunc_voxels, depth_max=depth_max, device=device)
+
+    @property
+    def nbytes(self):
+        return 20 * self.dims[0] * self.dims[1] * self.dims[2]
+
+    @torch.no_grad()
+    def integrate(self, depth, w2c, K, rgb=None, conf=None, conf_ds=1, conf_min=None):
+        """fuse B views in order, in launches of <= 16.  depth [B,H,W] metres; w2c [B,12] (or [B,3,4] / [B,4,4]) world->camera; K [4] or
+        [B,4] fx fy cx cy; rgb u8 [B,3,H,W]; conf [B,h,w] at stride conf_ds, pixels with conf < conf_min skipped (conf_min None: no gate)."""
+        dev = self.device
+        depth = torch.as_tensor(depth).to(dev, torch.float32).contiguous()
+        if depth.dim() == 2:
+            depth = depth[None]
+        B = depth.shape[0]
+        w2c = torch.as_tensor(w2c).to(dev, torch.float32)
+        w2c = (w2c.reshape(B, -1, 4)[:, :3] if w2c.shape[-2:] in ((3, 4), (4, 4)) else w2c.reshape(B, 12)).reshape(B, 12).contiguous()
+        K = torch.as_tensor(K).to(dev, torch.float32).reshape(-1, 4)
+        K = (K.expand(B, 4) if K.shape[0] == 1 else K).contiguous()
+        if rgb is not None:
+            rgb = torch.as_tensor(rgb).to(dev).contiguous()
+        if conf is not None and conf_min is not None:
+            conf = torch.as_tensor(conf).to(dev, torch.float32).contiguous()
+        else:
+            conf = None
+        for a in range(0, B, ops.TSDF_MAX_VIEWS):
+            b = min(B, a + ops.TSDF_MAX_VIEWS)
+            ops.tsdf_integrate(self.tsdf, self.weight, self.color, self.origin, self.voxel_size, depth[a:b], w2c[a:b], K[a:b], self.trunc,
+                               self.depth_max, rgb=None if rgb is None else rgb[a:b], conf=None if conf is None else conf[a:b],
+                               conf_ds=conf_ds, conf_min=0.0 if conf_min is None else conf_min)
+        return self
+
+    @torch.no_grad()
+    def extract_mesh(self, weight_threshold=1.0) -> Mesh:
+        v, c, f = ops.tsdf_extract_mesh(self.tsdf, self.weight, self.color, self.origin, self.voxel_size, weight_threshold)
+        return Mesh(v.cpu().numpy(), c.cpu().numpy(), f.cpu().numpy())
+
+
+# ------------------------------------------------------------------------------------------------------------------------ PLY
+def write_ply(path, mesh: Mesh) -> None:
+    V, F = len(mesh.vertices), len(mesh.faces)
+    vert = np.empty(V, np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")]))
+    v = np.asarray(mesh.vertices, np.float32).reshape(V, 3)
+    c = np.asarray(mesh.colors, np.uint8).reshape(V, 3) if mesh.colors is not None else np.zeros((V, 3), np.uint8)
+    vert["x"], vert["y"], vert["z"] = v[:, 0], v[:, 1], v[:, 2]
+    vert["red"], vert["green"], vert["blue"] = c[:, 0], c[:, 1], c[:, 2]
+    face = np.empty(F, np.dtype([("n", "u1"), ("idx", "<i4", (3,))]))
+    face["n"] = 3
+    face["idx"] = np.asarray(mesh.faces, np.int32).reshape(F, 3)
+    header = ("ply\nformat binary_little_endian 1.0\n"
+              f"element vertex {V}\nproperty float x\nproperty float y\nproperty float z\n"
+              "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+              f"element face {F}\nproperty list uchar int vertex_indices\nend_header\n")
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        fh.write(vert.tobytes())
+        fh.write(face.tobytes())
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "<i2", "int16": "<i2", "ushort": "<u2", "uint16": "<u2",
+              "int": "<i4", "int32": "<i4", "uint": "<u4", "uint32": "<u4", "float": "<f4", "float32": "<f4", "double": "<f8",
+              "float64": "<f8"}
+
+
+def read_ply(path) -> Mesh:
+    """binary little-endian PLY with scalar vertex properties (x y z, optional red green blue) and triangle faces"""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    end = data.find(b"end_header\n")
+    if not data.startswith(b"ply\n") or end < 0:
+        raise ValueError(f"{path}: not a PLY file")
+    lines = data[:end].decode("ascii").splitlines()
+    if "format binary_little_endian 1.0" not in lines:
+        raise ValueError(f"{path}: only binary_little_endian PLY is read")
+    elements, cur = [], None
+    for ln in lines:
+        tok = ln.split()
+        if tok[:1] == ["element"]:
+            cur = [tok[1], int(tok[2]), []]
+            elements.append(cur)
+        elif tok[:1] == ["property"]:
+            cur[2].append(tok[1:])
+    off = end + len(b"end_header\n")
+    verts = cols = faces = None
+    for name, count, props in elements:
+        if name == "face":
+            if len(props) != 1 or props[0][0] != "list":
+                raise ValueError(f"{path}: faces must be one list property")
+            dt = np.dtype([("n", _PLY_TYPES[props[0][1]]), ("idx", _PLY_TYPES[props[0][2]], (3,))])
+            arr = np.frombuffer(data, dt, count, off)
+            if count and not np.all(arr["n"] == 3):
+                raise ValueError(f"{path}: only triangle faces are read")
+            faces = arr["idx"].astype(np.int32)
+        else:
+            if any(p[0] == "list" for p in props):
+                raise ValueError(f"{path}: list property in element {name}")
+            dt = np.dtype([(p[1], _PLY_TYPES[p[0]]) for p in props])
+            arr = np.frombuffer(data, dt, count, off)
+            if name == "vertex":
+                verts = np.stack([arr["x"], arr["y"], arr["z"]], 1).astype(np.float32)
+                if "red" in arr.dtype.names:
+                    cols = np.stack([arr["red"], arr["green"], arr["blue"]], 1).astype(np.uint8)
+        off += dt.itemsize * count
+    if verts is None:
+        raise ValueError(f"{path}: no vertex element")
+    return Mesh(verts, cols if cols is not None else np.zeros((len(verts), 3), np.uint8),
+                faces if faces is not None else np.zeros((0, 3), np.int32))
+
+
+# -------------------------------------------------------------------------------------------------------------------- sources
+@torch.no_grad()
+def depth_bounds(depth, w2c, K, depth_max):
+    """AABB (lo, hi) in world coordinates of the back-projected pixels with 0 < d <= depth_max (None when there is none)"""
+    B, H, W = depth.shape
+    dev = depth.device
+    rows = w2c.reshape(B, 3, 4).double()
+    R, t = rows[:, :, :3], rows[:, :, 3]
+    K = K.reshape(B, 4).double().to(dev)
+    v, u = torch.meshgrid(torch.arange(H, device=dev, dtype=torch.float64), torch.arange(W, device=dev, dtype=torch.float64), indexing="ij")
+    lo = torch.full((3,), math.inf, dtype=torch.float64, device=dev)
+    hi = -lo
+    for b in range(B):
+        d = depth[b].double()
+        ok = (d > 0) & (d <= depth_max)
+        if not bool(ok.any()):
+            continue
+        dd = d[ok]
+        pc = torch.stack([(u[ok] - K[b, 2]) / K[b, 0] * dd, (v[ok] - K[b, 3]) / K[b, 1] * dd, dd], 1)
+        pw = (pc - t[b]) @ R[b]                          # R^T (p - t)
+        lo = torch.minimum(lo, pw.min(0).values)
+        hi = torch.maximum(hi, pw.max(0).values)
+    if not bool(torch.isfinite(lo).all()):
+        return None
+    return lo.cpu().numpy(), hi.cpu().numpy()
+
+
+def _volume_for(depth, w2c, K, voxel_size, trunc_voxels, depth_max, bounds, max_voxels, device):
+    if bounds is None:
+        bounds = depth_bounds(depth, w2c, K, depth_max)
+        if bounds is None:
+            raise ValueError(f"no depth in (0, {depth_max}]: nothing to fuse")
+    return TSDFVolume.from_bounds(bounds[0], bounds[1], voxel_size, max_voxels=max_voxels, trunc_voxels=trunc_voxels, depth_max=depth_max,
+                                  device=device)
+
+
+@torch.no_grad()
+def fuse_keyframes(keyframes, n, voxel_size, trunc_voxels=8.0, depth_max=5.0, conf_min=None, bounds=None, max_voxels=2 ** 30):
+    """the tracker's keyframes 0..n-1: depth (s*z at tracking resolution), image, the device world->camera rows and the intrinsics; with
+    conf_min, pixels whose stored confidence (conf_ds[i // 5, i % 5], at the store's downsample ratio) is below it are skipped.
+    bounds: (lo, hi) or None = the AABB of the valid depths padded by the truncation distance."""
+    kf = keyframes
+    n = int(n)
+    if n <= 0:
+        raise ValueError("no tracked keyframes to fuse")
+    dev = kf.device
+    depth = kf.depth[:n].contiguous()
+    rgb = kf.image[:n].contiguous()
+    w2c = kf.w2c[:n].contiguous()
+    K = kf.intrinsic[:n].to(dev, torch.float32).contiguous()
+    conf = None
+    if conf_min is not None:
+        idx = torch.arange(n, device=dev)
+        conf = kf.conf_ds[idx // 5, idx % 5].contiguous()
+    vol = _volume_for(depth, w2c, K, voxel_size, trunc_voxels, depth_max, bounds, max_voxels, dev)
+    return vol.integrate(depth, w2c, K, rgb=rgb, conf=conf, conf_ds=kf.downsample_ratio, conf_min=conf_min)
+
+
+@torch.no_grad()
+def render_mapper_views(mapper):
+    """per mapper keyframe (sorted): quantised depth [H,W] (metres), colour u8 [3,H,W], w2c rows [12], K [4] -- what the reference's
+    eval_rendering_kf writes to renders_kf/{depth,image}_after_opt and tsdf_integrate.py reads back"""
+    from .gs_mapper import get_pose, render
+    depths, rgbs, w2cs, Ks = [], [], [], []
+    for k in sorted(mapper.viewpoints):
+        v = mapper.viewpoints[k]
+        pkg = render(v, mapper.gaussians, mapper.background)
+        image = pkg["render"]
+        if getattr(v, "exposure_a", None) is not None:                  # eval_utils.py:123
+            image = (image.permute(1, 2, 0) @ v.exposure_a + v.exposure_b).permute(2, 0, 1)
+        image = torch.clamp(image, 0.0, 1.0)
+        rgbs.append((image * 255).to(torch.uint8))                     # numpy astype(uint8): truncation
+        d = pkg["depth"].reshape(image.shape[-2:]).float()
+        depths.append(torch.floor(torch.clamp(d * DEPTH_SCALE, 0, 65535)) / DEPTH_SCALE)
+        w2cs.append(get_pose(v).detach()[:3, :4].reshape(12).float())
+        Ks.append(torch.tensor([v.fx, v.fy, v.cx, v.cy], dtype=torch.float32))
+    dev = mapper.device
+    return (torch.stack(depths).contiguous(), torch.stack(rgbs).contiguous(), torch.stack(w2cs).contiguous(),
+            torch.stack(Ks).to(dev).contiguous())
+
+
+@torch.no_grad()
+def fuse_mapper(mapper, voxel_size, trunc_voxels=8.0, depth_max=5.0, bounds=None, max_voxels=2 ** 30):
+    """the reference's source (tsdf_integrate.py over renders_kf/*_after_opt): every mapper keyframe rendered at its refined pose.  The
+    intrinsics are the views' own, as the reference passes intrinsics.npy unchanged."""
+    if not mapper.viewpoints:
+        raise ValueError("the mapper has no keyframes to fuse")
+    depth, rgb, w2c, K = render_mapper_views(mapper)
+    vol = _volume_for(depth, w2c, K, voxel_size, trunc_voxels, depth_max, bounds, max_voxels, mapper.device)
+    return vol.integrate(depth, w2c, K, rgb=rgb)

@@ -4,7 +4,8 @@
     python demo.py --imagedir data/Replica/room0/colors --calib calib/replica.txt --config config/replica_config.yaml \\
                    --output outputs/room0 [--kf_every 10] [--ckpt_path checkpoints/cut3r_512_dpt_4_64.pth]
 
-Writes <output>/traj_kf.txt and <output>/intrinsics.npy exactly as the reference does (evo-compatible TUM rows).  The
+Writes <output>/traj_kf.txt and <output>/intrinsics.npy exactly as the reference does (evo-compatible TUM rows); with --mesh also
+<output>/tsdf_mesh_w{W:.1f}.ply per --mesh-weight, the reference's post-run mesh (TSDF fusion on the GPU, cut3r_slam_amd/tsdf.py).  The
 Gaussian-splatting mapper and its viewers are out of scope: --droidvis/--gsvis/--gtdepthdir/--posedir/
 --weights are accepted and ignored.  Without a checkpoint, `--synthetic-weights` runs the production-shape network with
 seeded random weights (throughput / plumbing runs only).
@@ -70,6 +71,13 @@ def main(argv=None):
                    "position_lr_max_steps, as the reference; 0 skips it)")
     p.add_argument("--gs", action="store_true", help="attach the Gaussian-splatting mapper (hislam2/hi2.py:47-48 always does; needs the "
                    "Mapping / Training / opt_params sections of the config, config/scannet_config.yaml:44-79)")
+    p.add_argument("--mesh", action="store_true", help="TSDF-fuse the keyframes and write <output>/tsdf_mesh_w{W:.1f}.ply per weight threshold "
+                   "(scripts/run_replica.py:40-52 + tsdf_integrate.py)")
+    p.add_argument("--voxel-size", type=float, default=0.03, help="TSDF voxel size in scene units (tsdf_integrate.py default)")
+    p.add_argument("--depth-max", type=float, default=5.0, help="depths beyond this are not fused")
+    p.add_argument("--mesh-weight", type=float, nargs="+", default=[1.0], help="weight thresholds of the extracted meshes")
+    p.add_argument("--mesh-source", choices=("auto", "tracker", "mapper"), default="auto",
+                   help="auto: the Gaussian map's keyframe renders with --gs, else the tracked keyframes")
     args = p.parse_args(argv)
     os.makedirs(args.output, exist_ok=True)
 
@@ -143,6 +151,21 @@ def main(argv=None):
         slam.mapper.save(os.path.join(args.output, "gaussians.safetensors"))
         print(f"GS mapper: {len(slam.mapper.gaussians)} Gaussians, {len(slam.mapper.viewpoints)} keyframes, PSNR {ev['mean_psnr']:.2f} dB, "
               f"SSIM {ev['mean_ssim']:.4f} -> {args.output}/gaussians.safetensors")
+    if args.mesh:
+        from cut3r_slam_amd.tsdf import write_ply
+        t_int = time.time()
+        vol = slam.fuse(args.voxel_size, depth_max=args.depth_max, source=args.mesh_source)
+        torch.cuda.synchronize()
+        t_int = time.time() - t_int
+        X, Y, Z = vol.dims
+        print(f"TSDF: {X}x{Y}x{Z} voxels of {vol.voxel_size:g} ({vol.nbytes / 1e9:.2f} GB), integrated in {1e3 * t_int:.1f} ms")
+        for w in args.mesh_weight:
+            t_ext = time.time()
+            mesh = vol.extract_mesh(w)
+            t_ext = time.time() - t_ext
+            path = os.path.join(args.output, f"tsdf_mesh_w{w:.1f}.ply")
+            write_ply(path, mesh)
+            print(f"mesh w >= {w:g}: {len(mesh.vertices)} vertices, {len(mesh.faces)} faces, extracted in {1e3 * t_ext:.1f} ms -> {path}")
     print(f"{nframes} frames, {len(traj)} keyframes, {len(slam.graph.edges_numpy()[0])} graph edges in {time.time() - t0:.1f}s "
           f"-> {args.output}/traj_kf.txt")
     return 0

@@ -473,6 +473,32 @@ int cut3r_refine_loss_forward(const float* img, const float* gt_img, const float
 int cut3r_refine_loss_backward(const float* img, const float* gt_img, const float* depth, const float* gt_depth, const float* alpha,
                                float alpha_th, int H, int W, const float* coef, float* grad_img, float* grad_depth, void* stream);
 
+/* ---- TSDF fusion and mesh extraction (csrc/tsdf.hip) -------------------------------------------------------------------------------
+ * A DENSE grid replaces the Open3D VoxelBlockGrid of tsdf_integrate.py: fp32 planes tsdf [N], weight [N], color [3][N] (0..255), N =
+ * X*Y*Z < 2^31, voxel n = (k*Y + j)*X + i, centre (ox + voxel*i, oy + voxel*j, oz + voxel*k).  Initial values tsdf = 1, weight = color = 0.
+ *
+ * integrate replaces VoxelBlockGrid.integrate (tsdf_integrate.py:31-62): B in 1..16 views applied in order, each voxel read and written
+ * at most once per call.  depth [B,H,W] fp32 metres, rgb u8 [B,3,H,W] or NULL (colours untouched), conf [B,ch,cw] at stride ds or NULL
+ * (a pixel with conf[min(v/ds,ch-1), min(u/ds,cw-1)] < conf_min is skipped), w2c [B,12] world->camera rows, K [B,4] fx fy cx cy, all on
+ * the device.  Per view in fp32: x_c = ((r0 . p) + t); skip z_c <= 0; u = fx x_c / z_c + cx rounded floor(u + 0.5), outside the image
+ * skipped; skip !(0 < d <= depth_max); sdf = d - z_c, skip sdf < -trunc; t = min(1, sdf / trunc); running weighted means, weight + 1.
+ *
+ * mesh_count / mesh_emit replace VoxelBlockGrid.extract_triangle_mesh (tsdf_integrate.py:83-88) by marching tetrahedra over the Kuhn split
+ * (six tetrahedra per cell along the corner 0 -> 7 diagonal).  A cell is valid when its 8 corners have weight >= weight_threshold; inside
+ * = tsdf < 0; triangles face from negative to positive tsdf.  count writes per-voxel counts into `workspace`
+ * (cut3r_tsdf_mesh_workspace_bytes: 18 B per voxel + scan scratch), scans them and writes totals [2] = (vertices, faces) as int64 on the
+ * device; emit (same workspace, untouched in between) writes verts [nv,3] fp32, colors [nv,3] u8 (NULL: none) and faces [nf,3] int32:
+ * vertices in (owning voxel, direction mask) order, faces in (cell, tetrahedron, triangle) order, only referenced vertices. */
+int cut3r_tsdf_integrate(float* tsdf, float* weight, float* color, int X, int Y, int Z, float ox, float oy, float oz, float voxel,
+                         const float* depth, const unsigned char* rgb, const float* conf, int B, int H, int W, int ch, int cw, int ds,
+                         float conf_min, const float* w2c, const float* K, float trunc, float depth_max, void* stream);
+long long cut3r_tsdf_mesh_workspace_bytes(int X, int Y, int Z);       /* -1 on bad dimensions */
+int cut3r_tsdf_mesh_count(const float* tsdf, const float* weight, int X, int Y, int Z, float weight_threshold, void* workspace,
+                          long long workspace_bytes, long long* totals, void* stream);
+int cut3r_tsdf_mesh_emit(const float* tsdf, const float* color, int X, int Y, int Z, float ox, float oy, float oz, float voxel,
+                         const void* workspace, long long workspace_bytes, float* verts, unsigned char* colors, int* faces, long long nv,
+                         long long nf, void* stream);
+
 /* Measurement aid of bench.py's roofline (no reference counterpart; not on the product path): a bare MFMA loop (v_mfma_f32_16x16x32_f16,
  * 16 independent accumulator chains per wave, 8 waves per workgroup, `grid` workgroups, `iters` x 16 MFMAs per wave, operands = 16-byte
  * chunks of data[nhalf] fp16, nhalf a power of two >= 32768) with s_memtime / s_memrealtime stamps around the loop.  stamps [grid,2] u64 =
