@@ -15,8 +15,9 @@ rasteriser.  Mirrors, with the same names, argument meaning
 
 The reference's backend cannot run here (CUDA rasteriser, open3d, munch): PARITY UNPINNED, covered by functional tests on a
 synthetic scene (tests/test_gs_mapper_gpu.py).  The rasteriser and the 3-NN search are the HIP kernels of csrc/gs.hip; the loss
-terms and the Adam updates are plain torch tensor arithmetic on the GPU.  Not built: GUI, Gaussian ply export, LPIPS and the reconstruction metrics (PSNR / SSIM of the keyframes,
-a safetensors checkpoint and -- cut3r_slam_amd/tsdf.py, fuse_mapper -- the TSDF mesh of the keyframe renders are).
+terms and the Adam updates are plain torch tensor arithmetic on the GPU.  Not built: GUI, Gaussian ply export and LPIPS (PSNR / SSIM of the keyframes,
+a safetensors checkpoint, -- cut3r_slam_amd/tsdf.py, fuse_mapper -- the TSDF mesh of the keyframe renders and -- eval_recon.py -- its
+reconstruction metrics are).
 `gaussain_update` (the map correction after a loop closure, :701-774) composes rotations consistently by default; see its docstring."""
 from __future__ import annotations
 

@@ -768,3 +768,107 @@ def tsdf_extract_mesh(tsdf, weight, color, origin, voxel, weight_threshold=1.0):
     check(lib.cut3r_tsdf_mesh_emit(_p(tsdf), _p(color), X, Y, Z, float(origin[0]), float(origin[1]), float(origin[2]), float(voxel), _p(ws),
                                    nbytes, _p(verts), _p(cols), _p(faces), nv, nf, _stream()), "cut3r_tsdf_mesh_emit")
     return verts, cols, faces
+
+
+# ------------------------------------------------------------------------------------------------ reconstruction metrics
+def _points(t, name):
+    _cuda(t)
+    _req(t.dim() == 2 and t.shape[1] == 3 and t.dtype == F32 and t.is_contiguous(), f"{name}: contiguous fp32 [N,3]")
+    _req(0 < t.shape[0] < 2 ** 31, f"{name}: 1 .. 2^31 - 1 points")
+    _req(bool(torch.isfinite(t).all()), f"{name}: non-finite coordinates")
+    return t.shape[0]
+
+
+def _transform34(T, dev):
+    if T is None:
+        return None
+    T = torch.as_tensor(T, dtype=torch.float64).reshape(-1)
+    _req(T.numel() in (12, 16), "transform: 3x4 or 4x4")
+    T = T[:12].to(dev, F32).contiguous()
+    _req(bool(torch.isfinite(T).all()), "transform: non-finite entries")
+    return T
+
+
+def mesh_area_cdf(verts, faces):
+    """face areas fp32 [F] and their inclusive fp64 scan [F] (the area weights of trimesh.sample.sample_surface, eval_recon.py:104-107);
+    faces int32 [F,3] must index verts"""
+    V = _points(verts, "verts")
+    _cuda(faces)
+    _req(faces.dim() == 2 and faces.shape[1] == 3 and faces.dtype == torch.int32 and faces.is_contiguous(), "faces: contiguous int32 [F,3]")
+    F = faces.shape[0]
+    _req(0 < F < 2 ** 31, "faces: 1 .. 2^31 - 1 faces")
+    _req(int(faces.min()) >= 0 and int(faces.max()) < V, "faces: vertex index out of range")
+    lib = _lib.load()
+    nbytes = lib.cut3r_mesh_cdf_workspace_bytes(F)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=verts.device)
+    area = torch.empty(F, dtype=F32, device=verts.device)
+    cdf = torch.empty(F, dtype=torch.float64, device=verts.device)
+    check(lib.cut3r_mesh_area_cdf(_p(verts), V, _p(faces), F, _p(area), _p(cdf), _p(ws), nbytes, _stream()), "cut3r_mesh_area_cdf")
+    return area, cdf
+
+
+def mesh_sample(verts, faces, cdf, n, seed=0, stream_id=0):
+    """n points [n,3] fp32, uniform over the surface by area (cdf from mesh_area_cdf); sample i depends on (seed, stream_id, i) only"""
+    V = _points(verts, "verts")
+    _cuda(faces, cdf)
+    _req(faces.dim() == 2 and faces.shape[1] == 3 and faces.dtype == torch.int32 and faces.is_contiguous(), "faces: contiguous int32 [F,3]")
+    F = faces.shape[0]
+    _req(F > 0 and cdf.shape == (F,) and cdf.dtype == torch.float64 and cdf.is_contiguous(), "cdf: contiguous fp64 [F]")
+    _req(int(n) > 0, "n must be > 0")
+    _req(float(cdf[-1]) > 0, "mesh has zero total area")
+    out = torch.empty(int(n), 3, dtype=F32, device=verts.device)
+    lib = _lib.load()
+    check(lib.cut3r_mesh_sample(_p(verts), V, _p(faces), F, _p(cdf), int(n), int(seed) % 2 ** 64, int(stream_id) % 2 ** 64, _p(out), _stream()),
+          "cut3r_mesh_sample")
+    return out
+
+
+class NNGrid:
+    """exact 1-NN searches among a fixed reference set ref [P,3] fp32 (cKDTree(ref).query, eval_recon.py:22-41): the grid is built once,
+    then query() any number of query sets of up to `max_queries` points"""
+
+    def __init__(self, ref, max_queries):
+        self.P = _points(ref, "ref")
+        self.ref = ref
+        self.max_queries = int(max_queries)
+        _req(0 < self.max_queries < 2 ** 31, "max_queries: 1 .. 2^31 - 1")
+        lib = _lib.load()
+        self.nbytes = lib.cut3r_nn_workspace_bytes(self.P, self.max_queries)
+        _req(self.nbytes > 0, "NN workspace")
+        self.ws = torch.empty(self.nbytes, dtype=torch.uint8, device=ref.device)
+        check(lib.cut3r_nn_build(_p(ref), self.P, _p(self.ws), self.nbytes, _stream()), "cut3r_nn_build")
+
+    def query(self, query, max_dist=None, transform=None):
+        """(dist2 fp32 [Q], idx int32 [Q]) of every query point (under `transform`, 3x4 or 4x4, applied in fp32 on load); ties to the
+        smallest reference index; no reference point with d2 <= max_dist^2: idx -1, dist2 +inf"""
+        Q = _points(query, "query")
+        _req(Q <= self.max_queries, f"query: {Q} points, the grid was sized for {self.max_queries}")
+        md = float("inf") if max_dist is None else float(max_dist)
+        _req(md >= 0, "max_dist must be >= 0")
+        T = _transform34(transform, query.device)
+        dist2 = torch.empty(Q, dtype=F32, device=query.device)
+        idx = torch.empty(Q, dtype=torch.int32, device=query.device)
+        lib = _lib.load()
+        check(lib.cut3r_nn_query(self.P, _p(query), Q, _p(T), md, _p(dist2), _p(idx), _p(self.ws), self.nbytes, _stream()), "cut3r_nn_query")
+        return dist2, idx
+
+    def moments(self, query, dist2, idx, transform=None):
+        """fp64 [17] over the correspondences idx >= 0: count, sum dist2, sum src [3], sum dst [3], sum src_a dst_b [3,3] (src = the query
+        point under `transform` as query() loaded it, dst = ref[idx])"""
+        Q = _points(query, "query")
+        _cuda(dist2, idx)
+        _req(dist2.shape == (Q,) and dist2.dtype == F32 and idx.shape == (Q,) and idx.dtype == torch.int32, "dist2 / idx of this query")
+        _req(int(idx.max()) < self.P, "idx: reference index out of range")
+        T = _transform34(transform, query.device)
+        lib = _lib.load()
+        nbytes = lib.cut3r_icp_moments_workspace_bytes(Q)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=query.device)
+        out = torch.empty(17, dtype=torch.float64, device=query.device)
+        check(lib.cut3r_icp_moments(_p(query), Q, _p(self.ref), self.P, _p(T), _p(dist2), _p(idx.contiguous()), _p(out), _p(ws), nbytes,
+                                    _stream()), "cut3r_icp_moments")
+        return out
+
+
+def nn_query(ref, query, max_dist=None, transform=None):
+    """one-shot NNGrid(ref).query(query)"""
+    return NNGrid(ref, query.shape[0] if query.dim() == 2 else 0).query(query, max_dist=max_dist, transform=transform)

@@ -78,7 +78,15 @@ def main(argv=None):
     p.add_argument("--mesh-weight", type=float, nargs="+", default=[1.0], help="weight thresholds of the extracted meshes")
     p.add_argument("--mesh-source", choices=("auto", "tracker", "mapper"), default="auto",
                    help="auto: the Gaussian map's keyframe renders with --gs, else the tracked keyframes")
+    p.add_argument("--gt-mesh", type=str, default=None, help="score every mesh written against this GT mesh (scripts/eval_recon.py "
+                   "--eval_3d) -> <output>/eval_recon_w{W:.1f}.txt; needs --mesh")
+    p.add_argument("--gt-traj", type=str, default=None, help="TUM ground-truth trajectory: the Sim(3) of traj_kf.txt onto it is applied to "
+                   "the mesh before scoring (scripts/run_replica.py:45-46)")
     args = p.parse_args(argv)
+    if args.gt_mesh and not args.mesh:
+        p.error("--gt-mesh needs --mesh")
+    if args.gt_traj and not args.gt_mesh:
+        p.error("--gt-traj needs --gt-mesh")
     os.makedirs(args.output, exist_ok=True)
 
     from cut3r_slam_amd import stream
@@ -166,6 +174,15 @@ def main(argv=None):
             path = os.path.join(args.output, f"tsdf_mesh_w{w:.1f}.ply")
             write_ply(path, mesh)
             print(f"mesh w >= {w:g}: {len(mesh.vertices)} vertices, {len(mesh.faces)} faces, extracted in {1e3 * t_ext:.1f} ms -> {path}")
+            if args.gt_mesh and len(mesh.faces):
+                from cut3r_slam_amd import eval_recon as ER
+                if args.gt_traj:
+                    mesh = ER.apply_transform(mesh, ER.sim3_from_trajectories(os.path.join(args.output, "traj_kf.txt"), args.gt_traj))
+                res = ER.calc_3d_metric(mesh, args.gt_mesh)
+                with open(os.path.join(args.output, f"eval_recon_w{w:.1f}.txt"), "w") as fh:
+                    fh.write(f"{res}")
+                print(f"  vs {args.gt_mesh}: accuracy {res['accuracy']:.3f} cm, completion {res['completion']:.3f} cm, "
+                      f"completion ratio {res['completion_ratio']:.2f} %")
     print(f"{nframes} frames, {len(traj)} keyframes, {len(slam.graph.edges_numpy()[0])} graph edges in {time.time() - t0:.1f}s "
           f"-> {args.output}/traj_kf.txt")
     return 0

@@ -499,6 +499,34 @@ int cut3r_tsdf_mesh_emit(const float* tsdf, const float* color, int X, int Y, in
                          const void* workspace, long long workspace_bytes, float* verts, unsigned char* colors, int* faces, long long nv,
                          long long nf, void* stream);
 
+/* ---- Reconstruction metrics (csrc/recon.hip) ----------------------------------------------------------------------------------------
+ * mesh_area_cdf / mesh_sample replace trimesh.sample.sample_surface (scripts/eval_recon.py:104-107).  verts [V,3] fp32, faces [F,3] int32
+ * (a face with an index outside 0..V-1 has area 0).  area_cdf: area [F] fp32 = 0.5 |(b - a) x (c - a)|, cdf [F] fp64 = inclusive scan of
+ * the areas; workspace: cut3r_mesh_cdf_workspace_bytes(F).  sample: out [n,3]; sample i takes the first face with cdf[f] > u0 cdf[F-1]
+ * and p = (a + u1 (b - a)) + u2 (c - a), (u1, u2) -> (1 - u1, 1 - u2) when u1 + u2 > 1; u_k from splitmix64 of (seed, stream_id, 3i + k):
+ * u0 53 bits, u1 and u2 24 bits.  Sample i does not depend on n. */
+long long cut3r_mesh_cdf_workspace_bytes(int F);                      /* -1 when F <= 0 */
+int cut3r_mesh_area_cdf(const float* verts, int V, const int* faces, int F, float* area, double* cdf, void* workspace, long long workspace_bytes,
+                        void* stream);
+int cut3r_mesh_sample(const float* verts, int V, const int* faces, int F, const double* cdf, long long n, unsigned long long seed,
+                      unsigned long long stream_id, float* out, void* stream);
+/* exact 1-NN of every query point among the reference points: scipy cKDTree.query of eval_recon.py:22-41, pykdtree of
+ * geometry_eval_utils.py:79-110 and the correspondence search of Open3D registration_icp (eval_recon.py:44-58).  build bins ref [P,3]
+ * into a uniform grid inside `workspace` (cut3r_nn_workspace_bytes(P, Q) bytes; build needs (P, 0)); query (the same workspace, built for
+ * the same P, untouched in between) transforms each query [Q,3] by T (fp32 3x4 row-major, NULL: identity) as it loads it and writes
+ * dist2 [Q] fp32 (d2 = dx*dx + dy*dy + dz*dz, dx = ref.x - q.x) and idx [Q] int32, ties to the smallest reference index.  A query with no
+ * reference point at d2 <= max_dist^2 gets idx -1, dist2 +inf (max_dist = +inf: no limit; < 0 or NaN is refused). */
+long long cut3r_nn_workspace_bytes(int P, int Q);                     /* -1 when P <= 0 or Q < 0 */
+int cut3r_nn_build(const float* ref, int P, void* workspace, long long workspace_bytes, void* stream);
+int cut3r_nn_query(int P, const float* query, int Q, const float* T, float max_dist, float* dist2, int* idx, void* workspace,
+                   long long workspace_bytes, void* stream);
+/* the moments of one point-to-point ICP update (TransformationEstimationPointToPoint, eval_recon.py:54-56) in fp64 over the
+ * correspondences (idx >= 0) of a query: out [17] = count, sum dist2, sum src [3], sum dst [3], sum src_a dst_b [3][3], src = the query
+ * point under T as cut3r_nn_query loads it, dst = ref[idx].  Identical on every run.  workspace: cut3r_icp_moments_workspace_bytes(Q). */
+long long cut3r_icp_moments_workspace_bytes(int Q);                   /* -1 when Q <= 0 */
+int cut3r_icp_moments(const float* src, int Q, const float* ref, int P, const float* T, const float* dist2, const int* idx, double* out,
+                      void* workspace, long long workspace_bytes, void* stream);
+
 /* Measurement aid of bench.py's roofline (no reference counterpart; not on the product path): a bare MFMA loop (v_mfma_f32_16x16x32_f16,
  * 16 independent accumulator chains per wave, 8 waves per workgroup, `grid` workgroups, `iters` x 16 MFMAs per wave, operands = 16-byte
  * chunks of data[nhalf] fp16, nhalf a power of two >= 32768) with s_memtime / s_memrealtime stamps around the loop.  stamps [grid,2] u64 =
