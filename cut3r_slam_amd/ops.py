@@ -293,7 +293,8 @@ def _linear_desc(A, W, out, bias, act, res1, tile, rope=None, ln=None, emit=None
 def linear_pair(p0, p1, act=0, tile=0):
     """Two independent linears in ONE launch (cut3r_gemm_f16_pair): p = (A [M,K], W [N,K], out [M,N], bias | None, res1 | None[, extras]) with
     the same N and K; rows are bit-identical to ops.linear.  The decoder runs its state-side and image-side projection of a layer this
-    way.  extras: dict with any of rope / ln / emit as in ops.linear (per problem)."""
+    way.  extras: dict with any of rope / ln / emit as in ops.linear (per problem).  `tile` is written into both descriptors; the C side reads
+    the first one's only (both problems run the same tile kernel)."""
     x0 = p0[5] if len(p0) > 5 and p0[5] else {}
     x1 = p1[5] if len(p1) > 5 and p1[5] else {}
     d0 = _linear_desc(p0[0], p0[1], p0[2], p0[3], act, p0[4], tile, **x0)
