@@ -1,11 +1,13 @@
-"""Reconstruction metrics of a mesh against a ground-truth mesh on the gfx950 kernels of csrc/recon.hip: the 3-D half of the reference's
-scripts/eval_recon.py (accuracy, completion, completion ratio over 200 000 surface samples per mesh, after a point-to-point ICP of the
-mesh vertices onto the GT vertices) and the clipped Chamfer distances of geometry_eval_utils.py:79-110.
+"""Reconstruction metrics of a mesh against a ground-truth mesh on the gfx950 kernels of csrc/recon.hip and csrc/raster.hip: the 3-D half
+of the reference's scripts/eval_recon.py (accuracy, completion, completion ratio over 200 000 surface samples per mesh, after a
+point-to-point ICP of the mesh vertices onto the GT vertices), its 2-D half (the depth L1 between renders of the two meshes from random
+viewpoints inside the room) and the clipped Chamfer distances of geometry_eval_utils.py:79-110.
 
   sample_surface         area-weighted uniform samples (trimesh.sample.sample_surface), counter-based: sample i depends on (seed, stream, i)
   accuracy / completion / completion_ratio     mean distance rec -> GT, GT -> rec, share of GT samples closer than dist_th (strict <)
   get_align_transformation                     Open3D registration_icp point-to-point with its defaults, as eval_recon.py:44-58 calls it
   calc_3d_metric / eval_recon                  eval_recon.py:92-116 (cm and %)
+  check_proj / get_cam_position / sample_views / calc_2d_metric     eval_recon.py:60-89, 118-223 ('depth l1' in cm)
   chamfer_distance / chamfer_distance_RMSE     geometry_eval_utils.py:79-110
   voxel_down_sample                            Open3D's PointCloud.voxel_down_sample (eval7_scenes_dense.py:238-250), output sorted by voxel
   sim3_from_trajectories                       the Sim(3) that run_replica.py:45-46 applies to the mesh before it is scored
@@ -158,12 +160,147 @@ def calc_3d_metric(rec_mesh, gt_mesh, align=True, samples=N_SAMPLES, seed=0):
     return {"accuracy": acc * 100, "completion": comp * 100, "completion_ratio": ratio * 100}
 
 
-def eval_recon(rec_mesh, gt_mesh, eval_3d=True, align=True, samples=N_SAMPLES, seed=0):
-    """eval_recon.py:226-250 without the 2-D depth metric and the external run_evaluation"""
+def eval_recon(rec_mesh, gt_mesh, eval_3d=True, align=True, samples=N_SAMPLES, seed=0, eval_2d=False, n_imgs=10, unseen=None):
+    """eval_recon.py:226-250 without the external run_evaluation; the 2-D depth metric (n_imgs views, 10 as eval_recon.py:238) only with
+    eval_2d"""
     result = {}
     if eval_3d:
         result.update(calc_3d_metric(rec_mesh, gt_mesh, align=align, samples=samples, seed=seed))
+    if eval_2d:
+        result.update(calc_2d_metric(rec_mesh, gt_mesh, align=align, n_imgs=n_imgs, unseen=unseen, seed=seed))
     return result
+
+
+# ------------------------------------------------------------------------------------------------------------------- 2-D metric
+EDGE = 10                          # eval_recon.py:86
+_M64 = (1 << 64) - 1
+
+
+def _splitmix64(z):
+    z = np.asarray(z, np.uint64) + np.uint64(0x9E3779B97F4A7C15)
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def _uniform(seed, views, attempts, ncomp):
+    """fp64 [len(views), ncomp] in [0, 1): the project's counter-based splitmix64 (csrc/recon.hip) with stream = view and counter =
+    8 * try + component, 53 bits each"""
+    with np.errstate(over="ignore"):
+        key = _splitmix64(_splitmix64(np.array([int(seed) & _M64], np.uint64)) ^ np.asarray(views, np.uint64))
+        ctr = np.uint64(8) * np.asarray(attempts, np.uint64)[:, None] + np.arange(ncomp, dtype=np.uint64)[None]
+        h = _splitmix64(key[:, None] ^ ctr)
+    return (h >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+
+
+def check_proj(points, W, H, fx, fy, cx, cy, c2w) -> bool:
+    """eval_recon.py:60-89: does the camera c2w see one of the points inside the image shrunk by 10 pixels.
+
+    The reference negates the y and z columns of c2w, inverts, negates the camera x, multiplies by K, adds 1e-5 to the third component
+    and tests `0 <= -z`.  With (x, y, z) the point in the plain OpenCV camera inv(c2w), its camera coordinates are (-x, -y, -z), K maps
+    them to (-(fx x + cx z), -(fy y + cy z), -z), and the signs cancel in the division: u = (fx x + cx z) / z', v = (fy y + cy z) / z'
+    with z' = z - 1e-5, tested as 0 <= z', 10 < u < W - 10, 10 < v < H - 10.  That is what cut3r_points_in_view evaluates (fp32)."""
+    w2c = np.linalg.inv(np.asarray(c2w, np.float64).reshape(4, 4))[None, :3]
+    return bool(int(ops.points_in_view(as_points(points), w2c, [fx, fy, cx, cy], H, W, EDGE)[0]) > 0)
+
+
+def get_cam_position(gt_mesh):
+    """(extents [3], transform [4,4]) of the box camera positions are drawn from (eval_recon.py:118-126).  DEVIATION: the reference takes
+    trimesh's minimum-volume oriented box of the GT mesh; trimesh is not available here, so this is the axis-aligned box of the GT
+    vertices, with the reference's three factors applied as 0.3 on the shortest axis and 0.7 on the other two and the centre raised by
+    0.4 along world z.  For a room whose walls are not axis-aligned the two differ, and nobody has compared them: pass your own box to
+    sample_views where it matters."""
+    v = np.asarray(as_mesh(gt_mesh).vertices, np.float64)
+    lo, hi = v.min(0), v.max(0)
+    fac = np.full(3, 0.7)
+    fac[np.argmin(hi - lo)] = 0.3
+    T = np.eye(4)
+    T[:3, 3] = 0.5 * (lo + hi)
+    T[2, 3] += 0.4
+    return (hi - lo) * fac, T
+
+
+def viewmatrix(z, up, pos) -> np.ndarray:
+    """eval_recon.py:129-135 as a 4x4 c2w: columns normalize(up x z), z x that, normalize(z), pos"""
+    unit = lambda x: x / np.linalg.norm(x)
+    v2 = unit(np.asarray(z, np.float64))
+    v0 = unit(np.cross(up, v2))
+    v1 = unit(np.cross(v2, v0))
+    m = np.eye(4)
+    m[:3] = np.stack([v0, v1, v2, np.asarray(pos, np.float64)], 1)
+    return m
+
+
+def sample_views(extents, transform, n, unseen=None, seed=0, max_tries=1000, W=500, H=500, focal=300.0) -> np.ndarray:
+    """n camera poses c2w [n,4,4] (eval_recon.py:166-187): position uniform in the box (extents, transform), looking at a target uniform
+    in [-10000, 10000]^3 rounded to 2 decimals, up (0, 0, -1); a candidate that sees one of the `unseen` points (check_proj) is redrawn.
+    Candidate `try` of view k is a function of (seed, k, try) only, so view k does not depend on n.  The reference loops for ever when no
+    candidate qualifies; here max_tries rejections in a row raise RuntimeError.  The candidates of one round are tested in one batch."""
+    extents, transform = np.asarray(extents, np.float64).reshape(3), np.asarray(transform, np.float64).reshape(4, 4)
+    out = np.zeros((int(n), 4, 4))
+    pts = None if unseen is None or len(unseen) == 0 else as_points(unseen)
+    K = [focal, focal, W / 2.0 - 0.5, H / 2.0 - 0.5]
+    todo = np.arange(int(n))
+    for attempt in range(int(max_tries)):
+        if len(todo) == 0:
+            break
+        u = _uniform(seed, todo, np.full(len(todo), attempt), 6)
+        pos = ((u[:, :3] - 0.5) * extents) @ transform[:3, :3].T + transform[:3, 3]
+        target = np.array([[round(-10000.0 + 20000.0 * x, 2) for x in row] for row in u[:, 3:]]).reshape(-1, 3)
+        c2w = np.stack([viewmatrix(t - p, np.array([0.0, 0.0, -1.0]), p) for t, p in zip(target, pos)]) if len(todo) else np.zeros((0, 4, 4))
+        out[todo] = c2w
+        if pts is None:
+            todo = todo[:0]
+            break
+        seen = ops.points_in_view(pts, np.linalg.inv(c2w)[:, :3], K, H, W, EDGE).cpu().numpy() > 0
+        todo = todo[seen]
+    if len(todo):
+        raise RuntimeError(f"view {int(todo[0])}: {max_tries} candidates in a row see the unseen region")
+    return out
+
+
+def _unseen_next_to(gt_mesh):
+    if isinstance(gt_mesh, (str, os.PathLike)):
+        path = os.path.splitext(os.fspath(gt_mesh))[0] + "_pc_unseen.npy"
+        if os.path.isfile(path):
+            return np.load(path)
+    return None
+
+
+def _gpu_mesh(mesh):
+    v = as_points(mesh.vertices)
+    return v, torch.as_tensor(np.ascontiguousarray(mesh.faces, np.int32)).to(v.device).reshape(-1, 3).contiguous()
+
+
+def calc_2d_metric(rec_mesh, gt_mesh, align=True, n_imgs=1000, unseen=None, views=None, seed=0, H=500, W=500, focal=300):
+    """eval_recon.py:138-223: {'depth l1' (cm)}.  Both meshes are rendered by cut3r_mesh_raster (z_far 20 as set_constant_z_far) from the
+    same cameras: `views` [n,4,4] c2w when given, else n_imgs poses of sample_views in the box of get_cam_position(gt_mesh), redrawn
+    while they see a point of `unseen` (an [N,3] array; None: <gt stem>_pc_unseen.npy next to a GT path, and no rejection when there is
+    none).  Per view the mean |gt - ours| over the pixels with ours > 0 (a pixel where only the GT is empty counts with gt = 0); views
+    where the reconstruction is empty are skipped; the mean over the others times 100, nan when none is left."""
+    if unseen is None:
+        unseen = _unseen_next_to(gt_mesh)
+    rec, gt = as_mesh(rec_mesh), as_mesh(gt_mesh)
+    if align:
+        rec = apply_transform(rec, get_align_transformation(rec, gt).transformation)
+    if views is None:
+        extents, transform = get_cam_position(gt)
+        views = sample_views(extents, transform, n_imgs, unseen=unseen, seed=seed, W=W, H=H, focal=focal)
+    views = np.asarray(views, np.float64).reshape(-1, 4, 4)
+    if len(views) == 0:
+        return {"depth l1": float("nan")}
+    w2c = np.linalg.inv(views)[:, :3]
+    K = [focal, focal, W / 2.0 - 0.5, H / 2.0 - 0.5]
+    gv, gf = _gpu_mesh(gt)
+    rv, rf = _gpu_mesh(rec)
+    sums = []
+    for b0 in range(0, len(w2c), ops.RASTER_MAX_VIEWS):
+        w = w2c[b0:b0 + ops.RASTER_MAX_VIEWS]
+        sums.append(ops.depth_l1(ops.mesh_raster(gv, gf, w, K, H, W), ops.mesh_raster(rv, rf, w, K, H, W)))
+    s = torch.cat(sums).cpu().numpy()
+    ok = s[:, 0] > 0
+    errors = s[ok, 1] / s[ok, 0]
+    return {"depth l1": float(errors.mean() * 100) if len(errors) else float("nan")}
 
 
 # ----------------------------------------------------------------------------------------------------------------------- Chamfer
@@ -223,10 +360,14 @@ def sim3_from_trajectories(est_tum, gt_tum, max_diff=0.01) -> np.ndarray:
 
 # ------------------------------------------------------------------------------------------------------------------------- CLI
 def parse_args(argv=None):
-    p = argparse.ArgumentParser(description="3-D reconstruction metrics of a mesh against a ground-truth mesh (scripts/eval_recon.py)")
+    p = argparse.ArgumentParser(description="reconstruction metrics of a mesh against a ground-truth mesh (scripts/eval_recon.py)")
     p.add_argument("rec_mesh", type=str, help="reconstructed mesh (binary PLY)")
     p.add_argument("gt_mesh", type=str, help="ground-truth mesh (binary PLY)")
-    p.add_argument("--eval_3d", action="store_true", help="accepted for compatibility: the 3-D metric is the only one built")
+    p.add_argument("--eval_3d", action="store_true", help="accepted for compatibility: the 3-D metric is always computed")
+    p.add_argument("--eval_2d", action="store_true", help="also the 2-D metric: depth L1 of renders from random viewpoints inside the room")
+    p.add_argument("--n-imgs", type=int, default=10, help="views of the 2-D metric (the reference's eval_recon uses 10, its tables 1000)")
+    p.add_argument("--unseen", type=str, default=None, help="[N,3] .npy of GT points no sampled view may see (default: "
+                   "<gt stem>_pc_unseen.npy when it exists)")
     p.add_argument("--save", type=str, default=None, help="write the result dict as f'{result}' (ast.literal_eval reads it back)")
     p.add_argument("--no-align", action="store_true", help="skip the ICP alignment of the rec mesh onto the GT mesh")
     p.add_argument("--transform", type=str, default=None, help="4x4 .npy applied to the rec mesh first")
@@ -239,6 +380,8 @@ def parse_args(argv=None):
         p.error("--traj-est and --traj-gt go together")
     if a.samples <= 0:
         p.error("--samples must be > 0")
+    if a.n_imgs <= 0:
+        p.error("--n-imgs must be > 0")
     return a
 
 
@@ -249,7 +392,8 @@ def main(argv=None):
         rec = apply_transform(rec, np.load(a.transform))
     if a.traj_est is not None:
         rec = apply_transform(rec, sim3_from_trajectories(a.traj_est, a.traj_gt))
-    result = eval_recon(rec, a.gt_mesh, eval_3d=True, align=not a.no_align, samples=a.samples, seed=a.seed)
+    extra = dict(eval_2d=True, n_imgs=a.n_imgs, unseen=None if a.unseen is None else np.load(a.unseen)) if a.eval_2d else {}
+    result = eval_recon(rec, a.gt_mesh, eval_3d=True, align=not a.no_align, samples=a.samples, seed=a.seed, **extra)
     print(result)
     if a.save:
         with open(a.save, "w") as fh:

@@ -873,3 +873,122 @@ class NNGrid:
 def nn_query(ref, query, max_dist=None, transform=None):
     """one-shot NNGrid(ref).query(query)"""
     return NNGrid(ref, query.shape[0] if query.dim() == 2 else 0).query(query, max_dist=max_dist, transform=transform)
+
+
+# ------------------------------------------------------------------------------------------------ mesh depth rasteriser, 2-D metric
+RASTER_MAX_VIEWS = 16
+
+
+def _views(w2c, K, dev):
+    """(w2c [B,12] fp32, K [B,4] fp32, B) on `dev` from [B,12] / [B,3,4] / [B,4,4] poses and [B,4] (or one [4]) fx fy cx cy"""
+    w2c = torch.as_tensor(w2c)
+    _req(w2c.dim() in (2, 3) and w2c.shape[0] > 0, "w2c: [B,12], [B,3,4] or [B,4,4]")
+    B = w2c.shape[0]
+    w2c = w2c.reshape(B, -1)
+    _req(w2c.shape[1] in (12, 16), "w2c: [B,12], [B,3,4] or [B,4,4]")
+    w2c = w2c[:, :12].to(dev, F32).contiguous()
+    K = torch.as_tensor(K).to(dev, F32)
+    if K.dim() == 1:
+        K = K[None].expand(B, -1)
+    _req(K.shape == (B, 4), "K: [B,4] fx fy cx cy")
+    K = K.contiguous()
+    _req(bool(torch.isfinite(w2c).all()) and bool(torch.isfinite(K).all()), "w2c / K: non-finite entries")
+    _req(bool((K[:, :2] > 0).all()), "K: fx and fy must be > 0")
+    return w2c, K, B
+
+
+def _image_size(H, W):
+    H, W = int(H), int(W)
+    _req(1 <= H <= 65535 and 1 <= W <= 65535, "H, W: 1 .. 65535")
+    return H, W
+
+
+def mesh_raster(verts, faces, w2c, K, H, W, z_near=0.0, z_far=20.0, face_id=False):
+    """depth [B,H,W] fp32 (0 = nothing hit) of the mesh from B cameras, and with face_id=True also the int32 [B,H,W] index of the face
+    seen (-1 = nothing): the depth buffer the reference captures from its Open3D window (scripts/eval_recon.py:189-213).  w2c world->camera
+    (OpenCV axes), K = fx fy cx cy per view, pixel centres at integer coordinates; both faces of a triangle are drawn, the nearest z in
+    (z_near, z_far] wins, ties go to the smaller face index.  Any B: 16 views go into one launch."""
+    V = _points(verts, "verts")
+    _cuda(faces)
+    _req(faces.dim() == 2 and faces.shape[1] == 3 and faces.dtype == torch.int32 and faces.is_contiguous(), "faces: contiguous int32 [F,3]")
+    F = faces.shape[0]
+    _req(0 < F < 2 ** 31, "faces: 1 .. 2^31 - 1 faces")
+    _req(int(faces.min()) >= 0 and int(faces.max()) < V, "faces: vertex index out of range")
+    H, W = _image_size(H, W)
+    z_near, z_far = float(z_near), float(z_far)
+    _req(z_near >= 0 and z_far > z_near and z_far < float("inf"), "0 <= z_near < z_far < inf")
+    w2c, K, B = _views(w2c, K, verts.device)
+    depth = torch.empty(B, H, W, dtype=F32, device=verts.device)
+    fid = torch.empty(B, H, W, dtype=torch.int32, device=verts.device) if face_id else None
+    lib = _lib.load()
+    ws = None
+    for b0 in range(0, B, RASTER_MAX_VIEWS):
+        nb = min(RASTER_MAX_VIEWS, B - b0)
+        nbytes = lib.cut3r_mesh_raster_workspace_bytes(F, nb, H, W)
+        _req(nbytes > 0, "raster workspace")
+        if ws is None or ws.numel() < nbytes:
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=verts.device)
+        check(lib.cut3r_mesh_raster(_p(verts), V, _p(faces), F, _p(w2c[b0:b0 + nb]), _p(K[b0:b0 + nb]), nb, H, W, z_near, z_far,
+                                    _p(depth[b0:b0 + nb]), _p(fid[b0:b0 + nb]) if face_id else C.c_void_p(0), _p(ws), nbytes, _stream()),
+              "cut3r_mesh_raster")
+    return (depth, fid) if face_id else depth
+
+
+def depth_l1(gt, ours):
+    """fp64 [B,2] per view: the number of pixels with ours > 0 and the sum of |gt - ours| over them (scripts/eval_recon.py:216-218 before
+    the mean); gt, ours fp32 [B,H,W].  The same bits on every run."""
+    _cuda(gt, ours)
+    _req(ours.dim() == 3 and ours.numel() > 0 and ours.shape == gt.shape, "gt, ours: [B,H,W] of one shape")
+    _req(gt.dtype == F32 and ours.dtype == F32 and gt.is_contiguous() and ours.is_contiguous(), "gt, ours: contiguous fp32")
+    B, H, W = ours.shape
+    _req(H * W < 2 ** 31, "image too large")
+    out = torch.empty(B, 2, dtype=torch.float64, device=ours.device)
+    lib = _lib.load()
+    for b0 in range(0, B, 65535):
+        nb = min(65535, B - b0)
+        nbytes = lib.cut3r_depth_l1_workspace_bytes(nb)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=ours.device)
+        check(lib.cut3r_depth_l1(_p(gt[b0:b0 + nb]), _p(ours[b0:b0 + nb]), nb, H, W, _p(out[b0:b0 + nb]), _p(ws), nbytes, _stream()),
+              "cut3r_depth_l1")
+    return out
+
+
+def points_in_view(points, w2c, K, H, W, edge=10.0):
+    """int32 [B]: how many of points [N,3] each camera sees strictly inside the image shrunk by `edge` pixels, in front of it (the test of
+    the reference's check_proj, scripts/eval_recon.py:60-89, for B candidate cameras)"""
+    N = _points(points, "points")
+    H, W = _image_size(H, W)
+    edge = float(edge)
+    _req(edge >= 0, "edge must be >= 0")
+    w2c, K, B = _views(w2c, K, points.device)
+    counts = torch.empty(B, dtype=torch.int32, device=points.device)
+    lib = _lib.load()
+    for b0 in range(0, B, RASTER_MAX_VIEWS):
+        nb = min(RASTER_MAX_VIEWS, B - b0)
+        check(lib.cut3r_points_in_view(_p(points), N, _p(w2c[b0:b0 + nb]), _p(K[b0:b0 + nb]), nb, H, W, edge, _p(counts[b0:b0 + nb]),
+                                       _stream()), "cut3r_points_in_view")
+    return counts
+
+
+def mesh_vertex_visible(verts, depth, w2c, K, eps=0.03, z_far=20.0, flags=None):
+    """u8 [V]: flags (given ones are kept: OR) set where a vertex is seen by one of the B views whose rendered depth [B,H,W] is `depth`:
+    0 < z <= z_far, its nearest pixel inside the image, and not more than eps behind the depth there"""
+    V = _points(verts, "verts")
+    _cuda(depth)
+    _req(depth.dim() == 3 and depth.dtype == F32 and depth.is_contiguous() and depth.numel() > 0, "depth: contiguous fp32 [B,H,W]")
+    B, H, W = depth.shape
+    H, W = _image_size(H, W)
+    w2c, K, Bv = _views(w2c, K, verts.device)
+    _req(Bv == B, "depth and w2c: one view each")
+    eps, z_far = float(eps), float(z_far)
+    _req(eps >= 0 and z_far > 0, "eps >= 0, z_far > 0")
+    if flags is None:
+        flags = torch.zeros(V, dtype=torch.uint8, device=verts.device)
+    _cuda(flags)
+    _req(flags.shape == (V,) and flags.dtype == torch.uint8 and flags.is_contiguous(), "flags: contiguous u8 [V]")
+    lib = _lib.load()
+    for b0 in range(0, B, RASTER_MAX_VIEWS):
+        nb = min(RASTER_MAX_VIEWS, B - b0)
+        check(lib.cut3r_mesh_vertex_visible(_p(verts), V, _p(depth[b0:b0 + nb]), _p(w2c[b0:b0 + nb]), _p(K[b0:b0 + nb]), nb, H, W, eps, z_far,
+                                            _p(flags), _stream()), "cut3r_mesh_vertex_visible")
+    return flags

@@ -82,9 +82,19 @@ def main(argv=None):
                    "--eval_3d) -> <output>/eval_recon_w{W:.1f}.txt; needs --mesh")
     p.add_argument("--gt-traj", type=str, default=None, help="TUM ground-truth trajectory: the Sim(3) of traj_kf.txt onto it is applied to "
                    "the mesh before scoring (scripts/run_replica.py:45-46)")
+    p.add_argument("--eval-2d", action="store_true", help="with --gt-mesh: also the 2-D metric (scripts/eval_recon.py calc_2d_metric), "
+                   "'depth l1' in cm added to eval_recon_w{W:.1f}.txt")
+    p.add_argument("--gt-unseen", type=str, default=None, help="[N,3] .npy of GT points that no view of --eval-2d may see")
+    p.add_argument("--n-imgs", type=int, default=10, help="views of --eval-2d (scripts/eval_recon.py:238)")
     args = p.parse_args(argv)
     if args.gt_mesh and not args.mesh:
         p.error("--gt-mesh needs --mesh")
+    if args.eval_2d and not args.gt_mesh:
+        p.error("--eval-2d needs --gt-mesh")
+    if args.gt_unseen and not args.eval_2d:
+        p.error("--gt-unseen needs --eval-2d")
+    if args.n_imgs <= 0:
+        p.error("--n-imgs must be > 0")
     if args.gt_traj and not args.gt_mesh:
         p.error("--gt-traj needs --gt-mesh")
     os.makedirs(args.output, exist_ok=True)
@@ -179,10 +189,14 @@ def main(argv=None):
                 if args.gt_traj:
                     mesh = ER.apply_transform(mesh, ER.sim3_from_trajectories(os.path.join(args.output, "traj_kf.txt"), args.gt_traj))
                 res = ER.calc_3d_metric(mesh, args.gt_mesh)
+                if args.eval_2d:
+                    import numpy as np
+                    res.update(ER.calc_2d_metric(mesh, args.gt_mesh, n_imgs=args.n_imgs,
+                                                 unseen=np.load(args.gt_unseen) if args.gt_unseen else None))
                 with open(os.path.join(args.output, f"eval_recon_w{w:.1f}.txt"), "w") as fh:
                     fh.write(f"{res}")
                 print(f"  vs {args.gt_mesh}: accuracy {res['accuracy']:.3f} cm, completion {res['completion']:.3f} cm, "
-                      f"completion ratio {res['completion_ratio']:.2f} %")
+                      f"completion ratio {res['completion_ratio']:.2f} %" + (f", depth L1 {res['depth l1']:.3f} cm" if args.eval_2d else ""))
     print(f"{nframes} frames, {len(traj)} keyframes, {len(slam.graph.edges_numpy()[0])} graph edges in {time.time() - t0:.1f}s "
           f"-> {args.output}/traj_kf.txt")
     return 0

@@ -527,6 +527,39 @@ long long cut3r_icp_moments_workspace_bytes(int Q);                   /* -1 when
 int cut3r_icp_moments(const float* src, int Q, const float* ref, int P, const float* T, const float* dist2, const int* idx, double* out,
                       void* workspace, long long workspace_bytes, void* stream);
 
+/* ---- Mesh depth rasteriser and the 2-D depth-L1 metric (csrc/raster.hip) -----------------------------------------------------------------
+ * mesh_raster replaces the off-screen Open3D window of scripts/eval_recon.py:162-213 (capture_depth_float_buffer of a mesh drawn with
+ * mesh_show_back_face and set_constant_z_far(20)).  verts [V,3] fp32, faces [F,3] int32 (a face with an index outside 0..V-1 is not
+ * drawn), w2c [B,12] world->camera rows (OpenCV camera: x right, y down, z forward), K [B,4] fx fy cx cy with fx, fy > 0, B in 1..16, H
+ * and W in 1..65535.  depth [B,H,W] fp32, 0 where nothing is hit; face_id [B,H,W] int32 or NULL, -1 where nothing is hit.  Per pixel
+ * (i, j), sampled at its centre, and triangle (a, b, c) in camera space (p_c = ((T0 x + T1 y) + T2 z) + T3, fp32): the ray d =
+ * ((j - cx) / fx, (i - cy) / fy, 1) in fp32, then in fp64 e0 = d . (b x c), e1 = d . (c x a), e2 = d . (a x b); a hit when all three are
+ * >= 0 or all three <= 0 (both faces), den = (e0 + e1) + e2 != 0 and z = float((a . (b x c)) / den) lies in (z_near, z_far].  A triangle
+ * with no vertex in front of the camera plane is not drawn; one with all three in front is tried only inside the box of its projected
+ * vertices padded by a pixel (in exact arithmetic both follow from the hit test; stated so that rounding cannot place a sliver outside
+ * itself); nothing is clipped, a triangle across the camera plane is drawn where it is in front.  The pixel takes the smallest z, ties
+ * the smallest face index; the result does not depend on the launch shape or on the order in which faces arrive.  The order of every
+ * operation is fixed in csrc/raster.hip and restated by tests/raster_oracle.py.  z_near < 0 (or NaN) and z_far <= z_near are refused.
+ * workspace: cut3r_mesh_raster_workspace_bytes(F, B, H, W). */
+long long cut3r_mesh_raster_workspace_bytes(int F, int B, int H, int W);   /* -1 on bad sizes */
+int cut3r_mesh_raster(const float* verts, int V, const int* faces, int F, const float* w2c, const float* K, int B, int H, int W, float z_near,
+                      float z_far, float* depth, int* face_id, void* workspace, long long workspace_bytes, void* stream);
+/* the per-view sums of the depth L1 (eval_recon.py:216-218): out [B,2] fp64 = (number of pixels with ours > 0, sum of |gt - ours| over
+ * them), gt and ours [B,H,W] fp32.  Fixed reduction order: identical on every run.  workspace: cut3r_depth_l1_workspace_bytes(B). */
+long long cut3r_depth_l1_workspace_bytes(int B);                      /* -1 when B <= 0 */
+int cut3r_depth_l1(const float* gt, const float* ours, int B, int H, int W, double* out, void* workspace, long long workspace_bytes,
+                   void* stream);
+/* check_proj of eval_recon.py:60-89 for B in 1..16 candidate cameras at once: counts [B] int32 = how many of points [N,3] satisfy, with
+ * p_c as above and z' = z - 1e-5, 0 <= z', edge < (fx x + cx z) / z' < W - edge and edge < (fy y + cy z) / z' < H - edge (the reference's
+ * axis flips cancel to this). */
+int cut3r_points_in_view(const float* points, int N, const float* w2c, const float* K, int B, int H, int W, float edge, int* counts,
+                         void* stream);
+/* which vertices a set of views sees (no reference counterpart: the reference reads GT meshes culled by an outside script): flags [V]
+ * u8, flags[v] set to 1 (never cleared) when in one of the B views 0 < z <= z_far, the nearest pixel (floor(u + 0.5), u = fx (x / z) +
+ * cx) is inside the image and the depth d of cut3r_mesh_raster there is 0 or z <= d + eps.  depth [B,H,W]. */
+int cut3r_mesh_vertex_visible(const float* verts, int V, const float* depth, const float* w2c, const float* K, int B, int H, int W, float eps,
+                              float z_far, unsigned char* flags, void* stream);
+
 /* Measurement aid of bench.py's roofline (no reference counterpart; not on the product path): a bare MFMA loop (v_mfma_f32_16x16x32_f16,
  * 16 independent accumulator chains per wave, 8 waves per workgroup, `grid` workgroups, `iters` x 16 MFMAs per wave, operands = 16-byte
  * chunks of data[nhalf] fp16, nhalf a power of two >= 32768) with s_memtime / s_memrealtime stamps around the loop.  stamps [grid,2] u64 =
