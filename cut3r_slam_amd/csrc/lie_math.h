@@ -128,14 +128,29 @@ template <typename T> DEVINL V3<T> so3_log(const Q4<T>& q) {
     return {k * q.x, k * q.y, k * q.z};
 }
 
-// V(phi) tau (SE3) : t = tau + a (phi x tau) + b phi x (phi x tau)
+// The SE3 / Sim3 coefficients are smooth even functions of theta (and of sigma) whose closed forms subtract nearly equal numbers at small
+// arguments: fp32 1 - cos(th) is exactly 0 below th = 2.4e-4, and the forward-mode derivative of such a quotient loses one more factor 1/th.  Each one
+// therefore takes its Taylor series below |theta| = 0.3 (|sigma| = 0.3; theta^2 + sigma^2 = 0.09 for the two-variable Sim3 pair).  At that point the
+// closed forms, written without a cancelling difference of O(1) terms, are already good to ~1e-6 in value and derivative, and the series (to x^3 in
+// x = theta^2, degree 7 in sigma) truncate below 1e-8.  Both branches are T arithmetic, so the dual numbers differentiate the branch they take.
+constexpr float SERIES_X2 = 0.09f;
+
+// sin(th) / th
+template <typename T> DEVINL T sinc_coeff(const T& th2) {
+    if (val(th2) < SERIES_X2) return T(1.0f) + th2 * (T(-1.0f / 6.0f) + th2 * (T(1.0f / 120.0f) + th2 * T(-1.0f / 5040.0f)));
+    const T th = Sqrt(th2);
+    return Sin(th) / th;
+}
+
+// V(phi) tau (SE3) : t = tau + a (phi x tau) + b phi x (phi x tau),  a = (1 - cos th)/th^2 = 2 sin^2(th/2)/th^2,  b = (th - sin th)/th^3
 template <typename T> DEVINL void se3_coeffs(const T& th2, T& a, T& b) {
-    if (val(th2) < 1e-8f) {
-        a = T(0.5f) - th2 * T(1.0f / 24.0f);
-        b = T(1.0f / 6.0f) - th2 * T(1.0f / 120.0f);
+    if (val(th2) < SERIES_X2) {
+        a = T(0.5f) + th2 * (T(-1.0f / 24.0f) + th2 * (T(1.0f / 720.0f) + th2 * T(-1.0f / 40320.0f)));
+        b = T(1.0f / 6.0f) + th2 * (T(-1.0f / 120.0f) + th2 * (T(1.0f / 5040.0f) + th2 * T(-1.0f / 362880.0f)));
     } else {
         const T th = Sqrt(th2);
-        a = (T(1.0f) - Cos(th)) / th2;
+        const T sh = Sin(th * T(0.5f));
+        a = T(2.0f) * sh * sh / th2;
         b = (th - Sin(th)) / (th2 * th);
     }
 }
@@ -149,41 +164,54 @@ template <typename T> DEVINL void se3_exp(const V3<T>& tau, const V3<T>& phi, V3
     t = add(tau, add(scale(a, pt), scale(b, cross(phi, pt))));
 }
 
-// V^-1 t = t - 1/2 phi x t + c phi x (phi x t),  c = 1/th^2 - (1+cos th)/(2 th sin th)
+// V^-1 t = t - 1/2 phi x t + c phi x (phi x t),  c = 1/th^2 - (1+cos th)/(2 th sin th) = (1 - (th/2) cot(th/2))/th^2
+// (the half-angle form has no 1 + cos(th) to cancel near th = pi)
 template <typename T> DEVINL void se3_log(const V3<T>& t, const Q4<T>& q, V3<T>& tau, V3<T>& phi) {
     phi = so3_log(q);
     const T th2 = phi.x * phi.x + phi.y * phi.y + phi.z * phi.z;
     T c;
-    if (val(th2) < 1e-6f) {
-        c = T(1.0f / 12.0f) + th2 * T(1.0f / 720.0f);
+    if (val(th2) < SERIES_X2) {
+        c = T(1.0f / 12.0f) + th2 * (T(1.0f / 720.0f) + th2 * (T(1.0f / 30240.0f) + th2 * T(1.0f / 1209600.0f)));
     } else {
-        const T th = Sqrt(th2);
-        c = T(1.0f) / th2 - (T(1.0f) + Cos(th)) / (T(2.0f) * th * Sin(th));
+        const T h = Sqrt(th2) * T(0.5f);
+        c = (T(1.0f) - h * Cos(h) / Sin(h)) / th2;
     }
     const V3<T> pt = cross(phi, t);
     tau = add(t, add(scale(T(-0.5f), pt), scale(c, cross(phi, pt))));
 }
 
-// Sim3: W = A [phi]x + B [phi]x^2 + C I   (Sophus Sim3::exp)
+// Sim3: W = A [phi]x + B [phi]x^2 + C I   (Sophus Sim3::exp).  With z = sigma + i theta and f(z) = (e^z - 1)/z = sum_n z^n/(n+1)!:
+//   C = f(sigma),  A = Im f(z) / theta,  B = (C - Re f(z)) / theta^2
 template <typename T> DEVINL void sim3_coeffs(const T& th2, const T& sigma, T& A, T& B, T& C) {
     const T s = Exp(sigma);
-    const float sv = val(sigma), tv = val(th2);
-    if (fabsf(sv) < 1e-4f) {
-        C = T(1.0f) + sigma * T(0.5f);
-        if (tv < 1e-8f) { A = T(0.5f); B = T(1.0f / 6.0f); }
-        else { const T th = Sqrt(th2); A = (T(1.0f) - Cos(th)) / th2; B = (th - Sin(th)) / (th2 * th); }
+    const T sg2 = sigma * sigma;
+    if (val(sg2) < SERIES_X2) {
+        C = T(1.0f) + sigma * (T(1.0f / 2.0f) + sigma * (T(1.0f / 6.0f) + sigma * (T(1.0f / 24.0f) + sigma * (T(1.0f / 120.0f) +
+            sigma * (T(1.0f / 720.0f) + sigma * (T(1.0f / 5040.0f) + sigma * T(1.0f / 40320.0f)))))));
     } else {
         C = (s - T(1.0f)) / sigma;
-        const T sg2 = sigma * sigma;
-        if (tv < 1e-8f) {
-            A = ((sigma - T(1.0f)) * s + T(1.0f)) / sg2;
-            B = (s * T(0.5f) * sg2 + s - T(1.0f) - sigma * s) / (sg2 * sigma);
-        } else {
-            const T th = Sqrt(th2);
-            const T a = s * Sin(th), b = s * Cos(th), c = th2 + sg2;
-            A = (a * sigma + (T(1.0f) - b) * th) / (th * c);
-            B = (C - ((b - T(1.0f)) * sigma + a * th) / c) / th2;
+    }
+    const T c = th2 + sg2;
+    if (val(c) < SERIES_X2) {
+        // z^n = re + i theta q and sigma^n - re = theta^2 r are polynomials in (sigma, theta^2):  z^(n+1) = z^n z
+        const float inv_fact[9] = {1.0f, 1.0f, 1.0f / 2.0f, 1.0f / 6.0f, 1.0f / 24.0f, 1.0f / 120.0f, 1.0f / 720.0f, 1.0f / 5040.0f, 1.0f / 40320.0f};
+        T re = sigma, q = T(1.0f), r = T(0.0f);                       // n = 1
+        A = T(0.5f);
+        B = T(0.0f);
+#pragma unroll
+        for (int n = 2; n <= 7; n++) {
+            const T re_n = sigma * re - th2 * q, q_n = re + sigma * q, r_n = sigma * r + q;
+            re = re_n; q = q_n; r = r_n;
+            A = A + q * T(inv_fact[n + 1]);
+            B = B + r * T(inv_fact[n + 1]);
         }
+    } else {
+        // the same quotients with 1 - e^sigma cos(th) split into -sigma C + e^sigma (1 - cos th): every term is a well-conditioned function
+        T al, be;
+        se3_coeffs(th2, al, be);
+        const T sc = sinc_coeff(th2);
+        A = (sigma * (s * sc - C) + s * th2 * al) / c;
+        B = (C + s * (sigma * al - sc)) / c;
     }
 }
 

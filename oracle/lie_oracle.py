@@ -51,8 +51,8 @@ def matrix_to_data(group, M):
     return np.concatenate([d, [s]]) if group == 2 else d
 
 
-def log_tangent(group, M):
-    L = np.real(logm(M))
+def vee(group, L):
+    """tangent vector of a 4x4 algebra element (inverse of twist_matrix)"""
     phi = np.array([L[2, 1], L[0, 2], L[1, 0]])
     if group == 0:
         return phi
@@ -60,6 +60,10 @@ def log_tangent(group, M):
     if group == 1:
         return np.concatenate([tau, phi])
     return np.concatenate([tau, phi, [np.trace(L[:3, :3]) / 3.0]])
+
+
+def log_tangent(group, M):
+    return vee(group, np.real(logm(M)))
 
 
 def adjoint_matrix(group, M, eps=1e-6):
@@ -74,3 +78,30 @@ def adjoint_matrix(group, M, eps=1e-6):
         m = log_tangent(group, M @ exp_matrix(group, -e) @ Mi)
         Ad[:, j] = (p - m) / (2 * eps)
     return Ad
+
+
+# ---- vectorised / logm-free twins for sweeps of thousands of points (logm costs milliseconds per 4x4); tests/test_lie_bands_gpu.py checks
+# each against the function it stands for
+def exp_matrix_batch(group, A):
+    """exp_matrix of every row of A [N, tangent dim] -> [N, 4, 4] (one batched scipy expm)"""
+    A = np.asarray(A, np.float64)
+    return expm(np.stack([twist_matrix(group, a) for a in A]))
+
+
+def matrix_to_data_batch(group, M):
+    """matrix_to_data of every matrix of M [N, 4, 4], with the quaternion sign fixed to w >= 0"""
+    M = np.asarray(M, np.float64)
+    s = np.cbrt(np.linalg.det(M[:, :3, :3])) if group == 2 else np.ones(len(M))
+    q = Rotation.from_matrix(M[:, :3, :3] / s[:, None, None]).as_quat()
+    q = q * np.where(q[:, 3:4] < 0, -1.0, 1.0)
+    if group == 0:
+        return q
+    d = np.concatenate([M[:, :3, 3], q], 1)
+    return np.concatenate([d, s[:, None]], 1) if group == 2 else d
+
+
+def adjoint_matrix_exact(group, M):
+    """Ad without differences: X a^ X^-1 = (Ad a)^  =>  column j = vee(X e_j^ X^-1)"""
+    n = {0: 3, 1: 6, 2: 7}[group]
+    Mi = np.linalg.inv(M)
+    return np.stack([vee(group, M @ twist_matrix(group, np.eye(n)[j]) @ Mi) for j in range(n)], 1)

@@ -1,6 +1,9 @@
 """GPU: lietorch-compatible SE3/SO3/Sim3 kernels vs the fp64 matrix-exponential oracle (oracle/lie_oracle.py).
 Parity vs lietorch itself is UNPINNED (the dependency is absent from the reference tree); conventions come from the
-reference call sites.  Tolerances: fp32 kernels vs fp64 oracle, 2e-5 absolute on O(1) quantities."""
+reference call sites.  Tolerances: fp32 kernels vs fp64 oracle, 3e-5 .. 2e-4 absolute on O(1) quantities at generic points, and rows scaled as
+a whole (translation shrinking with the rotation).  These cases do not reach the angles and log-scales where the coefficient functions change
+from series to closed form with a translation of size 1: tests/test_lie_bands_gpu.py sweeps those, at 1e-5 max(1, |tau|) for values and
+2e-4 max(1, |tau|) for gradients (measured there: 7e-7 and 5e-6)."""
 import numpy as np
 import pytest
 import torch
