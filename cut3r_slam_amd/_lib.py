@@ -144,6 +144,14 @@ SIGNATURES = {
     "cut3r_tsdf_mesh_workspace_bytes": [c_int, c_int, c_int],
     "cut3r_tsdf_mesh_count": [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_ll, c_void_p, c_void_p],
     "cut3r_tsdf_mesh_emit": [c_void_p, c_void_p, c_int, c_int, c_int] + [c_float] * 4 + [c_void_p, c_ll] + [c_void_p] * 3 + [c_ll, c_ll, c_void_p],
+    "cut3r_tsdf_sparse_mark": [c_void_p] + [c_int] * 3 + [c_float] * 4 + [c_void_p] + [c_int] * 3 + [c_void_p, c_void_p, c_float, c_float, c_void_p],
+    "cut3r_tsdf_sparse_assign_workspace_bytes": [c_int, c_int, c_int],
+    "cut3r_tsdf_sparse_assign": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_ll, c_void_p, c_void_p],
+    "cut3r_tsdf_sparse_integrate": [c_void_p] * 4 + [c_int] * 4 + [c_float] * 4 + [c_void_p] * 3 + [c_int] * 6 + [c_float, c_void_p, c_void_p,
+                                                                                                                 c_float, c_float, c_void_p],
+    "cut3r_tsdf_sparse_mesh_workspace_bytes": [c_int],
+    "cut3r_tsdf_sparse_mesh_count": [c_void_p] * 4 + [c_int] * 4 + [c_float, c_void_p, c_ll, c_void_p, c_void_p],
+    "cut3r_tsdf_sparse_mesh_emit": [c_void_p] * 4 + [c_int] * 4 + [c_float] * 4 + [c_void_p, c_ll] + [c_void_p] * 3 + [c_ll, c_ll, c_void_p],
     "cut3r_mesh_cdf_workspace_bytes": [c_int],
     "cut3r_mesh_area_cdf": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_ll, c_void_p],
     "cut3r_mesh_sample": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_ll, C.c_ulonglong, C.c_ulonglong, c_void_p, c_void_p],
@@ -161,7 +169,8 @@ SIGNATURES = {
     "cut3r_mesh_vertex_visible": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p],
 }
 RESTYPES = {"cut3r_ba_workspace_floats": c_ll, "cut3r_gs_workspace_bytes": c_ll, "cut3r_schur_mono_prior_workspace_floats": c_ll,
-            "cut3r_knn3_grid_workspace_bytes": c_ll, "cut3r_tsdf_mesh_workspace_bytes": c_ll, "cut3r_mesh_cdf_workspace_bytes": c_ll,
+            "cut3r_knn3_grid_workspace_bytes": c_ll, "cut3r_tsdf_mesh_workspace_bytes": c_ll, "cut3r_tsdf_sparse_assign_workspace_bytes": c_ll,
+            "cut3r_tsdf_sparse_mesh_workspace_bytes": c_ll, "cut3r_mesh_cdf_workspace_bytes": c_ll,
             "cut3r_nn_workspace_bytes": c_ll, "cut3r_icp_moments_workspace_bytes": c_ll, "cut3r_mesh_raster_workspace_bytes": c_ll,
             "cut3r_depth_l1_workspace_bytes": c_ll}
 

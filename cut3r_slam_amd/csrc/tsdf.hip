@@ -5,47 +5,20 @@
 // (k*Y + j)*X + i (x fastest).  Every formula is written in one fixed order and the file is compiled with -ffp-contract=off: the numpy
 // restatement in tests/tsdf_oracle.py reproduces the bits.
 //
+// The per-voxel fusion, the tetrahedron tables and the count packing live in tsdf_voxel.h, shared with the sparse brick volume
+// (tsdf_sparse.hip).
+//
 // Mesh: the Kuhn (Freudenthal) split of every cell into six tetrahedra along its corner-0 -> corner-7 diagonal, one per axis permutation.
 // Corners are numbered by bits (bit 0 = +x, bit 1 = +y, bit 2 = +z); the tetrahedron of permutation p is the chain 0 -> 1<<p0 ->
 // (1<<p0)|(1<<p1) -> 7, so every tetrahedron edge joins a corner to a superset corner: a global edge is (lower voxel, direction mask m in
 // 1..7) and that voxel owns its vertex.  Three passes: count (per voxel: a 7-bit mask of the vertices it owns + the triangles of the cell
 // whose corner 0 it is), two exclusive scans of those counts (hipcub), emit.
-#include <hipcub/hipcub.hpp>
-#include "common.h"
+#include "tsdf_voxel.h"
 #include "../../include/cut3r_hip.h"
-
-#define TSDF_MAX_VIEWS 16
 
 namespace {
 
-// the six tetrahedra: axis permutations in lexicographic order, and their parities (+1 even: the chain is positively oriented)
-__constant__ int kPerm[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
-__constant__ int kParity[6] = {1, -1, -1, 1, 1, -1};
-// tetrahedron edges (chain positions a < b) and the triangles of the 16 inside/outside cases (bit q = chain vertex q has tsdf < 0), as
-// edge ids, wound so that the normal (b - a) x (c - a) points from negative to positive tsdf on a positively oriented tetrahedron
-__constant__ int kEdge[6][2] = {{0, 1}, {0, 2}, {0, 3}, {1, 2}, {1, 3}, {2, 3}};
-__constant__ int kTri[16][2][3] = {
-    {{-1, -1, -1}, {-1, -1, -1}}, {{0, 1, 2}, {-1, -1, -1}}, {{0, 4, 3}, {-1, -1, -1}}, {{1, 2, 4}, {1, 4, 3}},
-    {{1, 3, 5}, {-1, -1, -1}},    {{0, 5, 2}, {0, 3, 5}},    {{0, 4, 5}, {0, 5, 1}},    {{2, 4, 5}, {-1, -1, -1}},
-    {{2, 5, 4}, {-1, -1, -1}},    {{0, 1, 5}, {0, 5, 4}},    {{0, 5, 3}, {0, 2, 5}},    {{1, 5, 3}, {-1, -1, -1}},
-    {{1, 3, 4}, {1, 4, 2}},       {{0, 3, 4}, {-1, -1, -1}}, {{0, 2, 1}, {-1, -1, -1}}, {{-1, -1, -1}, {-1, -1, -1}}};
-__constant__ int kNTri[16] = {0, 1, 1, 2, 1, 2, 2, 1, 1, 2, 2, 1, 2, 1, 1, 0};
-
-DEVINL int chain_corner(int t, int q) {
-    if (q == 0) return 0;
-    if (q == 3) return 7;
-    const int a = 1 << kPerm[t][0];
-    return q == 1 ? a : (a | (1 << kPerm[t][1]));
-}
-
 DEVINL long long corner_offset(int c, long long X, long long XY) { return (c & 1) + ((c >> 1) & 1) * X + ((c >> 2) & 1) * XY; }
-
-struct VoxelCountOp {                                  // code -> vertices owned
-    __host__ __device__ long long operator()(unsigned short c) const { return (long long)__builtin_popcount(c & 0x7fu); }
-};
-struct CellCountOp {                                   // code -> triangles of the cell at this corner 0
-    __host__ __device__ long long operator()(unsigned short c) const { return (long long)(c >> 8); }
-};
 
 // ------------------------------------------------------------------------------------------------------------------------- integrate
 // One thread per voxel (grid-stride); the B <= 16 views of the batch are applied in order with the voxel's state in registers, so the
@@ -62,72 +35,12 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(float* __restrict__
         sv[t] = c < 12 ? w2c[b * 12 + c] : K[b * 4 + (c - 12)];
     }
     __syncthreads();
-    const long long HW = (long long)H * W;
     for (long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x; n < N; n += (long long)gridDim.x * blockDim.x) {
         const unsigned n32 = (unsigned)n, r = n32 / (unsigned)X;      // N < 2^31: 32-bit division (a 64-bit one costs ~3x)
         const unsigned i = n32 - r * (unsigned)X, k = r / (unsigned)Y, j = r - k * (unsigned)Y;
         const float px = ox + voxel * (float)i, py = oy + voxel * (float)j, pz = oz + voxel * (float)k;
-        bool loaded = false;
-        float ts = 0.f, w = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f;
-        for (int b = 0; b < B; ++b) {
-            const float* v = sv + b * 16;
-            const float zc = ((v[8] * px + v[9] * py) + v[10] * pz) + v[11];
-            if (!(zc > 0.f)) continue;
-            const float xc = ((v[0] * px + v[1] * py) + v[2] * pz) + v[3];
-            const float yc = ((v[4] * px + v[5] * py) + v[6] * pz) + v[7];
-            // outside the image by more than a pixel: rejected on an approximate reciprocal before the two correctly rounded divisions.
-            // The estimate is within ~3e-7 (|u - cx| + |cx|) of the exact u, so the margin of 1 + 1e-6 (|c| + size) never drops a
-            // voxel-view the exact test keeps (the bits of what is fused do not depend on it); tiny z_c go to the exact test.
-            if (zc > 1e-30f) {
-                const float rz = __builtin_amdgcn_rcpf(zc);
-                const float ua = (v[12] * xc) * rz + v[14], va = (v[13] * yc) * rz + v[15];
-                const float mu = 1.f + 1e-6f * (fabsf(v[14]) + (float)W), mv = 1.f + 1e-6f * (fabsf(v[15]) + (float)H);
-                if (ua < -0.5f - mu || ua >= (float)W - 0.5f + mu || va < -0.5f - mv || va >= (float)H - 0.5f + mv) continue;
-            }
-            const float u = (v[12] * xc) / zc + v[14];
-            const float vv = (v[13] * yc) / zc + v[15];
-            const float uf = floorf(u + 0.5f), vf = floorf(vv + 0.5f);
-            if (!(uf >= 0.f && uf < (float)W && vf >= 0.f && vf < (float)H)) continue;
-            const int ui = (int)uf, vi = (int)vf;
-            const long long pix = (long long)b * HW + (long long)vi * W + ui;
-            const float d = depth[pix];
-            if (!(d > 0.f) || !(d <= depth_max)) continue;
-            if (conf) {
-                const int ci = min(vi / ds, ch - 1), cj = min(ui / ds, cw - 1);
-                if (conf[((long long)b * ch + ci) * cw + cj] < conf_min) continue;
-            }
-            const float sdf = d - zc;
-            if (sdf < -trunc) continue;
-            const float t = fminf(1.f, sdf / trunc);
-            if (!loaded) {
-                ts = tsdf[n];
-                w = weight[n];
-                if (rgb) {
-                    c0 = color[n];
-                    c1 = color[N + n];
-                    c2 = color[2 * N + n];
-                }
-                loaded = true;
-            }
-            const float w1 = w + 1.f;
-            ts = (ts * w + t) / w1;
-            if (rgb) {
-                const unsigned char* p = rgb + (long long)b * 3 * HW + (long long)vi * W + ui;
-                c0 = (c0 * w + (float)p[0]) / w1;
-                c1 = (c1 * w + (float)p[HW]) / w1;
-                c2 = (c2 * w + (float)p[2 * HW]) / w1;
-            }
-            w = w1;
-        }
-        if (loaded) {
-            tsdf[n] = ts;
-            weight[n] = w;
-            if (rgb) {
-                color[n] = c0;
-                color[N + n] = c1;
-                color[2 * N + n] = c2;
-            }
-        }
+        tsdf_fuse_voxel<false>(tsdf, weight, color, n, N, px, py, pz, sv, 0u, depth, rgb, conf, B, H, W, ch, cw, ds, conf_min, trunc,
+                               depth_max);
     }
 }
 
@@ -165,32 +78,7 @@ __global__ __launch_bounds__(256) void tsdf_mesh_count_kernel(const float* __res
             if (a < 0 || b < 0 || c < 0 || a >= X || b >= Y || c >= Z) continue;
             if (weight[n + dx + dy * XL + dz * XY] >= wth) ok |= 1u << q;
         }
-        unsigned cellv = 0;                            // bit d: the cell n - d is valid
-        for (int d = 0; d < 8; ++d) {
-            bool v = true;
-            for (int e = 0; e < 8; ++e) {
-                const int q = (((e >> 2) & 1) - ((d >> 2) & 1) + 1) * 9 + (((e >> 1) & 1) - ((d >> 1) & 1) + 1) * 3 + ((e & 1) - (d & 1) + 1);
-                v = v && ((ok >> q) & 1u);
-            }
-            cellv |= (v ? 1u : 0u) << d;
-        }
-        unsigned vm = 0;
-        for (int m = 1; m < 8; ++m) {
-            if ((((inside >> m) & 1u) != (inside & 1u))) {
-                bool any = false;
-                for (int d = 0; d < 8; ++d) any = any || (((d & m) == 0) && ((cellv >> d) & 1u));
-                if (any) vm |= 1u << (m - 1);
-            }
-        }
-        unsigned nf = 0;
-        if (cellv & 1u) {
-            for (int t = 0; t < 6; ++t) {
-                unsigned cs = 0;
-                for (int q = 0; q < 4; ++q) cs |= ((inside >> chain_corner(t, q)) & 1u) << q;
-                nf += kNTri[cs];
-            }
-        }
-        code[n] = (unsigned short)(vm | (nf << 8));
+        code[n] = mesh_code(inside, valid_cells(ok));
     }
 }
 
@@ -226,18 +114,17 @@ __global__ __launch_bounds__(256) void tsdf_mesh_emit_kernel(const float* __rest
             if (!((vm >> (m - 1)) & 1u)) continue;
             const long long u = n + corner_offset(m, XL, XY);
             const float t1 = tsdf[u];
-            const float s = t0 / (t0 - t1);
             const float p1[3] = {ox + voxel * (float)(i + (m & 1)), oy + voxel * (float)(j + ((m >> 1) & 1)),
                                  oz + voxel * (float)(k + ((m >> 2) & 1))};
             if (vi < nv) {
-                for (int a = 0; a < 3; ++a) verts[vi * 3 + a] = p0[a] + s * (p1[a] - p0[a]);
+                float ca[3] = {0.f, 0.f, 0.f}, cb[3] = {0.f, 0.f, 0.f};
                 if (vcol) {
                     for (int a = 0; a < 3; ++a) {
-                        const float ca = color[a * N + n], cb = color[a * N + u];
-                        const float c = floorf((ca + s * (cb - ca)) + 0.5f);
-                        vcol[vi * 3 + a] = (unsigned char)fminf(255.f, fmaxf(0.f, c));
+                        ca[a] = color[a * N + n];
+                        cb[a] = color[a * N + u];
                     }
                 }
+                mesh_vertex(t0, t1, p0, p1, ca, cb, verts + vi * 3, vcol ? vcol + vi * 3 : nullptr);
             }
             ++vi;
         }
@@ -276,22 +163,6 @@ __global__ __launch_bounds__(256) void tsdf_mesh_emit_kernel(const float* __rest
 
 bool dims_ok(int X, int Y, int Z) {
     return X > 0 && Y > 0 && Z > 0 && (long long)X * Y * Z < (1LL << 31);
-}
-
-int grid_for(long long N) {
-    const long long g = (N + 255) / 256;
-    return (int)(g < 256 * 64 ? g : 256 * 64);       // grid-stride beyond 64 blocks per CU
-}
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-size_t scan_temp_bytes(long long N) {                 // the larger of the two scans' scratch
-    size_t a = 0, b = 0;
-    rocprim::transform_iterator<const unsigned short*, VoxelCountOp, long long> vit(nullptr, VoxelCountOp());
-    rocprim::transform_iterator<const unsigned short*, CellCountOp, long long> fit(nullptr, CellCountOp());
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, a, vit, (long long*)nullptr, (int)(N > 0 ? N : 1), (hipStream_t)0);
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, fit, (long long*)nullptr, (int)(N > 0 ? N : 1), (hipStream_t)0);
-    return a > b ? a : b;
 }
 
 }  // namespace

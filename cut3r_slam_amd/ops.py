@@ -771,6 +771,129 @@ def tsdf_extract_mesh(tsdf, weight, color, origin, voxel, weight_threshold=1.0):
     return verts, cols, faces
 
 
+# ------------------------------------------------------------------------------------------------ sparse brick TSDF volume
+TSDF_BRICK = 8
+TSDF_BRICK_VOXELS = TSDF_BRICK ** 3
+TSDF_SPARSE_MAX_DIM = 2 ** 20           # virtual dims per axis: voxel indices stay exact in fp32
+TSDF_SPARSE_MAX_TABLE = 2 ** 28         # entries of the brick table
+
+
+def tsdf_brick_dims(dims):
+    """(BX, BY, BZ) bricks of 8 voxels covering the virtual grid (X, Y, Z)"""
+    return tuple((int(d) + TSDF_BRICK - 1) // TSDF_BRICK for d in dims)
+
+
+def _tsdf_sparse_grid(dims):
+    X, Y, Z = (int(d) for d in dims)
+    _req(min(X, Y, Z) > 0 and max(X, Y, Z) <= TSDF_SPARSE_MAX_DIM, f"sparse TSDF grid: dims in 1..{TSDF_SPARSE_MAX_DIM} per axis")
+    BX, BY, BZ = tsdf_brick_dims((X, Y, Z))
+    _req(BX * BY * BZ <= TSDF_SPARSE_MAX_TABLE, f"sparse TSDF grid: more than {TSDF_SPARSE_MAX_TABLE} table entries")
+    return X, Y, Z, BX * BY * BZ
+
+
+def _tsdf_table(t, name, dtype, T):
+    _cuda(t)
+    _req(t.dtype == dtype and t.is_contiguous() and t.numel() == T, f"{name}: contiguous {dtype} with one entry per brick of the grid")
+
+
+def _tsdf_pool(tsdf, weight, color, bricks, T):
+    """(tsdf [nb,512], weight [nb,512], color [3,nb,512]) fp32 and bricks int32 [nb] on the GPU -> nb"""
+    _cuda(tsdf, weight, color, bricks)
+    _req(tsdf.dim() == 2 and tsdf.shape[1] == TSDF_BRICK_VOXELS and tsdf.dtype == F32 and tsdf.is_contiguous(), "tsdf: contiguous fp32 [nb,512]")
+    nb = tsdf.shape[0]
+    _req(0 < nb <= T and nb * TSDF_BRICK_VOXELS < 2 ** 31, "sparse TSDF pool: 1 .. table entries bricks, fewer than 2^31 voxels")
+    _req(weight.shape == tsdf.shape and weight.dtype == F32 and weight.is_contiguous(), "weight: contiguous fp32 like tsdf")
+    _req(color.shape == (3, nb, TSDF_BRICK_VOXELS) and color.dtype == F32 and color.is_contiguous(), "color: contiguous fp32 [3,nb,512]")
+    _req(bricks.shape == (nb,) and bricks.dtype == torch.int32 and bricks.is_contiguous(), "bricks: contiguous int32 [nb]")
+    return nb
+
+
+def tsdf_sparse_mark(flags, dims, origin, voxel, depth, c2w, K, trunc, depth_max):
+    """in place: flag (u8 [BZ,BY,BX], never cleared) every brick that the views can give a negative tsdf or a 26-neighbour of one.
+    depth [B,H,W] fp32, c2w [B,12] camera->world rows (the inverse of the views' w2c), K [B,4], any B >= 1."""
+    X, Y, Z, T = _tsdf_sparse_grid(dims)
+    _tsdf_table(flags, "flags", torch.uint8, T)
+    _cuda(depth, c2w, K)
+    _req(depth.dim() == 3 and depth.dtype == F32 and depth.is_contiguous(), "depth: contiguous fp32 [B,H,W]")
+    B, H, W = depth.shape
+    _req(B >= 1 and H > 0 and W > 0 and B * H * W < 2 ** 31, "depth: 1 .. 2^31 - 1 pixels")
+    _req(c2w.shape == (B, 12) and c2w.dtype == F32 and c2w.is_contiguous(), "c2w: contiguous fp32 [B,12]")
+    _req(K.shape == (B, 4) and K.dtype == F32 and K.is_contiguous(), "K: contiguous fp32 [B,4]")
+    _req(float(voxel) > 0 and float(trunc) > 0, "voxel size and truncation must be > 0")
+    lib = _lib.load()
+    check(lib.cut3r_tsdf_sparse_mark(_p(flags), X, Y, Z, float(origin[0]), float(origin[1]), float(origin[2]), float(voxel), _p(depth), B, H, W,
+                                     _p(c2w), _p(K), float(trunc), float(depth_max), _stream()), "cut3r_tsdf_sparse_mark")
+
+
+def tsdf_sparse_assign(flags, table, dims):
+    """in place: table (int32 [BZ,BY,BX]) <- the pool slot of every flagged brick, numbered by ascending brick index, -1 elsewhere;
+    returns the number of flagged bricks (one read-back)"""
+    X, Y, Z, T = _tsdf_sparse_grid(dims)
+    _tsdf_table(flags, "flags", torch.uint8, T)
+    _tsdf_table(table, "table", torch.int32, T)
+    lib = _lib.load()
+    nbytes = lib.cut3r_tsdf_sparse_assign_workspace_bytes(X, Y, Z)
+    _req(nbytes >= 0, "sparse TSDF grid too large")
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=flags.device)
+    total = torch.empty(1, dtype=torch.int64, device=flags.device)
+    check(lib.cut3r_tsdf_sparse_assign(_p(flags), _p(table), X, Y, Z, _p(ws), nbytes, _p(total), _stream()), "cut3r_tsdf_sparse_assign")
+    return int(total.cpu())
+
+
+def tsdf_sparse_integrate(tsdf, weight, color, bricks, dims, origin, voxel, depth, w2c, K, trunc, depth_max, rgb=None, conf=None, conf_ds=1,
+                          conf_min=0.0):
+    """in place: tsdf_integrate over the allocated bricks of the virtual grid `dims` (B <= 16 views, one launch); the arguments of
+    tsdf_integrate with the pool (tsdf [nb,512], weight, color [3,nb,512]) and its brick list in place of the planes."""
+    X, Y, Z, T = _tsdf_sparse_grid(dims)
+    nb = _tsdf_pool(tsdf, weight, color, bricks, T)
+    _cuda(depth, w2c, K, rgb, conf)
+    _req(depth.dim() == 3 and depth.dtype == F32 and depth.is_contiguous(), "depth: contiguous fp32 [B,H,W]")
+    B, H, W = depth.shape
+    _req(1 <= B <= TSDF_MAX_VIEWS, f"tsdf_sparse_integrate: 1..{TSDF_MAX_VIEWS} views per launch")
+    _req(H > 0 and W > 0, "depth: empty image")
+    _req(w2c.shape == (B, 12) and w2c.dtype == F32 and w2c.is_contiguous(), "w2c: contiguous fp32 [B,12]")
+    _req(K.shape == (B, 4) and K.dtype == F32 and K.is_contiguous(), "K: contiguous fp32 [B,4]")
+    _req(float(voxel) > 0 and float(trunc) > 0, "voxel size and truncation must be > 0")
+    if rgb is not None:
+        _req(rgb.shape == (B, 3, H, W) and rgb.dtype == torch.uint8 and rgb.is_contiguous(), "rgb: contiguous uint8 [B,3,H,W]")
+    ch = cw = 0
+    if conf is not None:
+        _req(conf.dim() == 3 and conf.shape[0] == B and conf.dtype == F32 and conf.is_contiguous(), "conf: contiguous fp32 [B,h,w]")
+        ch, cw = conf.shape[1:]
+        _req(int(conf_ds) >= 1 and ch > 0 and cw > 0, "conf: stride >= 1, non-empty")
+    lib = _lib.load()
+    check(lib.cut3r_tsdf_sparse_integrate(_p(tsdf), _p(weight), _p(color), _p(bricks), nb, X, Y, Z, float(origin[0]), float(origin[1]),
+                                          float(origin[2]), float(voxel), _p(depth), _p(rgb), _p(conf), B, H, W, ch, cw, int(conf_ds),
+                                          float(conf_min), _p(w2c), _p(K), float(trunc), float(depth_max), _stream()),
+          "cut3r_tsdf_sparse_integrate")
+
+
+def tsdf_sparse_extract_mesh(tsdf, weight, color, table, bricks, dims, origin, voxel, weight_threshold=1.0):
+    """tsdf_extract_mesh over the pool: vertices in (pool voxel, direction mask) order, faces in (pool cell, tetrahedron, triangle)
+    order -> (vertices fp32 [V,3], colors u8 [V,3], faces int32 [F,3]) on the GPU"""
+    X, Y, Z, T = _tsdf_sparse_grid(dims)
+    nb = _tsdf_pool(tsdf, weight, color, bricks, T)
+    _tsdf_table(table, "table", torch.int32, T)
+    _req(float(voxel) > 0, "voxel size must be > 0")
+    lib = _lib.load()
+    dev = tsdf.device
+    nbytes = lib.cut3r_tsdf_sparse_mesh_workspace_bytes(nb)
+    _req(nbytes > 0, "sparse TSDF pool too large")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    totals = torch.empty(2, dtype=torch.int64, device=dev)
+    check(lib.cut3r_tsdf_sparse_mesh_count(_p(tsdf), _p(weight), _p(table), _p(bricks), nb, X, Y, Z, float(weight_threshold), _p(ws), nbytes,
+                                           _p(totals), _stream()), "cut3r_tsdf_sparse_mesh_count")
+    nv, nf = (int(v) for v in totals.cpu())
+    _req(nv < 2 ** 31, f"mesh of {nv} vertices: int32 face indices cannot address it")
+    verts = torch.empty(nv, 3, dtype=F32, device=dev)
+    cols = torch.empty(nv, 3, dtype=torch.uint8, device=dev)
+    faces = torch.empty(nf, 3, dtype=torch.int32, device=dev)
+    check(lib.cut3r_tsdf_sparse_mesh_emit(_p(tsdf), _p(color), _p(table), _p(bricks), nb, X, Y, Z, float(origin[0]), float(origin[1]),
+                                          float(origin[2]), float(voxel), _p(ws), nbytes, _p(verts), _p(cols), _p(faces), nv, nf, _stream()),
+          "cut3r_tsdf_sparse_mesh_emit")
+    return verts, cols, faces
+
+
 # ------------------------------------------------------------------------------------------------ reconstruction metrics
 def _points(t, name):
     _cuda(t)

@@ -3,7 +3,10 @@
 The reference makes a mesh after every run (scripts/run_replica.py:40-52 -> tsdf_integrate.py): the keyframe depth and colour renders
 of the Gaussian map go into an Open3D VoxelBlockGrid and `tsdf_mesh_w{w:.1f}.ply` is written per weight threshold.  Here:
 
-  TSDFVolume       a DENSE voxel grid in HBM (fp32 planes tsdf, weight, color[3]: 20 B per voxel; sparse blocks are not built)
+  TSDFVolume       a DENSE voxel grid in HBM (fp32 planes tsdf, weight, color[3]: 20 B per voxel), at most 2^31 - 1 voxels
+  SparseTSDFVolume the same lattice and the same per-voxel fusion restricted to allocated bricks of 8^3 voxels (csrc/tsdf_sparse.hip):
+                   memory follows the surface area, so a floor of rooms, a finer voxel or objects far apart fit where the dense grid
+                   raises; on its allocated voxels it holds the dense grid's bits and its mesh is the dense mesh (`sparse=True` below)
   fuse_keyframes   the tracker's keyframe store (depth, image, w2c, intrinsics, optional confidence gate) -> TSDFVolume
   fuse_mapper      the reference's source: every mapper keyframe rendered at its refined pose, quantised as the reference's files are
                    (hislam2/gaussian/utils/eval_utils.py:124-134: depth uint16 at 6553.5 per metre, colour (x*255) truncated to u8)
@@ -31,6 +34,34 @@ class Mesh(NamedTuple):
     faces: np.ndarray           # int32 [F,3]
 
 
+def _lattice(lo, hi, voxel_size, pad):
+    """(lo - pad, dims) of the voxel lattice over [lo - pad, hi + pad]: the last centre at >= hi + pad"""
+    lo = np.asarray(lo, np.float64) - pad
+    hi = np.asarray(hi, np.float64) + pad
+    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(hi >= lo)):
+        raise ValueError(f"TSDF bounds {lo} .. {hi} are not a box")
+    return lo, [int(math.ceil((h - l) / voxel_size - 1e-6)) + 1 for l, h in zip(lo, hi)]
+
+
+def _views(dev, depth, w2c, K, rgb, conf, conf_min):
+    """the views of integrate() as the kernels take them: depth [B,H,W], w2c [B,12], K [B,4] fp32, rgb u8, conf fp32 or None"""
+    depth = torch.as_tensor(depth).to(dev, torch.float32).contiguous()
+    if depth.dim() == 2:
+        depth = depth[None]
+    B = depth.shape[0]
+    w2c = torch.as_tensor(w2c).to(dev, torch.float32)
+    w2c = (w2c.reshape(B, -1, 4)[:, :3] if w2c.shape[-2:] in ((3, 4), (4, 4)) else w2c.reshape(B, 12)).reshape(B, 12).contiguous()
+    K = torch.as_tensor(K).to(dev, torch.float32).reshape(-1, 4)
+    K = (K.expand(B, 4) if K.shape[0] == 1 else K).contiguous()
+    if rgb is not None:
+        rgb = torch.as_tensor(rgb).to(dev).contiguous()
+    if conf is not None and conf_min is not None:
+        conf = torch.as_tensor(conf).to(dev, torch.float32).contiguous()
+    else:
+        conf = None
+    return depth, w2c, K, rgb, conf
+
+
 class TSDFVolume:
     """Dense TSDF grid: voxel (i, j, k) at origin + voxel_size * (i, j, k), planes [Z,Y,X] (x fastest); tsdf = 1, weight = color = 0 at start."""
 
@@ -53,11 +84,7 @@ class TSDFVolume:
     @staticmethod
     def grid_for(lo, hi, voxel_size, pad, max_voxels=2 ** 30):
         """(origin, dims) of the grid over [lo - pad, hi + pad]; ValueError naming the memory when it exceeds max_voxels"""
-        lo = np.asarray(lo, np.float64) - pad
-        hi = np.asarray(hi, np.float64) + pad
-        if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(hi >= lo)):
-            raise ValueError(f"TSDF bounds {lo} .. {hi} are not a box")
-        dims = [int(math.ceil((h - l) / voxel_size - 1e-6)) + 1 for l, h in zip(lo, hi)]    # the last centre at >= hi
+        lo, dims = _lattice(lo, hi, voxel_size, pad)
         n = dims[0] * dims[1] * dims[2]
         if n > max_voxels or n >= 2 ** 31:
             raise ValueError(f"TSDF grid {dims[0]}x{dims[1]}x{dims[2]} = {n} voxels needs {n * 20 / 1e9:.1f} GB at 20 B per voxel "
@@ -79,21 +106,8 @@ class TSDFVolume:
     def integrate(self, depth, w2c, K, rgb=None, conf=None, conf_ds=1, conf_min=None):
         """fuse B views in order, in launches of <= 16.  depth [B,H,W] metres; w2c [B,12] (or [B,3,4] / [B,4,4]) world->camera; K [4] or
         [B,4] fx fy cx cy; rgb u8 [B,3,H,W]; conf [B,h,w] at stride conf_ds, pixels with conf < conf_min skipped (conf_min None: no gate)."""
-        dev = self.device
-        depth = torch.as_tensor(depth).to(dev, torch.float32).contiguous()
-        if depth.dim() == 2:
-            depth = depth[None]
+        depth, w2c, K, rgb, conf = _views(self.device, depth, w2c, K, rgb, conf, conf_min)
         B = depth.shape[0]
-        w2c = torch.as_tensor(w2c).to(dev, torch.float32)
-        w2c = (w2c.reshape(B, -1, 4)[:, :3] if w2c.shape[-2:] in ((3, 4), (4, 4)) else w2c.reshape(B, 12)).reshape(B, 12).contiguous()
-        K = torch.as_tensor(K).to(dev, torch.float32).reshape(-1, 4)
-        K = (K.expand(B, 4) if K.shape[0] == 1 else K).contiguous()
-        if rgb is not None:
-            rgb = torch.as_tensor(rgb).to(dev).contiguous()
-        if conf is not None and conf_min is not None:
-            conf = torch.as_tensor(conf).to(dev, torch.float32).contiguous()
-        else:
-            conf = None
         for a in range(0, B, ops.TSDF_MAX_VIEWS):
             b = min(B, a + ops.TSDF_MAX_VIEWS)
             ops.tsdf_integrate(self.tsdf, self.weight, self.color, self.origin, self.voxel_size, depth[a:b], w2c[a:b], K[a:b], self.trunc,
@@ -105,6 +119,156 @@ class TSDFVolume:
     def extract_mesh(self, weight_threshold=1.0) -> Mesh:
         v, c, f = ops.tsdf_extract_mesh(self.tsdf, self.weight, self.color, self.origin, self.voxel_size, weight_threshold)
         return Mesh(v.cpu().numpy(), c.cpu().numpy(), f.cpu().numpy())
+
+
+def c2w_rows(w2c):
+    """camera->world rows fp32 [B,12] of world->camera rows [B,12]: the inverse of each 3x4 affine map, in float64 on the host (the mark
+    kernel back-projects with them; any invertible w2c will do, a rigid one gives R^T, -R^T t)"""
+    w = np.asarray(w2c, np.float64).reshape(-1, 3, 4)
+    Ri = np.linalg.inv(w[:, :, :3])
+    ti = -(Ri @ w[:, :, 3:])
+    return np.ascontiguousarray(np.concatenate([Ri, ti], 2).reshape(-1, 12), dtype=np.float32)
+
+
+class SparseTSDFVolume:
+    """Sparse TSDF volume: the lattice of TSDFVolume over a VIRTUAL grid `dims` (voxel (i, j, k) at origin + voxel_size * (i, j, k)), stored
+    only where bricks of 8^3 voxels are allocated.  An allocated voxel holds what the dense grid would hold, bit for bit: every view
+    updates every allocated voxel it would update there, free space included.
+
+    allocate() flags the bricks that the views can give a negative tsdf, or a 26-neighbour of one (a superset, from the depth maps
+    alone), so the mesh of a volume whose views were all allocated before any was integrated equals the dense mesh as a set of
+    triangles; vertices come in (pool voxel, direction mask) order, faces in (pool cell, tetrahedron, triangle) order.  A brick
+    allocated after some views were integrated has missed those views: integrate(allocate=True) on a fresh volume, or allocate() over
+    all views first and integrate(allocate=False) after, as fuse_keyframes / fuse_mapper do.
+
+    Limits: dims <= 2^20 per axis, ceil(dims / 8) bricks <= 2^28 table entries (5 B each), allocated voxels < 2^31."""
+
+    def __init__(self, origin, voxel_size, dims, trunc_voxels=8.0, depth_max=5.0, device="cuda:0"):
+        X, Y, Z = (int(d) for d in dims)
+        if min(X, Y, Z) <= 0 or max(X, Y, Z) > ops.TSDF_SPARSE_MAX_DIM:
+            raise ValueError(f"sparse TSDF grid {X}x{Y}x{Z}: dims must be in 1..{ops.TSDF_SPARSE_MAX_DIM} per axis")
+        BX, BY, BZ = ops.tsdf_brick_dims((X, Y, Z))
+        if BX * BY * BZ > ops.TSDF_SPARSE_MAX_TABLE:
+            raise ValueError(f"sparse TSDF grid {X}x{Y}x{Z}: {BX * BY * BZ} bricks exceed the table limit of {ops.TSDF_SPARSE_MAX_TABLE} entries")
+        if not voxel_size > 0 or not trunc_voxels > 0:
+            raise ValueError("voxel_size and trunc_voxels must be > 0")
+        self.origin = tuple(float(np.float32(o)) for o in origin)
+        self.voxel_size = float(np.float32(voxel_size))
+        self.dims = (X, Y, Z)
+        self.brick_dims = (BX, BY, BZ)
+        self.trunc = float(np.float32(trunc_voxels * self.voxel_size))
+        self.depth_max = float(depth_max)
+        self.device = torch.device(device)
+        self.flags = torch.zeros(BZ, BY, BX, dtype=torch.uint8, device=self.device)
+        self.table = torch.full((BZ, BY, BX), -1, dtype=torch.int32, device=self.device)
+        self.bricks = torch.zeros(0, dtype=torch.int32, device=self.device)
+        self.tsdf = torch.ones(0, ops.TSDF_BRICK_VOXELS, dtype=torch.float32, device=self.device)
+        self.weight = torch.zeros(0, ops.TSDF_BRICK_VOXELS, dtype=torch.float32, device=self.device)
+        self.color = torch.zeros(3, 0, ops.TSDF_BRICK_VOXELS, dtype=torch.float32, device=self.device)
+
+    @staticmethod
+    def grid_for(lo, hi, voxel_size, pad, max_bricks=ops.TSDF_SPARSE_MAX_TABLE):
+        """(origin, dims) of the virtual grid over [lo - pad, hi + pad], the lattice TSDFVolume.grid_for gives; ValueError when it has
+        more than max_bricks bricks of 8^3 voxels (the table holds 5 B per brick, allocated or not)"""
+        lo, dims = _lattice(lo, hi, voxel_size, pad)
+        nb = int(np.prod([(d + ops.TSDF_BRICK - 1) // ops.TSDF_BRICK for d in dims], dtype=object))
+        cap = min(int(max_bricks), ops.TSDF_SPARSE_MAX_TABLE)
+        if max(dims) > ops.TSDF_SPARSE_MAX_DIM or nb > cap:
+            raise ValueError(f"sparse TSDF grid {dims[0]}x{dims[1]}x{dims[2]} = {nb} bricks needs a {nb * 5 / 1e9:.1f} GB table at 5 B per brick "
+                             f"(limit {cap} bricks, {ops.TSDF_SPARSE_MAX_DIM} voxels per axis): raise voxel_size or tighten the bounds")
+        return tuple(float(v) for v in lo), tuple(dims)
+
+    @classmethod
+    def from_bounds(cls, lo, hi, voxel_size, pad=None, max_bricks=ops.TSDF_SPARSE_MAX_TABLE, trunc_voxels=8.0, depth_max=5.0, device="cuda:0"):
+        """the virtual grid covering the box [lo, hi] padded by `pad` (default: the truncation distance); nothing is allocated yet"""
+        pad = trunc_voxels * voxel_size if pad is None else pad
+        origin, dims = cls.grid_for(lo, hi, voxel_size, pad, max_bricks)
+        return cls(origin, voxel_size, dims, trunc_voxels=trunc_voxels, depth_max=depth_max, device=device)
+
+    @property
+    def n_bricks(self):
+        return int(self.bricks.shape[0])
+
+    @property
+    def nbytes(self):
+        """pool (20 B per allocated voxel) + brick list + table and flags (5 B per brick of the virtual grid)"""
+        return (20 * ops.TSDF_BRICK_VOXELS + 4) * self.n_bricks + 5 * self.table.numel()
+
+    @torch.no_grad()
+    def allocate(self, depth, w2c, K):
+        """allocate the bricks the views can give a negative tsdf or a neighbour of one; returns how many were added.  Bricks already
+        there keep their values; a new brick starts at tsdf = 1, weight = color = 0 and has missed every view integrated so far."""
+        depth, w2c, K, _, _ = _views(self.device, depth, w2c, K, None, None, None)
+        c2w = torch.from_numpy(c2w_rows(w2c.cpu().numpy())).to(self.device)
+        ops.tsdf_sparse_mark(self.flags, self.dims, self.origin, self.voxel_size, depth, c2w, K, self.trunc, self.depth_max)
+        old = self.bricks
+        n = ops.tsdf_sparse_assign(self.flags, self.table, self.dims)
+        if n == old.shape[0]:
+            return 0
+        if n * ops.TSDF_BRICK_VOXELS >= 2 ** 31:
+            raise ValueError(f"sparse TSDF pool of {n} bricks: 2^31 voxels or more ({n * ops.TSDF_BRICK_VOXELS * 20 / 1e9:.1f} GB)")
+        self.bricks = torch.nonzero(self.flags.reshape(-1)).reshape(-1).to(torch.int32)
+        tsdf = torch.ones(n, ops.TSDF_BRICK_VOXELS, dtype=torch.float32, device=self.device)
+        weight = torch.zeros(n, ops.TSDF_BRICK_VOXELS, dtype=torch.float32, device=self.device)
+        color = torch.zeros(3, n, ops.TSDF_BRICK_VOXELS, dtype=torch.float32, device=self.device)
+        if old.shape[0]:
+            slot = self.table.reshape(-1)[old.long()].long()           # where the bricks that were there have moved
+            tsdf[slot], weight[slot], color[:, slot] = self.tsdf, self.weight, self.color
+        self.tsdf, self.weight, self.color = tsdf, weight, color
+        return n - int(old.shape[0])
+
+    @torch.no_grad()
+    def integrate(self, depth, w2c, K, rgb=None, conf=None, conf_ds=1, conf_min=None, allocate=True):
+        """TSDFVolume.integrate over the allocated bricks.  allocate=True first allocates for ALL the views given (then fuses them in
+        launches of <= 16): right for a fresh volume; on a volume that already holds views, the bricks it adds have missed those."""
+        depth, w2c, K, rgb, conf = _views(self.device, depth, w2c, K, rgb, conf, conf_min)
+        if allocate:
+            self.allocate(depth, w2c, K)
+        if self.n_bricks == 0:
+            return self
+        B = depth.shape[0]
+        for a in range(0, B, ops.TSDF_MAX_VIEWS):
+            b = min(B, a + ops.TSDF_MAX_VIEWS)
+            ops.tsdf_sparse_integrate(self.tsdf, self.weight, self.color, self.bricks, self.dims, self.origin, self.voxel_size, depth[a:b],
+                                      w2c[a:b], K[a:b], self.trunc, self.depth_max, rgb=None if rgb is None else rgb[a:b],
+                                      conf=None if conf is None else conf[a:b], conf_ds=conf_ds, conf_min=0.0 if conf_min is None else conf_min)
+        return self
+
+    @torch.no_grad()
+    def extract_mesh(self, weight_threshold=1.0) -> Mesh:
+        if self.n_bricks == 0:
+            return Mesh(np.zeros((0, 3), np.float32), np.zeros((0, 3), np.uint8), np.zeros((0, 3), np.int32))
+        v, c, f = ops.tsdf_sparse_extract_mesh(self.tsdf, self.weight, self.color, self.table, self.bricks, self.dims, self.origin,
+                                               self.voxel_size, weight_threshold)
+        return Mesh(v.cpu().numpy(), c.cpu().numpy(), f.cpu().numpy())
+
+    @torch.no_grad()
+    def allocated_mask(self):
+        """bool [Z,Y,X]: the voxels of the virtual grid that are stored (raises above the dense limit of 2^31 - 1 voxels)"""
+        X, Y, Z = self._dense_dims()
+        m = self.flags.bool()[:, None, :, None, :, None].expand(-1, 8, -1, 8, -1, 8)
+        return m.reshape(self.brick_dims[2] * 8, self.brick_dims[1] * 8, self.brick_dims[0] * 8)[:Z, :Y, :X].contiguous()
+
+    def _dense_dims(self):
+        X, Y, Z = self.dims
+        if self.table.numel() * ops.TSDF_BRICK_VOXELS >= 2 ** 31:
+            raise ValueError(f"sparse TSDF grid {X}x{Y}x{Z}: too large for dense planes (2^31 voxels or more)")
+        return X, Y, Z
+
+    @torch.no_grad()
+    def to_dense(self):
+        """(tsdf [Z,Y,X], weight [Z,Y,X], color [3,Z,Y,X]) of the virtual grid, 1 / 0 / 0 where nothing is allocated (raises above the
+        dense limit of 2^31 - 1 voxels)"""
+        X, Y, Z = self._dense_dims()
+        BX, BY, BZ = self.brick_dims
+        t = self.bricks.long()
+        bx, by, bz = t % BX, (t // BX) % BY, t // (BX * BY)
+        out = []
+        for pool, init in ((self.tsdf, 1.0), (self.weight, 0.0), (self.color[0], 0.0), (self.color[1], 0.0), (self.color[2], 0.0)):
+            d = torch.full((BZ, 8, BY, 8, BX, 8), init, dtype=torch.float32, device=self.device)
+            d[bz, :, by, :, bx, :] = pool.reshape(-1, 8, 8, 8)
+            out.append(d.reshape(BZ * 8, BY * 8, BX * 8)[:Z, :Y, :X].contiguous())
+        return out[0], out[1], torch.stack(out[2:])
 
 
 # ------------------------------------------------------------------------------------------------------------------------ PLY
@@ -205,20 +369,23 @@ def depth_bounds(depth, w2c, K, depth_max):
     return lo.cpu().numpy(), hi.cpu().numpy()
 
 
-def _volume_for(depth, w2c, K, voxel_size, trunc_voxels, depth_max, bounds, max_voxels, device):
+def _volume_for(depth, w2c, K, voxel_size, trunc_voxels, depth_max, bounds, max_voxels, device, sparse=False):
     if bounds is None:
         bounds = depth_bounds(depth, w2c, K, depth_max)
         if bounds is None:
             raise ValueError(f"no depth in (0, {depth_max}]: nothing to fuse")
+    if sparse:                                                       # max_voxels caps the dense grid only
+        return SparseTSDFVolume.from_bounds(bounds[0], bounds[1], voxel_size, trunc_voxels=trunc_voxels, depth_max=depth_max, device=device)
     return TSDFVolume.from_bounds(bounds[0], bounds[1], voxel_size, max_voxels=max_voxels, trunc_voxels=trunc_voxels, depth_max=depth_max,
                                   device=device)
 
 
 @torch.no_grad()
-def fuse_keyframes(keyframes, n, voxel_size, trunc_voxels=8.0, depth_max=5.0, conf_min=None, bounds=None, max_voxels=2 ** 30):
+def fuse_keyframes(keyframes, n, voxel_size, trunc_voxels=8.0, depth_max=5.0, conf_min=None, bounds=None, max_voxels=2 ** 30, sparse=False):
     """the tracker's keyframes 0..n-1: depth (s*z at tracking resolution), image, the device world->camera rows and the intrinsics; with
     conf_min, pixels whose stored confidence (conf_ds[i // 5, i % 5], at the store's downsample ratio) is below it are skipped.
-    bounds: (lo, hi) or None = the AABB of the valid depths padded by the truncation distance."""
+    bounds: (lo, hi) or None = the AABB of the valid depths padded by the truncation distance.  sparse: a SparseTSDFVolume (bricks
+    allocated over all views, then all views fused) in place of the dense grid; max_voxels does not apply to it."""
     kf = keyframes
     n = int(n)
     if n <= 0:
@@ -232,7 +399,10 @@ def fuse_keyframes(keyframes, n, voxel_size, trunc_voxels=8.0, depth_max=5.0, co
     if conf_min is not None:
         idx = torch.arange(n, device=dev)
         conf = kf.conf_ds[idx // 5, idx % 5].contiguous()
-    vol = _volume_for(depth, w2c, K, voxel_size, trunc_voxels, depth_max, bounds, max_voxels, dev)
+    vol = _volume_for(depth, w2c, K, voxel_size, trunc_voxels, depth_max, bounds, max_voxels, dev, sparse)
+    if sparse:
+        vol.allocate(depth, w2c, K)
+        return vol.integrate(depth, w2c, K, rgb=rgb, conf=conf, conf_ds=kf.downsample_ratio, conf_min=conf_min, allocate=False)
     return vol.integrate(depth, w2c, K, rgb=rgb, conf=conf, conf_ds=kf.downsample_ratio, conf_min=conf_min)
 
 
@@ -260,11 +430,14 @@ def render_mapper_views(mapper):
 
 
 @torch.no_grad()
-def fuse_mapper(mapper, voxel_size, trunc_voxels=8.0, depth_max=5.0, bounds=None, max_voxels=2 ** 30):
+def fuse_mapper(mapper, voxel_size, trunc_voxels=8.0, depth_max=5.0, bounds=None, max_voxels=2 ** 30, sparse=False):
     """the reference's source (tsdf_integrate.py over renders_kf/*_after_opt): every mapper keyframe rendered at its refined pose.  The
-    intrinsics are the views' own, as the reference passes intrinsics.npy unchanged."""
+    intrinsics are the views' own, as the reference passes intrinsics.npy unchanged.  sparse: as in fuse_keyframes."""
     if not mapper.viewpoints:
         raise ValueError("the mapper has no keyframes to fuse")
     depth, rgb, w2c, K = render_mapper_views(mapper)
-    vol = _volume_for(depth, w2c, K, voxel_size, trunc_voxels, depth_max, bounds, max_voxels, mapper.device)
+    vol = _volume_for(depth, w2c, K, voxel_size, trunc_voxels, depth_max, bounds, max_voxels, mapper.device, sparse)
+    if sparse:
+        vol.allocate(depth, w2c, K)
+        return vol.integrate(depth, w2c, K, rgb=rgb, allocate=False)
     return vol.integrate(depth, w2c, K, rgb=rgb)

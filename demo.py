@@ -78,6 +78,8 @@ def main(argv=None):
     p.add_argument("--mesh-weight", type=float, nargs="+", default=[1.0], help="weight thresholds of the extracted meshes")
     p.add_argument("--mesh-source", choices=("auto", "tracker", "mapper"), default="auto",
                    help="auto: the Gaussian map's keyframe renders with --gs, else the tracked keyframes")
+    p.add_argument("--mesh-sparse", action="store_true", help="with --mesh: fuse into the sparse brick volume (bricks of 8^3 voxels near "
+                   "surfaces only: the same mesh, memory by surface area, no 2^31-voxel limit)")
     p.add_argument("--gt-mesh", type=str, default=None, help="score every mesh written against this GT mesh (scripts/eval_recon.py "
                    "--eval_3d) -> <output>/eval_recon_w{W:.1f}.txt; needs --mesh")
     p.add_argument("--gt-traj", type=str, default=None, help="TUM ground-truth trajectory: the Sim(3) of traj_kf.txt onto it is applied to "
@@ -89,6 +91,8 @@ def main(argv=None):
     args = p.parse_args(argv)
     if args.gt_mesh and not args.mesh:
         p.error("--gt-mesh needs --mesh")
+    if args.mesh_sparse and not args.mesh:
+        p.error("--mesh-sparse needs --mesh")
     if args.eval_2d and not args.gt_mesh:
         p.error("--eval-2d needs --gt-mesh")
     if args.gt_unseen and not args.eval_2d:
@@ -172,11 +176,15 @@ def main(argv=None):
     if args.mesh:
         from cut3r_slam_amd.tsdf import write_ply
         t_int = time.time()
-        vol = slam.fuse(args.voxel_size, depth_max=args.depth_max, source=args.mesh_source)
+        vol = slam.fuse(args.voxel_size, depth_max=args.depth_max, source=args.mesh_source, sparse=args.mesh_sparse)
         torch.cuda.synchronize()
         t_int = time.time() - t_int
         X, Y, Z = vol.dims
-        print(f"TSDF: {X}x{Y}x{Z} voxels of {vol.voxel_size:g} ({vol.nbytes / 1e9:.2f} GB), integrated in {1e3 * t_int:.1f} ms")
+        if args.mesh_sparse:
+            print(f"TSDF: {X}x{Y}x{Z} voxels of {vol.voxel_size:g}, {vol.n_bricks} of {vol.table.numel()} bricks allocated "
+                  f"({vol.nbytes / 1e9:.2f} GB), allocated and integrated in {1e3 * t_int:.1f} ms")
+        else:
+            print(f"TSDF: {X}x{Y}x{Z} voxels of {vol.voxel_size:g} ({vol.nbytes / 1e9:.2f} GB), integrated in {1e3 * t_int:.1f} ms")
         for w in args.mesh_weight:
             t_ext = time.time()
             mesh = vol.extract_mesh(w)

@@ -499,6 +499,40 @@ int cut3r_tsdf_mesh_emit(const float* tsdf, const float* color, int X, int Y, in
                          const void* workspace, long long workspace_bytes, float* verts, unsigned char* colors, int* faces, long long nv,
                          long long nf, void* stream);
 
+/* ---- Sparse brick TSDF volume (csrc/tsdf_sparse.hip) --------------------------------------------------------------------------------
+ * The dense volume above restricted to allocated bricks of 8x8x8 voxels: the same lattice over a VIRTUAL grid X x Y x Z (each <= 2^20),
+ * the same per-voxel fusion, so an allocated voxel holds the dense grid's bits.  B* = ceil(dim / 8), T = BX*BY*BZ <= 2^28 table entries.
+ *   flags  u8 [T]     1 = brick allocated (t = (bz*BY + by)*BX + bx)
+ *   table  int32 [T]  pool slot or -1; slots number the flagged bricks by ascending t
+ *   bricks int32 [nb] t of every slot, ascending; nb * 512 < 2^31
+ *   pool   tsdf [nb*512], weight [nb*512], color [3][nb*512]; voxel (lk*8 + lj)*8 + li inside its brick; initial values 1 / 0 / 0
+ *
+ * mark sets (never clears) the flag of every brick that a view of the batch (any B >= 1, B*H*W < 2^31) can give a negative tsdf or a
+ * 26-neighbour of one: per pixel with 0 < d <= depth_max the slab u +- 0.5, v +- 0.5, z in [d, d + trunc] in two z-segments, the world
+ * AABB of each segment's 8 corners through c2w [B,12] (camera->world rows, the inverse of w2c), dilated by 1.5 voxels.  assign numbers
+ * the flagged bricks (exclusive scan) into table and writes their count to total [1] (int64, device).  The caller builds `bricks` and
+ * sizes the pool; a brick allocated after views were integrated has missed those views.
+ *
+ * integrate = cut3r_tsdf_integrate over the pool: one workgroup per brick, views whose frustum the brick's bounding sphere misses are
+ * dropped for the whole brick.  mesh_count / mesh_emit = the dense pair over the pool voxels; an in-grid voxel of a brick that is not
+ * allocated reads as tsdf = 1, weight = 0.  Vertices in (pool voxel, direction mask) order, faces in (pool cell, tetrahedron,
+ * triangle) order.  Workspace: 18 B per pool voxel + scan scratch. */
+int cut3r_tsdf_sparse_mark(unsigned char* flags, int X, int Y, int Z, float ox, float oy, float oz, float voxel, const float* depth, int B,
+                           int H, int W, const float* c2w, const float* K, float trunc, float depth_max, void* stream);
+long long cut3r_tsdf_sparse_assign_workspace_bytes(int X, int Y, int Z);       /* -1 on bad dimensions */
+int cut3r_tsdf_sparse_assign(const unsigned char* flags, int* table, int X, int Y, int Z, void* workspace, long long workspace_bytes,
+                             long long* total, void* stream);
+int cut3r_tsdf_sparse_integrate(float* tsdf, float* weight, float* color, const int* bricks, int nb, int X, int Y, int Z, float ox, float oy,
+                                float oz, float voxel, const float* depth, const unsigned char* rgb, const float* conf, int B, int H, int W,
+                                int ch, int cw, int ds, float conf_min, const float* w2c, const float* K, float trunc, float depth_max,
+                                void* stream);
+long long cut3r_tsdf_sparse_mesh_workspace_bytes(int nb);                      /* -1 on a bad brick count */
+int cut3r_tsdf_sparse_mesh_count(const float* tsdf, const float* weight, const int* table, const int* bricks, int nb, int X, int Y, int Z,
+                                 float weight_threshold, void* workspace, long long workspace_bytes, long long* totals, void* stream);
+int cut3r_tsdf_sparse_mesh_emit(const float* tsdf, const float* color, const int* table, const int* bricks, int nb, int X, int Y, int Z,
+                                float ox, float oy, float oz, float voxel, const void* workspace, long long workspace_bytes, float* verts,
+                                unsigned char* colors, int* faces, long long nv, long long nf, void* stream);
+
 /* ---- Reconstruction metrics (csrc/recon.hip) ----------------------------------------------------------------------------------------
  * mesh_area_cdf / mesh_sample replace trimesh.sample.sample_surface (scripts/eval_recon.py:104-107).  verts [V,3] fp32, faces [F,3] int32
  * (a face with an index outside 0..V-1 has area 0).  area_cdf: area [F] fp32 = 0.5 |(b - a) x (c - a)|, cdf [F] fp64 = inclusive scan of

@@ -4,9 +4,12 @@ a 6 x 5 x 3 m box, fused at each voxel size (default 0.02 m and 0.006 m, the fin
 
 Per voxel size: integration time of the 300 views at B = 1 (300 launches) and B = 16 (19 launches), voxel-view updates/s, effective
 HBM bytes/s against the measured 6.3 TB/s (bytes = 40 B read + written per voxel a launch updates + the images it reads), and the
-extraction entry points (count + two scans, totals read-back, emit).  Host clock around work that ends in a device synchronise,
+extraction entry points (count + two scans, totals read-back, emit).  With --sparse also the sparse brick volume
+(csrc/tsdf_sparse.hip) on the same views: bricks allocated against the minimal set (the bricks holding a voxel with tsdf < 0 or one of
+its 26 neighbours, from the dense volume), bytes against the dense 38 B per voxel, allocation / integration / extraction times, and
+whether its mesh has the dense mesh's vertex and face counts.  Host clock around work that ends in a device synchronise,
 after a warm-up of every shape; best of --reps.  Kernel-level split of count / scan / emit: run under `rocprofv3 --kernel-trace --stats`.
-usage: python tools/bench_tsdf.py [--voxel 0.02 0.006] [--views 300] [--reps 2] [--json out.json]"""
+usage: python tools/bench_tsdf.py [--voxel 0.02 0.006] [--views 300] [--reps 2] [--sparse] [--json out.json]"""
 import argparse
 import json
 import math
@@ -19,7 +22,7 @@ import numpy as np
 import torch
 
 from cut3r_slam_amd import _lib, ops
-from cut3r_slam_amd.tsdf import TSDFVolume
+from cut3r_slam_amd.tsdf import SparseTSDFVolume, TSDFVolume
 
 HBM_TBS = 6.3          # measured float4 copy rate of the MI355X (MI355X_MICROARCH: 6.29 TB/s)
 ROOM = (6.0, 5.0, 3.0)
@@ -95,7 +98,59 @@ def touched_bytes(vol, depth, w2c, K, rgb, B):
     return 40 * touched + n * H * W * 7, touched, float(vol.weight.double().sum())
 
 
-def bench_voxel(voxel, depth, rgb, w2c, K, reps):
+@torch.no_grad()
+def minimal_bricks(tsdf):
+    """bricks of 8^3 voxels that hold a voxel with tsdf < 0 or one of its 26 neighbours"""
+    need = tsdf < 0
+    for ax in range(3):                                                  # the 3x3x3 dilation, one axis at a time
+        grown = need.clone()
+        lo, hi = [slice(None)] * 3, [slice(None)] * 3
+        lo[ax], hi[ax] = slice(0, -1), slice(1, None)
+        grown[tuple(lo)] |= need[tuple(hi)]
+        grown[tuple(hi)] |= need[tuple(lo)]
+        need = grown
+    Z, Y, X = need.shape
+    need = torch.nn.functional.pad(need, (0, -X % 8, 0, -Y % 8, 0, -Z % 8))
+    Z, Y, X = need.shape
+    return int(need.reshape(Z // 8, 8, Y // 8, 8, X // 8, 8).any(5).any(3).any(1).sum())
+
+
+def bench_sparse(vol, nv, nf, depth, rgb, w2c, K, reps):
+    """the sparse volume on the lattice of the dense `vol` (which holds the fused views): allocate all views, integrate at B = 16, extract"""
+    n = depth.shape[0]
+    X, Y, Z = vol.dims
+    made = []
+
+    def fresh():
+        made[:] = [SparseTSDFVolume(vol.origin, vol.voxel_size, vol.dims, depth_max=vol.depth_max, device=DEV)]
+
+    def allocate():
+        fresh()
+        made[0].allocate(depth, w2c, K)
+
+    def both():
+        allocate()
+        made[0].integrate(depth, w2c, K, rgb=rgb, allocate=False)
+
+    both()                                                               # warm-up
+    t_fresh = timed(fresh, reps)
+    t_alloc = timed(allocate, reps) - t_fresh
+    t_both = timed(both, reps) - t_fresh
+    sp = made[0]
+    t_ext = timed(lambda: sp.extract_mesh(1.0), reps)
+    mesh = sp.extract_mesh(1.0)
+    ws = _lib.load().cut3r_tsdf_sparse_mesh_workspace_bytes(sp.n_bricks)
+    need = minimal_bricks(vol.tsdf)
+    dense_bytes = 38 * X * Y * Z
+    return {"bricks": sp.n_bricks, "table_entries": sp.table.numel(), "minimal_bricks": need, "allocated_over_minimal": round(sp.n_bricks / need, 3),
+            "fraction_of_grid_allocated": round(sp.n_bricks / sp.table.numel(), 4), "pool_and_table_GB": round(sp.nbytes / 1e9, 3),
+            "workspace_GB": round(ws / 1e9, 3), "total_over_dense_38B_per_voxel": round((sp.nbytes + ws) / dense_bytes, 4),
+            "allocate_ms": round(1e3 * t_alloc, 2), "integrate_B16_ms": round(1e3 * (t_both - t_alloc), 2),
+            "allocate_plus_integrate_ms": round(1e3 * t_both, 2), "extract_mesh_ms_incl_allocation_and_host_copy": round(1e3 * t_ext, 2),
+            "vertices": len(mesh.vertices), "faces": len(mesh.faces), "same_counts_as_dense": len(mesh.vertices) == nv and len(mesh.faces) == nf}
+
+
+def bench_voxel(voxel, depth, rgb, w2c, K, reps, sparse=False):
     pad = 8 * voxel
     vol = TSDFVolume.from_bounds((0, 0, 0), ROOM, voxel, pad=pad, max_voxels=2 ** 31 - 1, device=DEV)
     X, Y, Z = vol.dims
@@ -155,7 +210,11 @@ def bench_voxel(voxel, depth, rgb, w2c, K, reps):
     out["extract"] = {"vertices": nv, "faces": nf, "workspace_GB": round(nbytes / 1e9, 2), "count_and_scans_ms": round(1e3 * t_count, 2),
                       "emit_ms": round(1e3 * t_emit, 2), "extract_mesh_ms_incl_allocation_and_host_copy": round(1e3 * t_all, 2),
                       "count_pass_GBps_lower_bound": round(N * 10 / t_count / 1e9, 1)}
-    del vol, ws, verts, cols, faces
+    del ws, verts, cols, faces
+    if sparse:
+        torch.cuda.empty_cache()
+        out["sparse"] = bench_sparse(vol, nv, nf, depth, rgb, w2c, K, reps)
+    del vol
     torch.cuda.empty_cache()
     return out
 
@@ -166,6 +225,7 @@ def main():
     ap.add_argument("--views", type=int, default=300)
     ap.add_argument("--size", type=int, nargs=2, default=[384, 512])
     ap.add_argument("--reps", type=int, default=2)
+    ap.add_argument("--sparse", action="store_true", help="also the sparse brick volume on the same views")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -180,7 +240,7 @@ def main():
     res = {"scene": f"six-walled room {ROOM[0]} x {ROOM[1]} x {ROOM[2]} m, {args.views} views at {W}x{H}, f = {f:g}, trunc = 8 voxels",
            "device": torch.cuda.get_device_name(0), "results": []}
     for v in args.voxel:
-        r = bench_voxel(v, depth, rgb, w2c, K, args.reps)
+        r = bench_voxel(v, depth, rgb, w2c, K, args.reps, args.sparse)
         res["results"].append(r)
         print(json.dumps(r), flush=True)
     if args.json:
