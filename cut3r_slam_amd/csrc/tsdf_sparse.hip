@@ -22,20 +22,14 @@
 // outside the view's frustum (the planes z = 0, u = -0.5, u = W - 0.5, v = -0.5, v = H - 0.5, z = depth_max + trunc, moved out by a
 // margin): it could not have updated any of its voxels.
 //
-// mesh: count / scan / emit as in tsdf.hip over the pool voxels, neighbours found through the table.  Vertices in (pool voxel, direction
-// mask) order, faces in (pool cell, tetrahedron, triangle) order.
+// mesh: the count / scan / emit of tsdf_voxel.h (the code the dense grid runs) over its BrickStore: the pool voxels, neighbours inside the
+// brick by arithmetic and across bricks through the table.  Vertices in (pool voxel, direction mask) order, faces in (pool cell,
+// tetrahedron, triangle) order.
 #include "tsdf_voxel.h"
-#include "../../include/cut3r_hip.h"
 
-#define BRICK 8
-#define BRICK_VOXELS 512
 #define MARK_SEGMENTS 2
 
 namespace {
-
-struct SparseGrid {
-    int X, Y, Z, BX, BY, BZ;
-};
 
 SparseGrid make_grid(int X, int Y, int Z) { return {X, Y, Z, (X + BRICK - 1) / BRICK, (Y + BRICK - 1) / BRICK, (Z + BRICK - 1) / BRICK}; }
 
@@ -135,13 +129,10 @@ __global__ __launch_bounds__(BRICK_VOXELS) void tsdf_sparse_integrate_kernel(
     float ox, float oy, float oz, float voxel, const float* __restrict__ depth, const unsigned char* __restrict__ rgb,
     const float* __restrict__ conf, int B, int H, int W, int ch, int cw, int ds, float conf_min, const float* __restrict__ w2c,
     const float* __restrict__ K, float trunc, float depth_max) {
-    __shared__ float sv[TSDF_MAX_VIEWS * 16];          // per view: w2c rows [12], fx fy cx cy
+    __shared__ float sv[TSDF_MAX_VIEWS * 16];
     __shared__ unsigned sviews;
     const int tid = threadIdx.x;
-    if (tid < B * 16) {
-        const int b = tid >> 4, c = tid & 15;
-        sv[tid] = c < 12 ? w2c[b * 12 + c] : K[b * 4 + (c - 12)];
-    }
+    stage_views(sv, w2c, K, B);
     if (tid == 0) sviews = 0u;
     __syncthreads();
     const int t = bricks[blockIdx.x];
@@ -178,167 +169,8 @@ __global__ __launch_bounds__(BRICK_VOXELS) void tsdf_sparse_integrate_kernel(
                           W, ch, cw, ds, conf_min, trunc, depth_max);
 }
 
-// ------------------------------------------------------------------------------------------------------------------------------ mesh
-// pool index of the in-grid voxel (i, j, k), or -1 when its brick is not allocated
-DEVINL long long pool_index(const int* __restrict__ table, const SparseGrid& g, int i, int j, int k) {
-    const int s = table[((long long)(k >> 3) * g.BY + (j >> 3)) * g.BX + (i >> 3)];
-    return s < 0 ? -1 : (long long)s * BRICK_VOXELS + (((k & 7) << 6) | ((j & 7) << 3) | (i & 7));
-}
-
-// the same for the neighbour at (di, dj, dk) in {-1,0,1}^3 of pool voxel n at (i, j, k): inside the brick without the table
-DEVINL long long pool_neighbour(const int* __restrict__ table, const SparseGrid& g, long long n, int i, int j, int k, int di, int dj, int dk) {
-    const unsigned li = (unsigned)((i & 7) + di), lj = (unsigned)((j & 7) + dj), lk = (unsigned)((k & 7) + dk);
-    if (li < 8u && lj < 8u && lk < 8u) return n + di + dj * 8 + dk * 64;
-    return pool_index(table, g, i + di, j + dj, k + dk);
-}
-
-DEVINL void pool_coords(const int* __restrict__ bricks, const SparseGrid& g, long long n, int& i, int& j, int& k) {
-    const int t = bricks[n >> 9], v = (int)(n & 511);
-    const int bx = t % g.BX, r = t / g.BX, by = r % g.BY, bz = r / g.BY;
-    i = bx * BRICK + (v & 7);
-    j = by * BRICK + ((v >> 3) & 7);
-    k = bz * BRICK + (v >> 6);
-}
-
-// code[n] as in tsdf.hip.  A voxel outside the virtual grid reads as in the dense rule (same sign as n, weight not ok); an in-grid voxel of
-// a brick that is not allocated reads as the initial state tsdf = 1, weight = 0.
-__global__ __launch_bounds__(256) void tsdf_sparse_count_kernel(const float* __restrict__ tsdf, const float* __restrict__ weight,
-                                                                const int* __restrict__ table, const int* __restrict__ bricks, long long NP,
-                                                                SparseGrid g, float wth, unsigned short* __restrict__ code) {
-    for (long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x; n < NP; n += (long long)gridDim.x * blockDim.x) {
-        int i, j, k;
-        pool_coords(bricks, g, n, i, j, k);
-        if (i >= g.X || j >= g.Y || k >= g.Z) {
-            code[n] = 0;
-            continue;
-        }
-        const bool in0 = tsdf[n] < 0.f;
-        unsigned inside = in0 ? 1u : 0u;
-        bool mixed = false;
-        for (int e = 1; e < 8; ++e) {
-            const int di = e & 1, dj = (e >> 1) & 1, dk = (e >> 2) & 1;
-            bool s = in0;
-            if (i + di < g.X && j + dj < g.Y && k + dk < g.Z) {
-                const long long u = pool_neighbour(table, g, n, i, j, k, di, dj, dk);
-                s = (u < 0 ? 1.f : tsdf[u]) < 0.f;
-            }
-            inside |= (s ? 1u : 0u) << e;
-            mixed |= s != in0;
-        }
-        if (!mixed) {
-            code[n] = 0;
-            continue;
-        }
-        unsigned ok = 0;
-        for (int q = 0; q < 27; ++q) {
-            const int dx = q % 3 - 1, dy = (q / 3) % 3 - 1, dz = q / 9 - 1;
-            const int a = i + dx, b = j + dy, c = k + dz;
-            if (a < 0 || b < 0 || c < 0 || a >= g.X || b >= g.Y || c >= g.Z) continue;
-            const long long u = pool_neighbour(table, g, n, i, j, k, dx, dy, dz);
-            if ((u < 0 ? 0.f : weight[u]) >= wth) ok |= 1u << q;
-        }
-        code[n] = mesh_code(inside, valid_cells(ok));
-    }
-}
-
-__global__ void tsdf_sparse_totals_kernel(const unsigned short* __restrict__ code, const long long* __restrict__ vofs,
-                                          const long long* __restrict__ fofs, long long NP, long long* __restrict__ totals) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        const unsigned c = code[NP - 1];
-        totals[0] = vofs[NP - 1] + __builtin_popcount(c & 0x7fu);
-        totals[1] = fofs[NP - 1] + (c >> 8);
-    }
-}
-
-// A vertex-carrying edge has a negative end, so both ends are stored whenever the allocation covers the negative voxels' neighbourhoods;
-// for any other pool contents the missing end reads as tsdf = 1, colour 0, and a face corner whose owner is missing gets index 0.
-__global__ __launch_bounds__(256) void tsdf_sparse_emit_kernel(const float* __restrict__ tsdf, const float* __restrict__ color,
-                                                               const int* __restrict__ table, const int* __restrict__ bricks, long long NP,
-                                                               SparseGrid g, float ox, float oy, float oz, float voxel,
-                                                               const unsigned short* __restrict__ code, const long long* __restrict__ vofs,
-                                                               const long long* __restrict__ fofs, float* __restrict__ verts,
-                                                               unsigned char* __restrict__ vcol, int* __restrict__ faces, long long nv,
-                                                               long long nf) {
-    for (long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x; n < NP; n += (long long)gridDim.x * blockDim.x) {
-        const unsigned cd = code[n];
-        if (cd == 0) continue;
-        int ii, jj, kk;
-        pool_coords(bricks, g, n, ii, jj, kk);
-        const long long i = ii, j = jj, k = kk;
-        const unsigned vm = cd & 0x7fu;
-        long long vi = vofs[n];
-        const float t0 = tsdf[n];
-        const float p0[3] = {ox + voxel * (float)i, oy + voxel * (float)j, oz + voxel * (float)k};
-        for (int m = 1; m < 8; ++m) {
-            if (!((vm >> (m - 1)) & 1u)) continue;
-            const long long u = pool_neighbour(table, g, n, ii, jj, kk, m & 1, (m >> 1) & 1, (m >> 2) & 1);
-            const float t1 = u < 0 ? 1.f : tsdf[u];
-            const float p1[3] = {ox + voxel * (float)(i + (m & 1)), oy + voxel * (float)(j + ((m >> 1) & 1)),
-                                 oz + voxel * (float)(k + ((m >> 2) & 1))};
-            if (vi < nv) {
-                float ca[3] = {0.f, 0.f, 0.f}, cb[3] = {0.f, 0.f, 0.f};
-                if (vcol) {
-                    for (int a = 0; a < 3; ++a) {
-                        ca[a] = color[a * NP + n];
-                        cb[a] = u < 0 ? 0.f : color[a * NP + u];
-                    }
-                }
-                mesh_vertex(t0, t1, p0, p1, ca, cb, verts + vi * 3, vcol ? vcol + vi * 3 : nullptr);
-            }
-            ++vi;
-        }
-        const unsigned ntri = cd >> 8;
-        if (ntri == 0) continue;
-        long long cn[8];                               // the cell's corners in the pool (a cell with triangles is valid: all inside the grid)
-        unsigned inside = 0;
-        for (int e = 0; e < 8; ++e) {
-            cn[e] = e == 0 ? n : pool_neighbour(table, g, n, ii, jj, kk, e & 1, (e >> 1) & 1, (e >> 2) & 1);
-            inside |= ((cn[e] < 0 ? 1.f : tsdf[cn[e]]) < 0.f ? 1u : 0u) << e;
-        }
-        long long fi = fofs[n];
-        for (int t = 0; t < 6; ++t) {
-            int cc[4];
-            unsigned cs = 0;
-            for (int q = 0; q < 4; ++q) {
-                cc[q] = chain_corner(t, q);
-                cs |= ((inside >> cc[q]) & 1u) << q;
-            }
-            for (int r = 0; r < kNTri[cs]; ++r) {
-                int id[3];
-                for (int q = 0; q < 3; ++q) {
-                    const int e = kTri[cs][r][q];
-                    const int lo = cc[kEdge[e][0]], m = lo ^ cc[kEdge[e][1]];
-                    long long w = -1;
-                    for (int c = 0; c < 8; ++c) w = c == lo ? cn[c] : w;            // no dynamic indexing of the register array
-                    id[q] = w < 0 ? 0 : (int)(vofs[w] + __builtin_popcount((unsigned)code[w] & ((1u << (m - 1)) - 1u)));
-                }
-                if (kParity[t] < 0) {
-                    const int tmp = id[1];
-                    id[1] = id[2];
-                    id[2] = tmp;
-                }
-                if (fi < nf)
-                    for (int q = 0; q < 3; ++q) faces[fi * 3 + q] = id[q];
-                ++fi;
-            }
-        }
-    }
-}
-
-struct MeshWorkspace {
-    unsigned short* code;
-    long long *vofs, *fofs;
-    void* tmp;
-};
-
-MeshWorkspace mesh_workspace(void* workspace, long long NP) {
-    char* ws = (char*)workspace;
-    MeshWorkspace m;
-    m.code = (unsigned short*)ws;
-    m.vofs = (long long*)(ws + align256(sizeof(unsigned short) * NP));
-    m.fofs = (long long*)((char*)m.vofs + align256(sizeof(long long) * NP));
-    m.tmp = (char*)m.fofs + align256(sizeof(long long) * NP);
-    return m;
+BrickStore make_store(const int* table, const int* bricks, int nb, int X, int Y, int Z) {
+    return {make_grid(X, Y, Z), table, bricks, (long long)nb * BRICK_VOXELS};
 }
 
 }  // namespace
@@ -375,10 +207,8 @@ extern "C" int cut3r_tsdf_sparse_integrate(float* tsdf, float* weight, float* co
                                            float oy, float oz, float voxel, const float* depth, const unsigned char* rgb, const float* conf,
                                            int B, int H, int W, int ch, int cw, int ds, float conf_min, const float* w2c, const float* K,
                                            float trunc, float depth_max, void* stream) {
-    if (!tsdf || !weight || !color || !bricks || !depth || !w2c || !K || !grid_ok(X, Y, Z) || !pool_ok(nb)) return CUT3R_ERR_ARG;
-    if (nb > table_entries(X, Y, Z)) return CUT3R_ERR_ARG;
-    if (B < 1 || B > TSDF_MAX_VIEWS || H <= 0 || W <= 0 || !(voxel > 0.f) || !(trunc > 0.f)) return CUT3R_ERR_ARG;
-    if (conf && (ch <= 0 || cw <= 0 || ds <= 0)) return CUT3R_ERR_ARG;
+    if (!tsdf || !weight || !color || !bricks || !grid_ok(X, Y, Z) || !pool_ok(nb) || nb > table_entries(X, Y, Z)) return CUT3R_ERR_ARG;
+    if (!views_ok(depth, conf, B, H, W, ch, cw, ds, w2c, K, voxel, trunc)) return CUT3R_ERR_ARG;
     hipLaunchKernelGGL(tsdf_sparse_integrate_kernel, dim3(nb), dim3(BRICK_VOXELS), 0, (hipStream_t)stream, tsdf, weight, color, bricks,
                        (long long)nb * BRICK_VOXELS, make_grid(X, Y, Z), ox, oy, oz, voxel, depth, rgb, conf, B, H, W, ch, cw, ds, conf_min, w2c,
                        K, trunc, depth_max);
@@ -386,9 +216,7 @@ extern "C" int cut3r_tsdf_sparse_integrate(float* tsdf, float* weight, float* co
 }
 
 extern "C" long long cut3r_tsdf_sparse_mesh_workspace_bytes(int nb) {
-    if (!pool_ok(nb)) return -1;
-    const long long NP = (long long)nb * BRICK_VOXELS;
-    return (long long)(align256(sizeof(unsigned short) * NP) + 2 * align256(sizeof(long long) * NP) + align256(scan_temp_bytes(NP)));
+    return pool_ok(nb) ? MeshWorkspace::bytes((long long)nb * BRICK_VOXELS) : -1;
 }
 
 extern "C" int cut3r_tsdf_sparse_mesh_count(const float* tsdf, const float* weight, const int* table, const int* bricks, int nb, int X, int Y,
@@ -396,32 +224,14 @@ extern "C" int cut3r_tsdf_sparse_mesh_count(const float* tsdf, const float* weig
                                             void* stream) {
     if (!tsdf || !weight || !table || !bricks || !workspace || !totals || !grid_ok(X, Y, Z) || !pool_ok(nb)) return CUT3R_ERR_ARG;
     if (nb > table_entries(X, Y, Z) || workspace_bytes < cut3r_tsdf_sparse_mesh_workspace_bytes(nb)) return CUT3R_ERR_ARG;
-    const long long NP = (long long)nb * BRICK_VOXELS;
-    hipStream_t s = (hipStream_t)stream;
-    const MeshWorkspace m = mesh_workspace(workspace, NP);
-    size_t tb = scan_temp_bytes(NP);
-    hipLaunchKernelGGL(tsdf_sparse_count_kernel, dim3(grid_for(NP)), dim3(256), 0, s, tsdf, weight, table, bricks, NP, make_grid(X, Y, Z),
-                       weight_threshold, m.code);
-    if (cut3r_check_launch() != CUT3R_OK) return CUT3R_ERR_LAUNCH;
-    rocprim::transform_iterator<const unsigned short*, VoxelCountOp, long long> vit(m.code, VoxelCountOp());
-    rocprim::transform_iterator<const unsigned short*, CellCountOp, long long> fit(m.code, CellCountOp());
-    if (hipcub::DeviceScan::ExclusiveSum(m.tmp, tb, vit, m.vofs, (int)NP, s) != hipSuccess) return CUT3R_ERR_LAUNCH;
-    tb = scan_temp_bytes(NP);
-    if (hipcub::DeviceScan::ExclusiveSum(m.tmp, tb, fit, m.fofs, (int)NP, s) != hipSuccess) return CUT3R_ERR_LAUNCH;
-    hipLaunchKernelGGL(tsdf_sparse_totals_kernel, dim3(1), dim3(64), 0, s, m.code, m.vofs, m.fofs, NP, totals);
-    return cut3r_check_launch();
+    return mesh_count(tsdf, weight, make_store(table, bricks, nb, X, Y, Z), weight_threshold, workspace, totals, (hipStream_t)stream);
 }
 
 extern "C" int cut3r_tsdf_sparse_mesh_emit(const float* tsdf, const float* color, const int* table, const int* bricks, int nb, int X, int Y,
                                            int Z, float ox, float oy, float oz, float voxel, const void* workspace, long long workspace_bytes,
                                            float* verts, unsigned char* colors, int* faces, long long nv, long long nf, void* stream) {
-    if (!tsdf || !color || !table || !bricks || !workspace || !grid_ok(X, Y, Z) || !pool_ok(nb) || !(voxel > 0.f)) return CUT3R_ERR_ARG;
-    if (nv < 0 || nf < 0 || nv >= (1LL << 31) || (nv > 0 && !verts) || (nf > 0 && !faces)) return CUT3R_ERR_ARG;
+    if (!tsdf || !color || !table || !bricks || !workspace || !grid_ok(X, Y, Z) || !pool_ok(nb)) return CUT3R_ERR_ARG;
     if (nb > table_entries(X, Y, Z) || workspace_bytes < cut3r_tsdf_sparse_mesh_workspace_bytes(nb)) return CUT3R_ERR_ARG;
-    if (nv == 0 && nf == 0) return CUT3R_OK;
-    const long long NP = (long long)nb * BRICK_VOXELS;
-    const MeshWorkspace m = mesh_workspace((void*)workspace, NP);
-    hipLaunchKernelGGL(tsdf_sparse_emit_kernel, dim3(grid_for(NP)), dim3(256), 0, (hipStream_t)stream, tsdf, color, table, bricks, NP,
-                       make_grid(X, Y, Z), ox, oy, oz, voxel, m.code, m.vofs, m.fofs, verts, colors, faces, nv, nf);
-    return cut3r_check_launch();
+    return mesh_emit(tsdf, color, make_store(table, bricks, nb, X, Y, Z), ox, oy, oz, voxel, workspace, verts, colors, faces, nv, nf,
+                     (hipStream_t)stream);
 }

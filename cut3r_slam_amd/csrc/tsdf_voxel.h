@@ -1,11 +1,16 @@
 // What the dense (tsdf.hip) and the sparse brick (tsdf_sparse.hip) TSDF volumes share, so that they agree bit for bit by construction:
-// the per-voxel fusion of a batch of views, the marching-tetrahedra tables and the packing of the per-voxel mesh counts.  Both files are
-// compiled with -ffp-contract=off; every formula here is written in one fixed order (tests/tsdf_oracle.py restates it in numpy).
+// the per-voxel fusion of a batch of views, and the whole mesh extraction -- the marching-tetrahedra tables, the count and emit kernels,
+// the workspace layout and the host drivers -- written once over a "voxel store" (DenseStore, BrickStore below) that says where voxel
+// (i, j, k) and its neighbours are kept.  Both files are compiled with -ffp-contract=off; every formula here is written in one fixed order
+// (tests/tsdf_oracle.py restates it in numpy).
 #pragma once
 #include <hipcub/hipcub.hpp>
 #include "common.h"
+#include "../../include/cut3r_hip.h"
 
 #define TSDF_MAX_VIEWS 16
+#define BRICK 8
+#define BRICK_VOXELS 512
 
 namespace {
 
@@ -72,6 +77,21 @@ DEVINL unsigned short mesh_code(unsigned inside, unsigned cellv) {
         }
     }
     return (unsigned short)(vm | (nf << 8));
+}
+
+// the views of an integrate launch, staged into LDS by the whole workgroup (the caller synchronises): per view w2c rows [12], fx fy cx cy
+DEVINL void stage_views(float* sv, const float* __restrict__ w2c, const float* __restrict__ K, int B) {
+    for (int t = threadIdx.x; t < B * 16; t += blockDim.x) {
+        const int b = t >> 4, c = t & 15;
+        sv[t] = c < 12 ? w2c[b * 12 + c] : K[b * 4 + (c - 12)];
+    }
+}
+
+// the view arguments of the two integrate entry points
+inline bool views_ok(const float* depth, const float* conf, int B, int H, int W, int ch, int cw, int ds, const float* w2c, const float* K,
+                     float voxel, float trunc) {
+    if (!depth || !w2c || !K || B < 1 || B > TSDF_MAX_VIEWS || H <= 0 || W <= 0 || !(voxel > 0.f) || !(trunc > 0.f)) return false;
+    return !conf || (ch > 0 && cw > 0 && ds > 0);
 }
 
 // The fusion of the B <= 16 views of a batch into the voxel at (px, py, pz), whose state lives at index n of the planes tsdf [N],
@@ -176,6 +196,250 @@ inline size_t scan_temp_bytes(long long N) {          // the larger of the two c
 inline int grid_for(long long N) {
     const long long g = (N + 255) / 256;
     return (int)(g < 256 * 64 ? g : 256 * 64);       // grid-stride beyond 64 blocks per CU
+}
+
+// ---------------------------------------------------------------------------------------------------------------------- voxel stores
+// A store keeps N voxels of the grid X x Y x Z and is passed to the mesh kernels by value:
+//   coords(n, i, j, k)                  the grid position of stored voxel n; false when that slot holds no voxel of the grid
+//   neighbour(n, i, j, k, di, dj, dk)   the stored index of the IN-GRID voxel (i + di, j + dj, k + dk), d in {-1,0,1}^3, or -1 when it is
+//                                       not stored
+//   kMayMiss                            whether neighbour() can return -1: where it cannot, the handling of -1 folds away at compile time
+
+// the dense grid: voxel n = (k*Y + j)*X + i (x fastest), every voxel stored
+struct DenseStore {
+    static constexpr bool kMayMiss = false;
+    int X, Y, Z;
+    long long XY, N;                                   // X*Y, X*Y*Z < 2^31
+
+    DEVINL bool coords(long long n, int& i, int& j, int& k) const {
+        const unsigned n32 = (unsigned)n, r = n32 / (unsigned)X, kk = r / (unsigned)Y;      // N < 2^31: 32-bit division (a 64-bit one costs ~3x)
+        i = (int)(n32 - r * (unsigned)X);
+        j = (int)(r - kk * (unsigned)Y);
+        k = (int)kk;
+        return true;
+    }
+    DEVINL long long neighbour(long long n, int, int, int, int di, int dj, int dk) const {
+        return n + di + dj * (long long)X + dk * XY;
+    }
+};
+
+struct SparseGrid {
+    int X, Y, Z, BX, BY, BZ;
+};
+
+// the brick pool: voxel n = slot * 512 + (lk*8 + lj)*8 + li of brick bricks[slot] = (bz*BY + by)*BX + bx; table[brick] = slot or -1.  The last
+// brick of an axis may reach past the grid: those slots hold no voxel.
+struct BrickStore : SparseGrid {
+    static constexpr bool kMayMiss = true;
+    const int *table, *bricks;
+    long long N;
+
+    DEVINL bool coords(long long n, int& i, int& j, int& k) const {
+        const int t = bricks[n >> 9], v = (int)(n & 511);
+        const int bx = t % BX, r = t / BX, by = r % BY, bz = r / BY;
+        i = bx * BRICK + (v & 7);
+        j = by * BRICK + ((v >> 3) & 7);
+        k = bz * BRICK + (v >> 6);
+        return i < X && j < Y && k < Z;
+    }
+    DEVINL long long index(int i, int j, int k) const {
+        const int s = table[((long long)(k >> 3) * BY + (j >> 3)) * BX + (i >> 3)];
+        return s < 0 ? -1 : (long long)s * BRICK_VOXELS + (((k & 7) << 6) | ((j & 7) << 3) | (i & 7));
+    }
+    DEVINL long long neighbour(long long n, int i, int j, int k, int di, int dj, int dk) const {       // inside the brick without the table
+        const unsigned li = (unsigned)((i & 7) + di), lj = (unsigned)((j & 7) + dj), lk = (unsigned)((k & 7) + dk);
+        if (li < 8u && lj < 8u && lk < 8u) return n + di + dj * 8 + dk * 64;
+        return index(i + di, j + dj, k + dk);
+    }
+};
+
+// whether neighbour() found no stored voxel; it then reads as the initial state tsdf = 1, weight = 0, colour 0
+template <class Store>
+DEVINL bool missing(long long u) {
+    return Store::kMayMiss && u < 0;
+}
+
+// ----------------------------------------------------------------------------------------------------------------------------- count
+// code[n] = (vertex mask of voxel n: bit m-1 = the edge (n, m) carries a vertex) | (triangles of the cell with corner 0 at n) << 8.
+// An edge carries a vertex when its ends differ in sign and some valid cell (all 8 corners weight >= threshold) contains it: the
+// cells n - d, d in {0,1}^3 with d & m == 0.  Every sign-changing edge of a tetrahedron of a valid cell is used by that tetrahedron's
+// triangles, so these are exactly the vertices some face references.
+template <class Store>
+__global__ __launch_bounds__(256) void tsdf_mesh_count_kernel(const float* __restrict__ tsdf, const float* __restrict__ weight, Store st,
+                                                              float wth, unsigned short* __restrict__ code) {
+    for (long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x; n < st.N; n += (long long)gridDim.x * blockDim.x) {
+        int i, j, k;
+        if (!st.coords(n, i, j, k)) {
+            code[n] = 0;
+            continue;
+        }
+        // signs of the 8 voxels n + e, e in {0,1}^3 (outside the grid: same sign as n, i.e. no crossing)
+        const bool in0 = tsdf[n] < 0.f;
+        unsigned inside = in0 ? 1u : 0u;
+        bool mixed = false;
+        for (int e = 1; e < 8; ++e) {
+            const int di = e & 1, dj = (e >> 1) & 1, dk = (e >> 2) & 1;
+            bool s = in0;
+            if (i + di < st.X && j + dj < st.Y && k + dk < st.Z) {
+                const long long u = st.neighbour(n, i, j, k, di, dj, dk);
+                s = (missing<Store>(u) ? 1.f : tsdf[u]) < 0.f;
+            }
+            inside |= (s ? 1u : 0u) << e;
+            mixed |= s != in0;
+        }
+        if (!mixed) {
+            code[n] = 0;
+            continue;
+        }
+        // weight >= threshold over the 3x3x3 neighbourhood (bit (dz+1)*9 + (dy+1)*3 + (dx+1)); outside the grid = not ok
+        unsigned ok = 0;
+        for (int q = 0; q < 27; ++q) {
+            const int dx = q % 3 - 1, dy = (q / 3) % 3 - 1, dz = q / 9 - 1;
+            const int a = i + dx, b = j + dy, c = k + dz;
+            if (a < 0 || b < 0 || c < 0 || a >= st.X || b >= st.Y || c >= st.Z) continue;
+            const long long u = st.neighbour(n, i, j, k, dx, dy, dz);
+            if ((missing<Store>(u) ? 0.f : weight[u]) >= wth) ok |= 1u << q;
+        }
+        code[n] = mesh_code(inside, valid_cells(ok));
+    }
+}
+
+__global__ void tsdf_mesh_totals_kernel(const unsigned short* __restrict__ code, const long long* __restrict__ vofs,
+                                        const long long* __restrict__ fofs, long long N, long long* __restrict__ totals) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        const unsigned c = code[N - 1];
+        totals[0] = vofs[N - 1] + __builtin_popcount(c & 0x7fu);
+        totals[1] = fofs[N - 1] + (c >> 8);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------ emit
+// vertex (n, m): s = t0 / (t0 - t1), p = p0 + s (p1 - p0) per axis, colour c0 + s (c1 - c0) rounded floor(c + 0.5); written at vofs[n] +
+// rank of m among the voxel's masks.  Faces of cell n at fofs[n], ordered by (tetrahedron, triangle); odd tetrahedra swap the winding.
+// In a store that may miss voxels a vertex-carrying edge has a negative end, so both ends are stored whenever the allocation covers the
+// negative voxels' neighbourhoods; for any other contents the missing end reads as tsdf = 1, colour 0, and a face corner whose owner is
+// missing gets index 0.
+template <class Store>
+__global__ __launch_bounds__(256) void tsdf_mesh_emit_kernel(const float* __restrict__ tsdf, const float* __restrict__ color, Store st,
+                                                             float ox, float oy, float oz, float voxel,
+                                                             const unsigned short* __restrict__ code, const long long* __restrict__ vofs,
+                                                             const long long* __restrict__ fofs, float* __restrict__ verts,
+                                                             unsigned char* __restrict__ vcol, int* __restrict__ faces, long long nv,
+                                                             long long nf) {
+    for (long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x; n < st.N; n += (long long)gridDim.x * blockDim.x) {
+        const unsigned cd = code[n];
+        if (cd == 0) continue;
+        int i, j, k;
+        st.coords(n, i, j, k);
+        const unsigned vm = cd & 0x7fu;
+        long long vi = vofs[n];
+        const float t0 = tsdf[n];
+        const float p0[3] = {ox + voxel * (float)i, oy + voxel * (float)j, oz + voxel * (float)k};
+        for (int m = 1; m < 8; ++m) {
+            if (!((vm >> (m - 1)) & 1u)) continue;
+            const long long u = st.neighbour(n, i, j, k, m & 1, (m >> 1) & 1, (m >> 2) & 1);
+            const float t1 = missing<Store>(u) ? 1.f : tsdf[u];
+            const float p1[3] = {ox + voxel * (float)(i + (m & 1)), oy + voxel * (float)(j + ((m >> 1) & 1)),
+                                 oz + voxel * (float)(k + ((m >> 2) & 1))};
+            if (vi < nv) {
+                float ca[3] = {0.f, 0.f, 0.f}, cb[3] = {0.f, 0.f, 0.f};
+                if (vcol) {
+                    for (int a = 0; a < 3; ++a) {
+                        ca[a] = color[a * st.N + n];
+                        cb[a] = missing<Store>(u) ? 0.f : color[a * st.N + u];
+                    }
+                }
+                mesh_vertex(t0, t1, p0, p1, ca, cb, verts + vi * 3, vcol ? vcol + vi * 3 : nullptr);
+            }
+            ++vi;
+        }
+        const unsigned ntri = cd >> 8;
+        if (ntri == 0) continue;
+        long long cn[8];                               // where the cell's corners are stored (a cell with triangles is valid: all inside the grid)
+        unsigned inside = 0;
+        for (int e = 0; e < 8; ++e) {
+            cn[e] = e == 0 ? n : st.neighbour(n, i, j, k, e & 1, (e >> 1) & 1, (e >> 2) & 1);
+            inside |= ((missing<Store>(cn[e]) ? 1.f : tsdf[cn[e]]) < 0.f ? 1u : 0u) << e;
+        }
+        long long fi = fofs[n];
+        for (int t = 0; t < 6; ++t) {
+            int cc[4];
+            unsigned cs = 0;
+            for (int q = 0; q < 4; ++q) {
+                cc[q] = chain_corner(t, q);
+                cs |= ((inside >> cc[q]) & 1u) << q;
+            }
+            for (int r = 0; r < kNTri[cs]; ++r) {
+                int id[3];
+                for (int q = 0; q < 3; ++q) {
+                    const int e = kTri[cs][r][q];
+                    const int lo = cc[kEdge[e][0]], m = lo ^ cc[kEdge[e][1]];
+                    // the vertex's owner, corner lo: by arithmetic where every voxel is stored, else picked from cn without dynamic
+                    // indexing of the register array
+                    long long w = Store::kMayMiss ? -1 : st.neighbour(n, i, j, k, lo & 1, (lo >> 1) & 1, (lo >> 2) & 1);
+                    if (Store::kMayMiss)
+                        for (int c = 0; c < 8; ++c) w = c == lo ? cn[c] : w;
+                    id[q] = missing<Store>(w) ? 0 : (int)(vofs[w] + __builtin_popcount((unsigned)code[w] & ((1u << (m - 1)) - 1u)));
+                }
+                if (kParity[t] < 0) {
+                    const int tmp = id[1];
+                    id[1] = id[2];
+                    id[2] = tmp;
+                }
+                if (fi < nf)
+                    for (int q = 0; q < 3; ++q) faces[fi * 3 + q] = id[q];
+                ++fi;
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------ host
+// the mesh workspace of N stored voxels: code | vofs | fofs | scan scratch, each part 256-byte aligned
+struct MeshWorkspace {
+    unsigned short* code;
+    long long *vofs, *fofs;
+    void* tmp;
+
+    // const in: mesh_emit only reads the parts (every workspace parameter of the emit kernel is const); only mesh_count writes them
+    MeshWorkspace(const void* workspace, long long N) {
+        char* ws = (char*)workspace;
+        code = (unsigned short*)ws;
+        vofs = (long long*)(ws + align256(sizeof(unsigned short) * N));
+        fofs = (long long*)((char*)vofs + align256(sizeof(long long) * N));
+        tmp = (char*)fofs + align256(sizeof(long long) * N);
+    }
+    static long long bytes(long long N) {
+        return (long long)(align256(sizeof(unsigned short) * N) + 2 * align256(sizeof(long long) * N) + align256(scan_temp_bytes(N)));
+    }
+};
+
+// count -> two exclusive scans -> totals [2] = (vertices, faces); the workspace holds MeshWorkspace::bytes(st.N)
+template <class Store>
+int mesh_count(const float* tsdf, const float* weight, const Store& st, float wth, void* workspace, long long* totals, hipStream_t s) {
+    const MeshWorkspace m(workspace, st.N);
+    size_t tb = scan_temp_bytes(st.N);
+    hipLaunchKernelGGL(tsdf_mesh_count_kernel<Store>, dim3(grid_for(st.N)), dim3(256), 0, s, tsdf, weight, st, wth, m.code);
+    if (cut3r_check_launch() != CUT3R_OK) return CUT3R_ERR_LAUNCH;
+    rocprim::transform_iterator<const unsigned short*, VoxelCountOp, long long> vit(m.code, VoxelCountOp());
+    rocprim::transform_iterator<const unsigned short*, CellCountOp, long long> fit(m.code, CellCountOp());
+    if (hipcub::DeviceScan::ExclusiveSum(m.tmp, tb, vit, m.vofs, (int)st.N, s) != hipSuccess) return CUT3R_ERR_LAUNCH;
+    tb = scan_temp_bytes(st.N);
+    if (hipcub::DeviceScan::ExclusiveSum(m.tmp, tb, fit, m.fofs, (int)st.N, s) != hipSuccess) return CUT3R_ERR_LAUNCH;
+    hipLaunchKernelGGL(tsdf_mesh_totals_kernel, dim3(1), dim3(64), 0, s, m.code, m.vofs, m.fofs, st.N, totals);
+    return cut3r_check_launch();
+}
+
+// emit into verts [nv,3], colors [nv,3] (or null), faces [nf,3] from the workspace mesh_count filled
+template <class Store>
+int mesh_emit(const float* tsdf, const float* color, const Store& st, float ox, float oy, float oz, float voxel, const void* workspace,
+              float* verts, unsigned char* colors, int* faces, long long nv, long long nf, hipStream_t s) {
+    if (!(voxel > 0.f) || nv < 0 || nf < 0 || nv >= (1LL << 31) || (nv > 0 && !verts) || (nf > 0 && !faces)) return CUT3R_ERR_ARG;
+    if (nv == 0 && nf == 0) return CUT3R_OK;
+    const MeshWorkspace m(workspace, st.N);
+    hipLaunchKernelGGL(tsdf_mesh_emit_kernel<Store>, dim3(grid_for(st.N)), dim3(256), 0, s, tsdf, color, st, ox, oy, oz, voxel, m.code,
+                       m.vofs, m.fofs, verts, colors, faces, nv, nf);
+    return cut3r_check_launch();
 }
 
 }  // namespace

@@ -723,16 +723,18 @@ def _tsdf_planes(tsdf, weight, color):
     return X, Y, Z
 
 
-def tsdf_integrate(tsdf, weight, color, origin, voxel, depth, w2c, K, trunc, depth_max, rgb=None, conf=None, conf_ds=1, conf_min=0.0):
-    """in place: fuse B <= 16 views (VoxelBlockGrid.integrate, tsdf_integrate.py:31-62) in one launch.  depth [B,H,W] fp32 metres, w2c
-    [B,12] / K [B,4] fp32 on the GPU, rgb u8 [B,3,H,W] or None, conf fp32 [B,h,w] at stride conf_ds with conf_min, or None."""
-    X, Y, Z = _tsdf_planes(tsdf, weight, color)
-    _cuda(depth, w2c, K, rgb, conf)
+def _tsdf_views(what, depth, pose, pose_name, K, voxel, trunc, max_views=None, rgb=None, conf=None, conf_ds=1):
+    """the views of a TSDF launch: depth [B,H,W], pose (w2c or c2w rows) [B,12], K [B,4] fp32, rgb u8 [B,3,H,W] or None, conf fp32 [B,h,w] or
+    None, all contiguous on the GPU -> (B, H, W, ch, cw).  max_views: the limit on B of one launch; None: any B with B*H*W < 2^31."""
+    _cuda(depth, pose, K, rgb, conf)
     _req(depth.dim() == 3 and depth.dtype == F32 and depth.is_contiguous(), "depth: contiguous fp32 [B,H,W]")
     B, H, W = depth.shape
-    _req(1 <= B <= TSDF_MAX_VIEWS, f"tsdf_integrate: 1..{TSDF_MAX_VIEWS} views per launch")
-    _req(H > 0 and W > 0, "depth: empty image")
-    _req(w2c.shape == (B, 12) and w2c.dtype == F32 and w2c.is_contiguous(), "w2c: contiguous fp32 [B,12]")
+    if max_views is None:
+        _req(B >= 1 and H > 0 and W > 0 and B * H * W < 2 ** 31, "depth: 1 .. 2^31 - 1 pixels")
+    else:
+        _req(1 <= B <= max_views, f"{what}: 1..{max_views} views per launch")
+        _req(H > 0 and W > 0, "depth: empty image")
+    _req(pose.shape == (B, 12) and pose.dtype == F32 and pose.is_contiguous(), f"{pose_name}: contiguous fp32 [B,12]")
     _req(K.shape == (B, 4) and K.dtype == F32 and K.is_contiguous(), "K: contiguous fp32 [B,4]")
     _req(float(voxel) > 0 and float(trunc) > 0, "voxel size and truncation must be > 0")
     if rgb is not None:
@@ -742,6 +744,32 @@ def tsdf_integrate(tsdf, weight, color, origin, voxel, depth, w2c, K, trunc, dep
         _req(conf.dim() == 3 and conf.shape[0] == B and conf.dtype == F32 and conf.is_contiguous(), "conf: contiguous fp32 [B,h,w]")
         ch, cw = conf.shape[1:]
         _req(int(conf_ds) >= 1 and ch > 0 and cw > 0, "conf: stride >= 1, non-empty")
+    return B, H, W, ch, cw
+
+
+def _tsdf_mesh(dev, voxel, workspace_bytes, count, emit, what, store):
+    """the driver of the two extract_mesh: workspace, count + scans, one read-back of the two totals, allocate, emit.  count(ws, nbytes,
+    totals) and emit(ws, nbytes, verts, cols, faces, nv, nf) return the status of the C entry points named cut3r_{what}_mesh_*; store names what is too large when no workspace fits."""
+    _req(float(voxel) > 0, "voxel size must be > 0")
+    nbytes = workspace_bytes()
+    _req(nbytes > 0, f"{store} too large")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    totals = torch.empty(2, dtype=torch.int64, device=dev)
+    check(count(_p(ws), nbytes, _p(totals)), f"cut3r_{what}_mesh_count")
+    nv, nf = (int(v) for v in totals.cpu())
+    _req(nv < 2 ** 31, f"mesh of {nv} vertices: int32 face indices cannot address it")
+    verts = torch.empty(nv, 3, dtype=F32, device=dev)
+    cols = torch.empty(nv, 3, dtype=torch.uint8, device=dev)
+    faces = torch.empty(nf, 3, dtype=torch.int32, device=dev)
+    check(emit(_p(ws), nbytes, _p(verts), _p(cols), _p(faces), nv, nf), f"cut3r_{what}_mesh_emit")
+    return verts, cols, faces
+
+
+def tsdf_integrate(tsdf, weight, color, origin, voxel, depth, w2c, K, trunc, depth_max, rgb=None, conf=None, conf_ds=1, conf_min=0.0):
+    """in place: fuse B <= 16 views (VoxelBlockGrid.integrate, tsdf_integrate.py:31-62) in one launch.  depth [B,H,W] fp32 metres, w2c
+    [B,12] / K [B,4] fp32 on the GPU, rgb u8 [B,3,H,W] or None, conf fp32 [B,h,w] at stride conf_ds with conf_min, or None."""
+    X, Y, Z = _tsdf_planes(tsdf, weight, color)
+    B, H, W, ch, cw = _tsdf_views("tsdf_integrate", depth, w2c, "w2c", K, voxel, trunc, TSDF_MAX_VIEWS, rgb, conf, conf_ds)
     lib = _lib.load()
     check(lib.cut3r_tsdf_integrate(_p(tsdf), _p(weight), _p(color), X, Y, Z, float(origin[0]), float(origin[1]), float(origin[2]),
                                    float(voxel), _p(depth), _p(rgb), _p(conf), B, H, W, ch, cw, int(conf_ds), float(conf_min), _p(w2c),
@@ -752,23 +780,13 @@ def tsdf_extract_mesh(tsdf, weight, color, origin, voxel, weight_threshold=1.0):
     """marching tetrahedra over the fused planes (VoxelBlockGrid.extract_triangle_mesh, tsdf_integrate.py:83-88): count, scan, one
     read-back of the two totals, emit -> (vertices fp32 [V,3], colors u8 [V,3], faces int32 [F,3]) on the GPU"""
     X, Y, Z = _tsdf_planes(tsdf, weight, color)
-    _req(float(voxel) > 0, "voxel size must be > 0")
     lib = _lib.load()
-    dev = tsdf.device
-    nbytes = lib.cut3r_tsdf_mesh_workspace_bytes(X, Y, Z)
-    _req(nbytes > 0, "TSDF grid too large")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    totals = torch.empty(2, dtype=torch.int64, device=dev)
-    check(lib.cut3r_tsdf_mesh_count(_p(tsdf), _p(weight), X, Y, Z, float(weight_threshold), _p(ws), nbytes, _p(totals), _stream()),
-          "cut3r_tsdf_mesh_count")
-    nv, nf = (int(v) for v in totals.cpu())
-    _req(nv < 2 ** 31, f"mesh of {nv} vertices: int32 face indices cannot address it")
-    verts = torch.empty(nv, 3, dtype=F32, device=dev)
-    cols = torch.empty(nv, 3, dtype=torch.uint8, device=dev)
-    faces = torch.empty(nf, 3, dtype=torch.int32, device=dev)
-    check(lib.cut3r_tsdf_mesh_emit(_p(tsdf), _p(color), X, Y, Z, float(origin[0]), float(origin[1]), float(origin[2]), float(voxel), _p(ws),
-                                   nbytes, _p(verts), _p(cols), _p(faces), nv, nf, _stream()), "cut3r_tsdf_mesh_emit")
-    return verts, cols, faces
+    o = [float(v) for v in origin]
+    return _tsdf_mesh(
+        tsdf.device, voxel, lambda: lib.cut3r_tsdf_mesh_workspace_bytes(X, Y, Z),
+        lambda ws, nbytes, totals: lib.cut3r_tsdf_mesh_count(_p(tsdf), _p(weight), X, Y, Z, float(weight_threshold), ws, nbytes, totals, _stream()),
+        lambda ws, nbytes, *out: lib.cut3r_tsdf_mesh_emit(_p(tsdf), _p(color), X, Y, Z, *o, float(voxel), ws, nbytes, *out, _stream()), "tsdf",
+        "TSDF grid")
 
 
 # ------------------------------------------------------------------------------------------------ sparse brick TSDF volume
@@ -813,13 +831,7 @@ def tsdf_sparse_mark(flags, dims, origin, voxel, depth, c2w, K, trunc, depth_max
     depth [B,H,W] fp32, c2w [B,12] camera->world rows (the inverse of the views' w2c), K [B,4], any B >= 1."""
     X, Y, Z, T = _tsdf_sparse_grid(dims)
     _tsdf_table(flags, "flags", torch.uint8, T)
-    _cuda(depth, c2w, K)
-    _req(depth.dim() == 3 and depth.dtype == F32 and depth.is_contiguous(), "depth: contiguous fp32 [B,H,W]")
-    B, H, W = depth.shape
-    _req(B >= 1 and H > 0 and W > 0 and B * H * W < 2 ** 31, "depth: 1 .. 2^31 - 1 pixels")
-    _req(c2w.shape == (B, 12) and c2w.dtype == F32 and c2w.is_contiguous(), "c2w: contiguous fp32 [B,12]")
-    _req(K.shape == (B, 4) and K.dtype == F32 and K.is_contiguous(), "K: contiguous fp32 [B,4]")
-    _req(float(voxel) > 0 and float(trunc) > 0, "voxel size and truncation must be > 0")
+    B, H, W, _, _ = _tsdf_views("tsdf_sparse_mark", depth, c2w, "c2w", K, voxel, trunc)
     lib = _lib.load()
     check(lib.cut3r_tsdf_sparse_mark(_p(flags), X, Y, Z, float(origin[0]), float(origin[1]), float(origin[2]), float(voxel), _p(depth), B, H, W,
                                      _p(c2w), _p(K), float(trunc), float(depth_max), _stream()), "cut3r_tsdf_sparse_mark")
@@ -846,21 +858,7 @@ def tsdf_sparse_integrate(tsdf, weight, color, bricks, dims, origin, voxel, dept
     tsdf_integrate with the pool (tsdf [nb,512], weight, color [3,nb,512]) and its brick list in place of the planes."""
     X, Y, Z, T = _tsdf_sparse_grid(dims)
     nb = _tsdf_pool(tsdf, weight, color, bricks, T)
-    _cuda(depth, w2c, K, rgb, conf)
-    _req(depth.dim() == 3 and depth.dtype == F32 and depth.is_contiguous(), "depth: contiguous fp32 [B,H,W]")
-    B, H, W = depth.shape
-    _req(1 <= B <= TSDF_MAX_VIEWS, f"tsdf_sparse_integrate: 1..{TSDF_MAX_VIEWS} views per launch")
-    _req(H > 0 and W > 0, "depth: empty image")
-    _req(w2c.shape == (B, 12) and w2c.dtype == F32 and w2c.is_contiguous(), "w2c: contiguous fp32 [B,12]")
-    _req(K.shape == (B, 4) and K.dtype == F32 and K.is_contiguous(), "K: contiguous fp32 [B,4]")
-    _req(float(voxel) > 0 and float(trunc) > 0, "voxel size and truncation must be > 0")
-    if rgb is not None:
-        _req(rgb.shape == (B, 3, H, W) and rgb.dtype == torch.uint8 and rgb.is_contiguous(), "rgb: contiguous uint8 [B,3,H,W]")
-    ch = cw = 0
-    if conf is not None:
-        _req(conf.dim() == 3 and conf.shape[0] == B and conf.dtype == F32 and conf.is_contiguous(), "conf: contiguous fp32 [B,h,w]")
-        ch, cw = conf.shape[1:]
-        _req(int(conf_ds) >= 1 and ch > 0 and cw > 0, "conf: stride >= 1, non-empty")
+    B, H, W, ch, cw = _tsdf_views("tsdf_sparse_integrate", depth, w2c, "w2c", K, voxel, trunc, TSDF_MAX_VIEWS, rgb, conf, conf_ds)
     lib = _lib.load()
     check(lib.cut3r_tsdf_sparse_integrate(_p(tsdf), _p(weight), _p(color), _p(bricks), nb, X, Y, Z, float(origin[0]), float(origin[1]),
                                           float(origin[2]), float(voxel), _p(depth), _p(rgb), _p(conf), B, H, W, ch, cw, int(conf_ds),
@@ -874,24 +872,15 @@ def tsdf_sparse_extract_mesh(tsdf, weight, color, table, bricks, dims, origin, v
     X, Y, Z, T = _tsdf_sparse_grid(dims)
     nb = _tsdf_pool(tsdf, weight, color, bricks, T)
     _tsdf_table(table, "table", torch.int32, T)
-    _req(float(voxel) > 0, "voxel size must be > 0")
     lib = _lib.load()
-    dev = tsdf.device
-    nbytes = lib.cut3r_tsdf_sparse_mesh_workspace_bytes(nb)
-    _req(nbytes > 0, "sparse TSDF pool too large")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    totals = torch.empty(2, dtype=torch.int64, device=dev)
-    check(lib.cut3r_tsdf_sparse_mesh_count(_p(tsdf), _p(weight), _p(table), _p(bricks), nb, X, Y, Z, float(weight_threshold), _p(ws), nbytes,
-                                           _p(totals), _stream()), "cut3r_tsdf_sparse_mesh_count")
-    nv, nf = (int(v) for v in totals.cpu())
-    _req(nv < 2 ** 31, f"mesh of {nv} vertices: int32 face indices cannot address it")
-    verts = torch.empty(nv, 3, dtype=F32, device=dev)
-    cols = torch.empty(nv, 3, dtype=torch.uint8, device=dev)
-    faces = torch.empty(nf, 3, dtype=torch.int32, device=dev)
-    check(lib.cut3r_tsdf_sparse_mesh_emit(_p(tsdf), _p(color), _p(table), _p(bricks), nb, X, Y, Z, float(origin[0]), float(origin[1]),
-                                          float(origin[2]), float(voxel), _p(ws), nbytes, _p(verts), _p(cols), _p(faces), nv, nf, _stream()),
-          "cut3r_tsdf_sparse_mesh_emit")
-    return verts, cols, faces
+    o = [float(v) for v in origin]
+    pool = (_p(table), _p(bricks), nb, X, Y, Z)
+    return _tsdf_mesh(
+        tsdf.device, voxel, lambda: lib.cut3r_tsdf_sparse_mesh_workspace_bytes(nb),
+        lambda ws, nbytes, totals: lib.cut3r_tsdf_sparse_mesh_count(_p(tsdf), _p(weight), *pool, float(weight_threshold), ws, nbytes, totals,
+                                                                    _stream()),
+        lambda ws, nbytes, *out: lib.cut3r_tsdf_sparse_mesh_emit(_p(tsdf), _p(color), *pool, *o, float(voxel), ws, nbytes, *out, _stream()),
+        "tsdf_sparse", "sparse TSDF pool")
 
 
 # ------------------------------------------------------------------------------------------------ reconstruction metrics

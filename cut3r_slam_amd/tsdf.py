@@ -62,21 +62,47 @@ def _views(dev, depth, w2c, K, rgb, conf, conf_min):
     return depth, w2c, K, rgb, conf
 
 
-class TSDFVolume:
+class _Volume:
+    """What the two volumes share: the fp32 lattice and truncation, from_bounds, the batching of views into launches of <= 16 and the mesh
+    as numpy arrays.  A subclass checks its dims, owns its storage and supplies grid_for, _integrate_batch and _extract."""
+
+    def __init__(self, origin, voxel_size, dims, trunc_voxels, depth_max, device):
+        if not voxel_size > 0 or not trunc_voxels > 0:
+            raise ValueError("voxel_size and trunc_voxels must be > 0")
+        self.origin = tuple(float(np.float32(o)) for o in origin)
+        self.voxel_size = float(np.float32(voxel_size))
+        self.dims = tuple(dims)
+        self.trunc = float(np.float32(trunc_voxels * self.voxel_size))
+        self.depth_max = float(depth_max)
+        self.device = torch.device(device)
+
+    @classmethod
+    def _from_bounds(cls, lo, hi, voxel_size, pad, limit, trunc_voxels, depth_max, device):
+        pad = trunc_voxels * voxel_size if pad is None else pad
+        origin, dims = cls.grid_for(lo, hi, voxel_size, pad, limit)
+        return cls(origin, voxel_size, dims, trunc_voxels=trunc_voxels, depth_max=depth_max, device=device)
+
+    def _integrate(self, depth, w2c, K, rgb, conf, conf_ds, conf_min):
+        """the views (as _views returns them) through _integrate_batch, <= 16 at a time, in order"""
+        for a in range(0, depth.shape[0], ops.TSDF_MAX_VIEWS):
+            b = a + ops.TSDF_MAX_VIEWS
+            self._integrate_batch(depth[a:b], w2c[a:b], K[a:b], self.trunc, self.depth_max, rgb=None if rgb is None else rgb[a:b],
+                                  conf=None if conf is None else conf[a:b], conf_ds=conf_ds, conf_min=0.0 if conf_min is None else conf_min)
+        return self
+
+    @torch.no_grad()
+    def extract_mesh(self, weight_threshold=1.0) -> Mesh:
+        return Mesh(*(t.cpu().numpy() for t in self._extract(weight_threshold)))
+
+
+class TSDFVolume(_Volume):
     """Dense TSDF grid: voxel (i, j, k) at origin + voxel_size * (i, j, k), planes [Z,Y,X] (x fastest); tsdf = 1, weight = color = 0 at start."""
 
     def __init__(self, origin, voxel_size, dims, trunc_voxels=8.0, depth_max=5.0, device="cuda:0"):
         X, Y, Z = (int(d) for d in dims)
         if min(X, Y, Z) <= 0 or X * Y * Z >= 2 ** 31:
             raise ValueError(f"TSDF grid {X}x{Y}x{Z}: dims must be > 0 and X*Y*Z < 2^31")
-        if not voxel_size > 0 or not trunc_voxels > 0:
-            raise ValueError("voxel_size and trunc_voxels must be > 0")
-        self.origin = tuple(float(np.float32(o)) for o in origin)
-        self.voxel_size = float(np.float32(voxel_size))
-        self.dims = (X, Y, Z)
-        self.trunc = float(np.float32(trunc_voxels * self.voxel_size))
-        self.depth_max = float(depth_max)
-        self.device = torch.device(device)
+        super().__init__(origin, voxel_size, (X, Y, Z), trunc_voxels, depth_max, device)
         self.tsdf = torch.ones(Z, Y, X, dtype=torch.float32, device=self.device)
         self.weight = torch.zeros(Z, Y, X, dtype=torch.float32, device=self.device)
         self.color = torch.zeros(3, Z, Y, X, dtype=torch.float32, device=self.device)
@@ -94,9 +120,7 @@ class TSDFVolume:
     @classmethod
     def from_bounds(cls, lo, hi, voxel_size, pad=None, max_voxels=2 ** 30, trunc_voxels=8.0, depth_max=5.0, device="cuda:0"):
         """the grid covering the box [lo, hi] padded by `pad` (default: the truncation distance)"""
-        pad = trunc_voxels * voxel_size if pad is None else pad
-        origin, dims = cls.grid_for(lo, hi, voxel_size, pad, max_voxels)
-        return cls(origin, voxel_size, dims, trunc_voxels=trunc_voxels, depth_max=depth_max, device=device)
+        return cls._from_bounds(lo, hi, voxel_size, pad, max_voxels, trunc_voxels, depth_max, device)
 
     @property
     def nbytes(self):
@@ -106,19 +130,13 @@ class TSDFVolume:
     def integrate(self, depth, w2c, K, rgb=None, conf=None, conf_ds=1, conf_min=None):
         """fuse B views in order, in launches of <= 16.  depth [B,H,W] metres; w2c [B,12] (or [B,3,4] / [B,4,4]) world->camera; K [4] or
         [B,4] fx fy cx cy; rgb u8 [B,3,H,W]; conf [B,h,w] at stride conf_ds, pixels with conf < conf_min skipped (conf_min None: no gate)."""
-        depth, w2c, K, rgb, conf = _views(self.device, depth, w2c, K, rgb, conf, conf_min)
-        B = depth.shape[0]
-        for a in range(0, B, ops.TSDF_MAX_VIEWS):
-            b = min(B, a + ops.TSDF_MAX_VIEWS)
-            ops.tsdf_integrate(self.tsdf, self.weight, self.color, self.origin, self.voxel_size, depth[a:b], w2c[a:b], K[a:b], self.trunc,
-                               self.depth_max, rgb=None if rgb is None else rgb[a:b], conf=None if conf is None else conf[a:b],
-                               conf_ds=conf_ds, conf_min=0.0 if conf_min is None else conf_min)
-        return self
+        return self._integrate(*_views(self.device, depth, w2c, K, rgb, conf, conf_min), conf_ds, conf_min)
 
-    @torch.no_grad()
-    def extract_mesh(self, weight_threshold=1.0) -> Mesh:
-        v, c, f = ops.tsdf_extract_mesh(self.tsdf, self.weight, self.color, self.origin, self.voxel_size, weight_threshold)
-        return Mesh(v.cpu().numpy(), c.cpu().numpy(), f.cpu().numpy())
+    def _integrate_batch(self, *views, **gate):
+        ops.tsdf_integrate(self.tsdf, self.weight, self.color, self.origin, self.voxel_size, *views, **gate)
+
+    def _extract(self, weight_threshold):
+        return ops.tsdf_extract_mesh(self.tsdf, self.weight, self.color, self.origin, self.voxel_size, weight_threshold)
 
 
 def c2w_rows(w2c):
@@ -130,7 +148,7 @@ def c2w_rows(w2c):
     return np.ascontiguousarray(np.concatenate([Ri, ti], 2).reshape(-1, 12), dtype=np.float32)
 
 
-class SparseTSDFVolume:
+class SparseTSDFVolume(_Volume):
     """Sparse TSDF volume: the lattice of TSDFVolume over a VIRTUAL grid `dims` (voxel (i, j, k) at origin + voxel_size * (i, j, k)), stored
     only where bricks of 8^3 voxels are allocated.  An allocated voxel holds what the dense grid would hold, bit for bit: every view
     updates every allocated voxel it would update there, free space included.
@@ -150,15 +168,8 @@ class SparseTSDFVolume:
         BX, BY, BZ = ops.tsdf_brick_dims((X, Y, Z))
         if BX * BY * BZ > ops.TSDF_SPARSE_MAX_TABLE:
             raise ValueError(f"sparse TSDF grid {X}x{Y}x{Z}: {BX * BY * BZ} bricks exceed the table limit of {ops.TSDF_SPARSE_MAX_TABLE} entries")
-        if not voxel_size > 0 or not trunc_voxels > 0:
-            raise ValueError("voxel_size and trunc_voxels must be > 0")
-        self.origin = tuple(float(np.float32(o)) for o in origin)
-        self.voxel_size = float(np.float32(voxel_size))
-        self.dims = (X, Y, Z)
+        super().__init__(origin, voxel_size, (X, Y, Z), trunc_voxels, depth_max, device)
         self.brick_dims = (BX, BY, BZ)
-        self.trunc = float(np.float32(trunc_voxels * self.voxel_size))
-        self.depth_max = float(depth_max)
-        self.device = torch.device(device)
         self.flags = torch.zeros(BZ, BY, BX, dtype=torch.uint8, device=self.device)
         self.table = torch.full((BZ, BY, BX), -1, dtype=torch.int32, device=self.device)
         self.bricks = torch.zeros(0, dtype=torch.int32, device=self.device)
@@ -181,9 +192,7 @@ class SparseTSDFVolume:
     @classmethod
     def from_bounds(cls, lo, hi, voxel_size, pad=None, max_bricks=ops.TSDF_SPARSE_MAX_TABLE, trunc_voxels=8.0, depth_max=5.0, device="cuda:0"):
         """the virtual grid covering the box [lo, hi] padded by `pad` (default: the truncation distance); nothing is allocated yet"""
-        pad = trunc_voxels * voxel_size if pad is None else pad
-        origin, dims = cls.grid_for(lo, hi, voxel_size, pad, max_bricks)
-        return cls(origin, voxel_size, dims, trunc_voxels=trunc_voxels, depth_max=depth_max, device=device)
+        return cls._from_bounds(lo, hi, voxel_size, pad, max_bricks, trunc_voxels, depth_max, device)
 
     @property
     def n_bricks(self):
@@ -226,21 +235,16 @@ class SparseTSDFVolume:
             self.allocate(depth, w2c, K)
         if self.n_bricks == 0:
             return self
-        B = depth.shape[0]
-        for a in range(0, B, ops.TSDF_MAX_VIEWS):
-            b = min(B, a + ops.TSDF_MAX_VIEWS)
-            ops.tsdf_sparse_integrate(self.tsdf, self.weight, self.color, self.bricks, self.dims, self.origin, self.voxel_size, depth[a:b],
-                                      w2c[a:b], K[a:b], self.trunc, self.depth_max, rgb=None if rgb is None else rgb[a:b],
-                                      conf=None if conf is None else conf[a:b], conf_ds=conf_ds, conf_min=0.0 if conf_min is None else conf_min)
-        return self
+        return self._integrate(depth, w2c, K, rgb, conf, conf_ds, conf_min)
 
-    @torch.no_grad()
-    def extract_mesh(self, weight_threshold=1.0) -> Mesh:
+    def _integrate_batch(self, *views, **gate):
+        ops.tsdf_sparse_integrate(self.tsdf, self.weight, self.color, self.bricks, self.dims, self.origin, self.voxel_size, *views, **gate)
+
+    def _extract(self, weight_threshold):
         if self.n_bricks == 0:
-            return Mesh(np.zeros((0, 3), np.float32), np.zeros((0, 3), np.uint8), np.zeros((0, 3), np.int32))
-        v, c, f = ops.tsdf_sparse_extract_mesh(self.tsdf, self.weight, self.color, self.table, self.bricks, self.dims, self.origin,
-                                               self.voxel_size, weight_threshold)
-        return Mesh(v.cpu().numpy(), c.cpu().numpy(), f.cpu().numpy())
+            return torch.zeros(0, 3, dtype=torch.float32), torch.zeros(0, 3, dtype=torch.uint8), torch.zeros(0, 3, dtype=torch.int32)
+        return ops.tsdf_sparse_extract_mesh(self.tsdf, self.weight, self.color, self.table, self.bricks, self.dims, self.origin,
+                                            self.voxel_size, weight_threshold)
 
     @torch.no_grad()
     def allocated_mask(self):
@@ -369,15 +373,19 @@ def depth_bounds(depth, w2c, K, depth_max):
     return lo.cpu().numpy(), hi.cpu().numpy()
 
 
-def _volume_for(depth, w2c, K, voxel_size, trunc_voxels, depth_max, bounds, max_voxels, device, sparse=False):
+def _fuse(depth, w2c, K, voxel_size, trunc_voxels, depth_max, bounds, max_voxels, device, sparse, **views):
+    """the volume over `bounds` (None: the AABB of the valid depths) with all the views fused; sparse: bricks allocated over all views first"""
     if bounds is None:
         bounds = depth_bounds(depth, w2c, K, depth_max)
         if bounds is None:
             raise ValueError(f"no depth in (0, {depth_max}]: nothing to fuse")
     if sparse:                                                       # max_voxels caps the dense grid only
-        return SparseTSDFVolume.from_bounds(bounds[0], bounds[1], voxel_size, trunc_voxels=trunc_voxels, depth_max=depth_max, device=device)
-    return TSDFVolume.from_bounds(bounds[0], bounds[1], voxel_size, max_voxels=max_voxels, trunc_voxels=trunc_voxels, depth_max=depth_max,
-                                  device=device)
+        vol = SparseTSDFVolume.from_bounds(bounds[0], bounds[1], voxel_size, trunc_voxels=trunc_voxels, depth_max=depth_max, device=device)
+        vol.allocate(depth, w2c, K)
+        return vol.integrate(depth, w2c, K, allocate=False, **views)
+    vol = TSDFVolume.from_bounds(bounds[0], bounds[1], voxel_size, max_voxels=max_voxels, trunc_voxels=trunc_voxels, depth_max=depth_max,
+                                 device=device)
+    return vol.integrate(depth, w2c, K, **views)
 
 
 @torch.no_grad()
@@ -399,11 +407,8 @@ def fuse_keyframes(keyframes, n, voxel_size, trunc_voxels=8.0, depth_max=5.0, co
     if conf_min is not None:
         idx = torch.arange(n, device=dev)
         conf = kf.conf_ds[idx // 5, idx % 5].contiguous()
-    vol = _volume_for(depth, w2c, K, voxel_size, trunc_voxels, depth_max, bounds, max_voxels, dev, sparse)
-    if sparse:
-        vol.allocate(depth, w2c, K)
-        return vol.integrate(depth, w2c, K, rgb=rgb, conf=conf, conf_ds=kf.downsample_ratio, conf_min=conf_min, allocate=False)
-    return vol.integrate(depth, w2c, K, rgb=rgb, conf=conf, conf_ds=kf.downsample_ratio, conf_min=conf_min)
+    return _fuse(depth, w2c, K, voxel_size, trunc_voxels, depth_max, bounds, max_voxels, dev, sparse, rgb=rgb, conf=conf,
+                 conf_ds=kf.downsample_ratio, conf_min=conf_min)
 
 
 @torch.no_grad()
@@ -436,8 +441,4 @@ def fuse_mapper(mapper, voxel_size, trunc_voxels=8.0, depth_max=5.0, bounds=None
     if not mapper.viewpoints:
         raise ValueError("the mapper has no keyframes to fuse")
     depth, rgb, w2c, K = render_mapper_views(mapper)
-    vol = _volume_for(depth, w2c, K, voxel_size, trunc_voxels, depth_max, bounds, max_voxels, mapper.device, sparse)
-    if sparse:
-        vol.allocate(depth, w2c, K)
-        return vol.integrate(depth, w2c, K, rgb=rgb, allocate=False)
-    return vol.integrate(depth, w2c, K, rgb=rgb)
+    return _fuse(depth, w2c, K, voxel_size, trunc_voxels, depth_max, bounds, max_voxels, mapper.device, sparse, rgb=rgb)
