@@ -15,6 +15,23 @@
 // LDS so bias / residual / output traffic is 16-B coalesced.  Tile 128x128 with 8 waves (4x2; two waves per SIMD hide
 // each other's LDS-DMA issue: +25-30 % over 4 waves) for large grids, 64x64 when the grid would not fill 256 CUs
 // (batch-1 decoder GEMMs; 8 waves when K >= 2048).  blockIdx.z batches independent problems with element strides.
+//
+// What cut3r_gemm_desc.tile and .stages select (plan_single / plan_pair at the end of this file; tile 0 = cut3r_gemm_tile_for decides):
+//   tile    block (M x N), waves             default kernel (stages 0 or a value not listed)                    stages variants
+//   16      <= 64 rows x 16, 4 | 8 (K>=2048) gemm_skinny_kernel: Linear only, no RoPE / LayerNorm fold          -
+//   64      64 x 64, 4 | 8 (K >= 2048)       3-deep ring (CUT3R_GEMM64_STAGES = 4 | 6: deeper); fast addressing 2, 4: generic 2- / 4-deep ring, 4 waves;
+//                                            1 (Linear) with compile-time epilogues 1 / 2 / 3 (8 waves: 3), or 2  8: 8 waves, generic, whatever K
+//   128     128 x 128, 8 (4 x 2)             2-deep ring; fast addressing 1 with epilogues 1 / 2 / 3, or 2;     3, 4: 3- / 2-deep ring at 4 waves; 8: waves 2 x 4;
+//                                            1-D XCD-aware order from CUT3R_GEMM_SWZ_MIN tiles                  9: generic; 10, 14: 3- / 4-deep ring; 13: 1-D order
+//   256     256 x 256, 8, ping-pong          gemm256_kernel: fast DMA with epilogues 1 - 6 where they apply     - (ignored)
+//   128192  128 x 192, 8                     generic (the tile of the 48-wide RoPE heads), 1-D order            -
+//   192128  192 x 128, 8                     fast addressing 1, or 2 with epilogues 1 / 4; 1-D order            3: 3-deep ring
+//   256128  256 x 128, 8                     generic                                                            3: 3-deep ring
+//   12864   128 x 64, 4                      generic                                                            3: 3-deep ring
+//   stages 12 (any tile): the default kernel with s_setprio(1) around the MFMA cluster.  Any other tile is refused.
+//   Addressing: 0 generic, 1 plain operands with whole K-tiles, 2 3x3 convolution with a power-of-two Cin >= 64 (tile_addr_mode).  Epilogues:
+//   see gemm256_body.  The LayerNorm fold's producer runs only in the default kernels of tiles 64 / 128 / 256 (addressing 1, epilogue 3), its
+//   consumer in any tile but 16 (at tile 256: epilogues 1 / 2 / 6).  Pairs (cut3r_gemm_f16_pair): tiles 64, 128, 192128, 256; no stages variants.
 #include <cstdlib>
 #include "common.h"
 #include "../../include/cut3r_hip.h"
@@ -1462,40 +1479,57 @@ __global__ __launch_bounds__(256) void gemv_kernel(const float* __restrict__ X, 
 
 }  // namespace
 
+// ---------------------------------------------------------------------------------------------------------------
+// Host side.  Each entry point fills its kernel arguments (fill_args), PLANS the launch (pure host code: every refusal first, then the
+// kernel's address, the grid and the workgroup size, and the fields of GemmArgs that dispatch decides: swz, prio, nblk0) and makes ONE launch.
+typedef void (*TileFn)(GemmArgs);
+typedef void (*PairFn)(GemmPairArgs);
+template <class Fn> struct Kern { Fn fn; unsigned block; };                   // a kernel instance and its workgroup size
+template <class Fn> struct Plan { Kern<Fn> k; dim3 grid; };
+
 static inline int batch_of(const cut3r_gemm_desc* d) { return d->batch > 0 ? d->batch : 1; }
+static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+static inline long long tiles_of(int M, int N, int BM, int BN) { return (long long)cdiv(M, BM) * cdiv(N, BN); }
+// the grid of a BM x BN tiling: 2-D (x over N, y over M), or 1-D for the kernels that derive the tile from blockIdx.x (swz, gemm256, pairs)
+static dim3 tile_grid(int M, int N, int BM, int BN, bool one_d, int batch) {
+    return one_d ? dim3((unsigned)tiles_of(M, N, BM, BN), 1, batch) : dim3(cdiv(N, BN), cdiv(M, BM), batch);
+}
+// 256 if allowed, N is a multiple of 256, there are >= min256 tiles of 256 x 256 and they fill the chip -- one workgroup per CU: a grid of
+// 300 tiles costs two full rounds, so beyond one round the last one must be >= fill_pct % full (tools/bench_gemm_r2.py: from 128 tiles the
+// 256^2 kernel beats 128^2 by 20-25 % on K = 768 / 1536 projections; at 72 tiles it loses by 50 %) -- else 128 from 128 tiles of 128 x 128, else 64
+static int tile_by_fill(int N, long long t256, long long t128, long long min256, long long fill_pct, bool allow256) {
+    const long long rounds = (t256 + 255) / 256;
+    const bool fills = rounds == 1 || t256 * 100 >= rounds * 256 * fill_pct;
+    if (allow256 && (N & 255) == 0 && t256 >= min256 && fills) return 256;
+    return t128 >= 128 ? 128 : 64;
+}
 
 extern "C" int cut3r_gemm_tile_for(const cut3r_gemm_desc* d) {
     if (!d) return 0;
     if (d->tile != 0) return d->tile;
     if (d->rope_pos && d->rope_cols && d->rope_d == 48) return 128192;      // the only tile whose width is a multiple of 48
-    const int batch = d->batch > 0 ? d->batch : 1;
-    const long long big_blocks = (long long)((d->M + 127) / 128) * ((d->N + 127) / 128) * batch;
+    const int batch = batch_of(d);
     // measured (tools/bench_gemm256.py, tools/bench_gemm.py): the 256^2 ping-pong kernel wins once its grid fills the
-    // chip (>= 200 tiles) on plain linears with N a multiple of 256; 3x3 convolutions and short grids stay on 128^2
+    // chip on plain linears with N a multiple of 256; 3x3 convolutions and short grids stay on 128^2
     // (two co-resident workgroups hide each other's prologue / epilogue); 64^2 below 128 tiles of 128^2
     static const long long t256_min = [] { const char* e = getenv("CUT3R_GEMM_T256_MIN"); return e ? atoll(e) : 128LL; }();
-    const long long blocks256 = (long long)((d->M + 255) / 256) * ((d->N + 255) / 256) * batch;
-    // one workgroup per CU: a grid of 300 tiles costs two full rounds, so beyond one round require >= 85 % of the last one
-    // (round 2, tools/bench_gemm_r2.py: from 128 tiles the 256^2 kernel beats 128^2 by 20-25 % on K = 768 / 1536 projections;
-    //  at 72 tiles it loses by 50 %)
-    const long long rounds = (blocks256 + 255) / 256;
     static const long long fill_pct = [] { const char* e = getenv("CUT3R_GEMM_T256_FILL"); return e ? atoll(e) : 85LL; }();
-    const bool fills = rounds == 1 || blocks256 * 100 >= rounds * 256 * fill_pct;
     static const int conv256 = [] { const char* e = getenv("CUT3R_GEMM_CONV256"); return e ? atoi(e) : 1; }();
-    if ((d->conv_k != 3 || conv256) && !d->shuf && (d->N & 255) == 0 && blocks256 >= t256_min && fills) return 256;
+    const long long big_blocks = tiles_of(d->M, d->N, 128, 128) * batch;
+    const int by_fill = tile_by_fill(d->N, tiles_of(d->M, d->N, 256, 256) * batch, big_blocks, t256_min, fill_pct, (d->conv_k != 3 || conv256) && !d->shuf);
+    if (by_fill == 256) return 256;
     // 192 x 128 (48 x 64 per wave: fewer LDS reads and L2->LDS bytes per FLOP than 128^2, still two workgroups per CU): round 2
     // A/B (tools/bench_gemm_r2.py, same box): +8-11 % on the DPT 3x3 convolutions with 128 output channels (head.0, head.2) and
     // on the 96x128 fusion convolutions; level on the M ~ 6k decoder projections, so it is the default for convolutions with
     // enough tiles to fill the chip and an explicit choice (tile = 192128, CUT3R_GEMM_T192_MIN_M) elsewhere
     static const long long t192_min = [] { const char* e = getenv("CUT3R_GEMM_T192_MIN_M"); return e ? atoll(e) : (1LL << 60); }();
     static const int conv192 = [] { const char* e = getenv("CUT3R_GEMM_CONV192"); return e ? atoi(e) : 1; }();
-    const long long blocks192 = (long long)((d->M + 191) / 192) * ((d->N + 127) / 128) * batch;
-    if (d->conv_k == 3 && conv192 && !d->shuf && blocks192 >= 512) return 192128;
+    if (d->conv_k == 3 && conv192 && !d->shuf && tiles_of(d->M, d->N, 192, 128) * batch >= 512) return 192128;
     if (!d->shuf && d->M >= t192_min && big_blocks >= 128) return 192128;
-    return (big_blocks >= 128) ? 128 : 64;
+    return by_fill;
 }
 
-// validation + translation of a descriptor into kernel arguments (shared by the single and the pair entry point)
+// validation + translation of a descriptor into kernel arguments (shared by the single and the pair entry point); swz, prio: the plan
 static int fill_args(const cut3r_gemm_desc* d, GemmArgs& g) {
     if (!d || !d->A || !d->B || !d->C) return CUT3R_ERR_ARG;
     if (d->M <= 0 || d->N <= 0 || d->K <= 0) return CUT3R_ERR_ARG;
@@ -1514,8 +1548,7 @@ static int fill_args(const cut3r_gemm_desc* d, GemmArgs& g) {
     g.conv_k = d->conv_k; g.H = d->H; g.W = d->W; g.Cin = d->Cin; g.cstride = d->conv_stride; g.Ho = d->Ho; g.Wo = d->Wo;
     g.relu_in = d->relu_in;
     g.shuf = d->shuf; g.shuf_cout = d->shuf_cout; g.shuf_Hin = d->shuf_Hin; g.shuf_Win = d->shuf_Win;
-    g.swz = 0;
-    g.prio = (d->stages == 12) ? 1 : 0;
+    g.swz = g.prio = 0;
     g.rope_pos = (const long long*)d->rope_pos; g.rope_table = d->rope_table;
     g.rope_cols = d->rope_pos ? d->rope_cols : 0; g.rope_pmin = d->rope_pmin; g.rope_npos = d->rope_npos;
     g.rope_d = d->rope_d ? d->rope_d : 64;
@@ -1545,211 +1578,197 @@ static int fill_args(const cut3r_gemm_desc* d, GemmArgs& g) {
     return CUT3R_OK;
 }
 
+// the LayerNorm fold's producer (stats_out) lives in the compile-time epilogue 3 of the DEFAULT kernels with plain fast addressing (mode 1):
+// the one rule for the 256, 128 and 64 tiles (4 and 8 waves) and for the pair kernels
+static bool producer_ok(bool default_kernel, int am, int ep) { return default_kernel && am == 1 && ep == 3; }
+// gemm256_fast_ok in tile_addr_mode's terms: 0 generic, 1 plain operands, 2 3x3 convolution
+static int addr_mode_256(const GemmArgs& g) { return !gemm256_fast_ok(g) ? 0 : (g.conv_k == 3 ? 2 : 1); }
+
+// ---- one selection function per tile: (stages, addressing mode, compile-time epilogue[, ring depth]) -> instance.  An entry exists only
+// where that instance is launched; everything else falls to the tile's default kernel.
+static Kern<TileFn> kern16(int M, int K) {              // 1, 2 or 3..4 row blocks of 16; K >= 2048 splits over 8 waves, else 4
+    static const TileFn t[2][3] = {{gemm_skinny_kernel<4, 1>, gemm_skinny_kernel<4, 2>, gemm_skinny_kernel<4, 4>},
+                                   {gemm_skinny_kernel<8, 1>, gemm_skinny_kernel<8, 2>, gemm_skinny_kernel<8, 4>}};
+    const int mb = cdiv(M, 16), w = K >= 2048;
+    return {t[w][mb <= 2 ? mb - 1 : 2], w ? 512u : 256u};
+}
+
+// 4 waves, plain fast addressing: the compile-time epilogues of the one-window (M = 769) Linear layers (fp16 + bias, + GELU, fp32 + bias + fp32 residual)
+template <int NS> static TileFn fast64(int ep) {
+    static const TileFn t[4] = {gemm_kernel<64, 64, NS, 2, 2, 1>, gemm_kernel<64, 64, NS, 2, 2, 1, 1>, gemm_kernel<64, 64, NS, 2, 2, 1, 2>, gemm_kernel<64, 64, NS, 2, 2, 1, 3>};
+    return t[ep >= 1 && ep <= 3 ? ep : 0];
+}
+static Kern<TileFn> kern64(int stages, int K, int am, int ep) {
+    if (stages == 2) return {gemm_kernel<64, 64, 2>, 256};
+    if (stages == 4) return {gemm_kernel<64, 64, 4>, 256};
+    const bool wide = stages == 8 || (stages == 0 && K >= 2048);            // long K: 8 waves
+    if (stages != 0) am = 0;        // the addressing mode counts on the default path only, the epilogue only with addressing mode 1
+    if (am != 1) ep = 0;
+    // ring depth of the default kernels: their launches put <= 2 workgroups on a CU and wait on HBM for their weight panels
+    static const int ns = [] { const char* e = getenv("CUT3R_GEMM64_STAGES"); return e ? atoi(e) : 3; }();
+    if (wide) {
+        static const TileFn res[3] = {gemm_kernel<64, 64, 3, 2, 4, 1, 3>, gemm_kernel<64, 64, 4, 2, 4, 1, 3>, gemm_kernel<64, 64, 6, 2, 4, 1, 3>};
+        if (ep == 3) return {res[ns == 6 ? 2 : ns == 4], 512};           // fc2 + residual at one window
+        if (am == 1) return {gemm_kernel<64, 64, 3, 2, 4, 1>, 512};
+        if (am == 2) return {gemm_kernel<64, 64, 3, 2, 4, 2>, 512};
+        return {gemm_kernel<64, 64, 3, 2, 4>, 512};
+    }
+    if (am == 1) return {ns == 6 ? fast64<6>(ep) : ns == 4 ? fast64<4>(ep) : fast64<3>(ep), 256};
+    if (am == 2) return {gemm_kernel<64, 64, 3, 2, 2, 2>, 256};
+    return {gemm_kernel<64, 64, 3>, 256};
+}
+
+static Kern<TileFn> kern128(int stages, int am, int ep) {
+    switch (stages) {
+        case 3: return {gemm_kernel<128, 128, 3>, 256};
+        case 4: return {gemm_kernel<128, 128, 2>, 256};
+        case 8: return {gemm_kernel<128, 128, 2, 2, 4>, 512};          // 8 waves, 2 x 4
+        case 9: return {gemm_kernel<128, 128, 2, 4, 2>, 512};          // 8 waves, 4 x 2, generic addressing
+        case 10: return {gemm_kernel<128, 128, 3, 4, 2>, 512};
+        case 14: return {gemm_kernel<128, 128, 4, 4, 2>, 512};         // 128 KiB ring, one workgroup per CU
+    }
+    static const TileFn fast[4] = {gemm_kernel<128, 128, 2, 4, 2, 1>, gemm_kernel<128, 128, 2, 4, 2, 1, 1>, gemm_kernel<128, 128, 2, 4, 2, 1, 2>, gemm_kernel<128, 128, 2, 4, 2, 1, 3>};
+    if (am == 1) return {fast[ep >= 1 && ep <= 3 ? ep : 0], 512};
+    if (am == 2) return {gemm_kernel<128, 128, 2, 4, 2, 2>, 512};
+    return {gemm_kernel<128, 128, 2, 4, 2>, 512};
+}
+
+static Kern<TileFn> kern192(int stages, int am, int ep) {
+    if (stages == 3) return {gemm_kernel<192, 128, 3, 4, 2>, 512};     // 120 KiB ring
+    if (am == 2 && ep == 1) return {gemm_kernel<192, 128, 2, 4, 2, 2, 1>, 512};
+    if (am == 2 && ep == 4) return {gemm_kernel<192, 128, 2, 4, 2, 2, 4>, 512};
+    if (am == 1) return {gemm_kernel<192, 128, 2, 4, 2, 1>, 512};
+    if (am == 2) return {gemm_kernel<192, 128, 2, 4, 2, 2>, 512};
+    return {gemm_kernel<192, 128, 2, 4, 2>, 512};
+}
+
+// gemm256_kernel<CONV3, RELU_IN, FAST_DMA, EPI, LN>; am = addr_mode_256, the epilogue counts only with fast addressing
+static TileFn kern256(bool conv, bool relu_in, int am, int ep, bool ln) {
+    if (conv) {                                                          // the eight convolution instances
+        if (!am) { if (relu_in) return gemm256_kernel<true, true>; return gemm256_kernel<true, false>; }
+        if (relu_in) { if (ep == 4) return gemm256_kernel<true, true, true, 4>; return gemm256_kernel<true, true, true>; }
+        switch (ep) {
+            case 1: return gemm256_kernel<true, false, true, 1>;
+            case 4: return gemm256_kernel<true, false, true, 4>;
+            case 5: return gemm256_kernel<true, false, true, 5>;
+            default: return gemm256_kernel<true, false, true>;
+        }
+    }
+    if (relu_in) return gemm256_kernel<false, true>;                     // (kept as it is: the generic loader even where the fast path would qualify)
+    if (!am) return gemm256_kernel<false, false>;
+    if (ln) {                                                            // the consumer rule has left epilogues 1, 2 and 6
+        if (ep == 1) return gemm256_kernel<false, false, true, 1, true>;
+        if (ep == 2) return gemm256_kernel<false, false, true, 2, true>;
+        return gemm256_kernel<false, false, true, 6, true>;
+    }
+    switch (ep) {
+        case 1: return gemm256_kernel<false, false, true, 1>;
+        case 2: return gemm256_kernel<false, false, true, 2>;
+        case 3: return gemm256_kernel<false, false, true, 3>;
+        case 6: return gemm256_kernel<false, false, true, 6>;
+        default: return gemm256_kernel<false, false, true>;
+    }
+}
+
+static int plan_single(const cut3r_gemm_desc* d, GemmArgs& g, Plan<TileFn>& p) {
+    const int tile = cut3r_gemm_tile_for(d), stages = d->stages, batch = batch_of(d), M = d->M, N = d->N;
+    const int am = tile == 256 ? addr_mode_256(g) : tile_addr_mode(g), ep = gemm256_epi_mode(g);
+    // ---- refusals, each rule once and before any selection
+    if (tile == 16 && (M > 64 || d->conv_k == 3 || d->shuf || d->relu_in || g.rope_cols || g.ln_stats || g.stats_out)) return CUT3R_ERR_ARG;
+    // at tile 256 the LayerNorm fold's consumer lives in the compile-time epilogues 1 / 2 / 6 of the plain fast kernels (mode 1: no convolution)
+    if (g.ln_stats && tile == 256 && !(am == 1 && !d->relu_in && (ep == 1 || ep == 2 || ep == 6))) return CUT3R_ERR_ARG;
+    // (tile 256 has no stages variants: all its kernels are default ones, whatever `stages` says)
+    if (g.stats_out && !producer_ok(tile == 256 ? !d->relu_in : (stages == 0 && (tile == 128 || tile == 64)), am, ep)) return CUT3R_ERR_ARG;
+    // ---- selection
+    g.prio = stages == 12;
+    static const long long swz_min = [] { const char* e = getenv("CUT3R_GEMM_SWZ_MIN"); return e ? atoll(e) : 200LL; }();
+    int BM, BN;
+    bool one_d = false;             // 1-D grid: gemm256_body's own tile order, or the XCD-aware rasterisation (swz)
+    switch (tile) {
+        case 16: BM = 64, BN = 16; p.k = kern16(M, d->K); break;
+        case 64: BM = 64, BN = 64; p.k = kern64(stages, d->K, am, ep); break;
+        case 128: BM = 128, BN = 128; p.k = kern128(stages, am, ep); one_d = g.swz = stages == 13 || (stages == 0 && tiles_of(M, N, 128, 128) >= swz_min); break;
+        case 256: BM = 256, BN = 256; one_d = true; p.k = {kern256(d->conv_k == 3, d->relu_in, am, ep, g.ln_stats != nullptr), 512}; break;
+        // 128 x 192 (four 48-wide or three 64-wide heads per tile), 8 waves (32 x 96 per wave), 80 KB LDS
+        case 128192: BM = 128, BN = 192; one_d = g.swz = 1; p.k = {gemm_kernel<128, 192, 2, 4, 2>, 512}; break;
+        // 192 x 128, 8 waves (48 x 64 per wave), 80 KB LDS: two workgroups per CU
+        case 192128: BM = 192, BN = 128; one_d = g.swz = 1; p.k = kern192(stages, am, ep); break;
+        case 256128: BM = 256, BN = 128; p.k = {stages == 3 ? (TileFn)gemm_kernel<256, 128, 3, 4, 2> : (TileFn)gemm_kernel<256, 128, 2, 4, 2>, 512}; break;     // 3: 144 KiB ring
+        case 12864: BM = 128, BN = 64; p.k = {stages == 3 ? (TileFn)gemm_kernel<128, 64, 3> : (TileFn)gemm_kernel<128, 64, 2>, 256}; break;
+        default: return CUT3R_ERR_ARG;
+    }
+    p.grid = tile_grid(M, N, BM, BN, one_d, batch);
+    return CUT3R_OK;
+}
+
 extern "C" int cut3r_gemm_f16(const cut3r_gemm_desc* d, void* stream) {
     GemmArgs g;
-    const int rc = fill_args(d, g);
+    Plan<TileFn> p;
+    int rc = fill_args(d, g);
+    if (rc == CUT3R_OK) rc = plan_single(d, g, p);
     if (rc != CUT3R_OK) return rc;
-    const int batch = d->batch > 0 ? d->batch : 1;
-    hipStream_t s = (hipStream_t)stream;
-    const int tile = cut3r_gemm_tile_for(d);
-    if (tile == 16) {
-        if (d->M > 64 || d->conv_k == 3 || d->shuf || d->relu_in || g.rope_cols || g.ln_stats || g.stats_out) return CUT3R_ERR_ARG;
-        dim3 grid((d->N + 15) / 16, 1, batch);
-        const int mb = (d->M + 15) / 16;            // 1..4 row blocks; K >= 2048 splits over 8 waves, else 4
-#define CUT3R_SKINNY(NWV, MBV) hipLaunchKernelGGL((gemm_skinny_kernel<NWV, MBV>), grid, dim3(64 * NWV), 0, s, g)
-        if (d->K >= 2048) { if (mb == 1) CUT3R_SKINNY(8, 1); else if (mb == 2) CUT3R_SKINNY(8, 2); else CUT3R_SKINNY(8, 4); }
-        else { if (mb == 1) CUT3R_SKINNY(4, 1); else if (mb == 2) CUT3R_SKINNY(4, 2); else CUT3R_SKINNY(4, 4); }
-#undef CUT3R_SKINNY
-    } else if (tile == 256) {
-        dim3 grid(((d->N + 255) / 256) * ((d->M + 255) / 256), 1, batch);
-        const bool fast = gemm256_fast_ok(g);
-        const int epi = fast ? gemm256_epi_mode(g) : 0;
-        // the LayerNorm fold lives in the compile-time epilogues: consumer 1 / 2 / 6, producer 3
-        if (g.ln_stats && !(fast && d->conv_k != 3 && !d->relu_in && (epi == 1 || epi == 2 || epi == 6))) return CUT3R_ERR_ARG;
-        if (g.stats_out && !(fast && d->conv_k != 3 && !d->relu_in && epi == 3)) return CUT3R_ERR_ARG;
-        if (d->conv_k == 3 && d->relu_in && fast && epi == 4) hipLaunchKernelGGL((gemm256_kernel<true, true, true, 4>), grid, dim3(512), 0, s, g);
-        else if (d->conv_k == 3 && !d->relu_in && fast && epi == 5) hipLaunchKernelGGL((gemm256_kernel<true, false, true, 5>), grid, dim3(512), 0, s, g);
-        else if (d->conv_k == 3 && !d->relu_in && fast && epi == 1) hipLaunchKernelGGL((gemm256_kernel<true, false, true, 1>), grid, dim3(512), 0, s, g);
-        else if (d->conv_k == 3 && !d->relu_in && fast && epi == 4) hipLaunchKernelGGL((gemm256_kernel<true, false, true, 4>), grid, dim3(512), 0, s, g);
-        else if (d->conv_k == 3 && d->relu_in && fast) hipLaunchKernelGGL((gemm256_kernel<true, true, true>), grid, dim3(512), 0, s, g);
-        else if (d->conv_k == 3 && fast) hipLaunchKernelGGL((gemm256_kernel<true, false, true>), grid, dim3(512), 0, s, g);
-        else if (d->conv_k == 3 && d->relu_in) hipLaunchKernelGGL((gemm256_kernel<true, true>), grid, dim3(512), 0, s, g);
-        else if (d->conv_k == 3) hipLaunchKernelGGL((gemm256_kernel<true, false>), grid, dim3(512), 0, s, g);
-        else if (d->relu_in) hipLaunchKernelGGL((gemm256_kernel<false, true>), grid, dim3(512), 0, s, g);
-        else if (fast && g.ln_stats) {
-            switch (epi) {
-                case 1: hipLaunchKernelGGL((gemm256_kernel<false, false, true, 1, true>), grid, dim3(512), 0, s, g); break;
-                case 2: hipLaunchKernelGGL((gemm256_kernel<false, false, true, 2, true>), grid, dim3(512), 0, s, g); break;
-                default: hipLaunchKernelGGL((gemm256_kernel<false, false, true, 6, true>), grid, dim3(512), 0, s, g);
-            }
-        }
-        else if (fast) {
-            switch (epi) {
-                case 1: hipLaunchKernelGGL((gemm256_kernel<false, false, true, 1>), grid, dim3(512), 0, s, g); break;
-                case 2: hipLaunchKernelGGL((gemm256_kernel<false, false, true, 2>), grid, dim3(512), 0, s, g); break;
-                case 3: hipLaunchKernelGGL((gemm256_kernel<false, false, true, 3>), grid, dim3(512), 0, s, g); break;
-                case 6: hipLaunchKernelGGL((gemm256_kernel<false, false, true, 6>), grid, dim3(512), 0, s, g); break;
-                default: hipLaunchKernelGGL((gemm256_kernel<false, false, true>), grid, dim3(512), 0, s, g);
-            }
-        }
-        else hipLaunchKernelGGL((gemm256_kernel<false, false>), grid, dim3(512), 0, s, g);
-    } else if (tile == 128) {
-        dim3 grid((d->N + 127) / 128, (d->M + 127) / 128, batch);
-        static const long long swz_min = [] { const char* e = getenv("CUT3R_GEMM_SWZ_MIN"); return e ? atoll(e) : 200LL; }();
-        if (d->stages == 13 || (d->stages == 0 && (long long)grid.x * grid.y >= swz_min)) {   // XCD-aware rasterisation
-            g.swz = 1;
-            grid = dim3(grid.x * grid.y, 1, batch);
-        }
-        if (g.stats_out && d->stages != 0) return CUT3R_ERR_ARG;
-        if (d->stages == 3) hipLaunchKernelGGL((gemm_kernel<128, 128, 3>), grid, dim3(256), 0, s, g);
-        else if (d->stages == 8) hipLaunchKernelGGL((gemm_kernel<128, 128, 2, 2, 4>), grid, dim3(512), 0, s, g);   // 8 waves
-        else if (d->stages == 9) hipLaunchKernelGGL((gemm_kernel<128, 128, 2, 4, 2>), grid, dim3(512), 0, s, g);   // 8 waves
-        else if (d->stages == 10) hipLaunchKernelGGL((gemm_kernel<128, 128, 3, 4, 2>), grid, dim3(512), 0, s, g);
-        else if (d->stages == 14) hipLaunchKernelGGL((gemm_kernel<128, 128, 4, 4, 2>), grid, dim3(512), 0, s, g);      // 128 KiB ring, one workgroup per CU
-        else if (d->stages == 4) hipLaunchKernelGGL((gemm_kernel<128, 128, 2>), grid, dim3(256), 0, s, g);
-        else {
-            const int am = tile_addr_mode(g), ep = gemm256_epi_mode(g);
-            if (g.stats_out && !(am == 1 && ep == 3)) return CUT3R_ERR_ARG;      // the producer side lives in the compile-time epilogue 3
-            if (am == 1 && ep == 1) hipLaunchKernelGGL((gemm_kernel<128, 128, 2, 4, 2, 1, 1>), grid, dim3(512), 0, s, g);
-            else if (am == 1 && ep == 2) hipLaunchKernelGGL((gemm_kernel<128, 128, 2, 4, 2, 1, 2>), grid, dim3(512), 0, s, g);
-            else if (am == 1 && ep == 3) hipLaunchKernelGGL((gemm_kernel<128, 128, 2, 4, 2, 1, 3>), grid, dim3(512), 0, s, g);
-            else if (am == 1) hipLaunchKernelGGL((gemm_kernel<128, 128, 2, 4, 2, 1>), grid, dim3(512), 0, s, g);
-            else if (am == 2) hipLaunchKernelGGL((gemm_kernel<128, 128, 2, 4, 2, 2>), grid, dim3(512), 0, s, g);
-            else hipLaunchKernelGGL((gemm_kernel<128, 128, 2, 4, 2>), grid, dim3(512), 0, s, g);
-        }
-    } else if (g.stats_out && tile != 64) {
-        return CUT3R_ERR_ARG;              // producer side of the LayerNorm fold: tiles 256, 128 and 64 only
-    } else if (tile == 128192) {       // 128 x 192 (four 48-wide or three 64-wide heads per tile), 8 waves (32 x 96 per wave), 80 KB LDS
-        dim3 grid(((d->N + 191) / 192) * ((d->M + 127) / 128), 1, batch);
-        g.swz = 1;
-        hipLaunchKernelGGL((gemm_kernel<128, 192, 2, 4, 2>), grid, dim3(512), 0, s, g);
-    } else if (tile == 192128) {       // 192 x 128, 8 waves (48 x 64 per wave), 80 KB LDS: two workgroups per CU
-        dim3 grid(((d->N + 127) / 128) * ((d->M + 191) / 192), 1, batch);
-        g.swz = 1;
-        if (d->stages == 3) hipLaunchKernelGGL((gemm_kernel<192, 128, 3, 4, 2>), grid, dim3(512), 0, s, g);                 // 120 KiB ring
-        else {
-            const int am = tile_addr_mode(g), ep = gemm256_epi_mode(g);
-            if (am == 2 && ep == 1) hipLaunchKernelGGL((gemm_kernel<192, 128, 2, 4, 2, 2, 1>), grid, dim3(512), 0, s, g);
-            else if (am == 2 && ep == 4) hipLaunchKernelGGL((gemm_kernel<192, 128, 2, 4, 2, 2, 4>), grid, dim3(512), 0, s, g);
-            else if (am == 1) hipLaunchKernelGGL((gemm_kernel<192, 128, 2, 4, 2, 1>), grid, dim3(512), 0, s, g);
-            else if (am == 2) hipLaunchKernelGGL((gemm_kernel<192, 128, 2, 4, 2, 2>), grid, dim3(512), 0, s, g);
-            else hipLaunchKernelGGL((gemm_kernel<192, 128, 2, 4, 2>), grid, dim3(512), 0, s, g);
-        }
-    } else if (tile == 256128) {
-        dim3 grid((d->N + 127) / 128, (d->M + 255) / 256, batch);
-        if (d->stages == 3) hipLaunchKernelGGL((gemm_kernel<256, 128, 3, 4, 2>), grid, dim3(512), 0, s, g);                 // 144 KiB ring
-        else hipLaunchKernelGGL((gemm_kernel<256, 128, 2, 4, 2>), grid, dim3(512), 0, s, g);
-    } else if (tile == 12864) {
-        dim3 grid((d->N + 63) / 64, (d->M + 127) / 128, batch);
-        if (d->stages == 3) hipLaunchKernelGGL((gemm_kernel<128, 64, 3>), grid, dim3(256), 0, s, g);
-        else hipLaunchKernelGGL((gemm_kernel<128, 64, 2>), grid, dim3(256), 0, s, g);
-    } else if (tile == 64) {
-        dim3 grid((d->N + 63) / 64, (d->M + 63) / 64, batch);
-        if (g.stats_out && d->stages != 0) return CUT3R_ERR_ARG;
-        if (d->stages == 2) hipLaunchKernelGGL((gemm_kernel<64, 64, 2>), grid, dim3(256), 0, s, g);
-        else if (d->stages == 8 || (d->stages == 0 && d->K >= 2048)) {   // long K: 8 waves
-            const int am = d->stages == 0 ? tile_addr_mode(g) : 0;
-            const int ep = am == 1 ? gemm256_epi_mode(g) : 0;
-            if (g.stats_out && ep != 3) return CUT3R_ERR_ARG;
-            // ring depth (CUT3R_GEMM64_STAGES): these launches put <= 2 workgroups on a CU and wait on HBM for their weight panels
-            static const int ns8 = [] { const char* e = getenv("CUT3R_GEMM64_STAGES"); return e ? atoi(e) : 3; }();
-            if (ep == 3 && ns8 == 6) hipLaunchKernelGGL((gemm_kernel<64, 64, 6, 2, 4, 1, 3>), grid, dim3(512), 0, s, g);
-            else if (ep == 3 && ns8 == 4) hipLaunchKernelGGL((gemm_kernel<64, 64, 4, 2, 4, 1, 3>), grid, dim3(512), 0, s, g);
-            else if (ep == 3) hipLaunchKernelGGL((gemm_kernel<64, 64, 3, 2, 4, 1, 3>), grid, dim3(512), 0, s, g);     // fc2 + residual at one window
-            else if (am == 1) hipLaunchKernelGGL((gemm_kernel<64, 64, 3, 2, 4, 1>), grid, dim3(512), 0, s, g);
-            else if (am == 2) hipLaunchKernelGGL((gemm_kernel<64, 64, 3, 2, 4, 2>), grid, dim3(512), 0, s, g);
-            else hipLaunchKernelGGL((gemm_kernel<64, 64, 3, 2, 4>), grid, dim3(512), 0, s, g);
-        }
-        else if (d->stages == 4) hipLaunchKernelGGL((gemm_kernel<64, 64, 4>), grid, dim3(256), 0, s, g);
-        else {
-            const int am = d->stages == 0 ? tile_addr_mode(g) : 0;
-            // compile-time epilogues for the one-window (M = 769) Linear layers: fp16 + bias, + GELU, fp32 + bias + fp32 residual
-            const int ep = am == 1 ? gemm256_epi_mode(g) : 0;
-            if (g.stats_out && ep != 3) return CUT3R_ERR_ARG;
-            static const int ns4 = [] { const char* e = getenv("CUT3R_GEMM64_STAGES"); return e ? atoi(e) : 3; }();
-#define CUT3R_T64(NS)                                                                                                   \
-    do {                                                                                                                 \
-        if (ep == 1) hipLaunchKernelGGL((gemm_kernel<64, 64, NS, 2, 2, 1, 1>), grid, dim3(256), 0, s, g);                \
-        else if (ep == 2) hipLaunchKernelGGL((gemm_kernel<64, 64, NS, 2, 2, 1, 2>), grid, dim3(256), 0, s, g);           \
-        else if (ep == 3) hipLaunchKernelGGL((gemm_kernel<64, 64, NS, 2, 2, 1, 3>), grid, dim3(256), 0, s, g);           \
-        else hipLaunchKernelGGL((gemm_kernel<64, 64, NS, 2, 2, 1>), grid, dim3(256), 0, s, g);                           \
-    } while (0)
-            if (am == 1 && ns4 == 6) CUT3R_T64(6);
-            else if (am == 1 && ns4 == 4) CUT3R_T64(4);
-            else if (am == 1) CUT3R_T64(3);
-#undef CUT3R_T64
-            else if (am == 2) hipLaunchKernelGGL((gemm_kernel<64, 64, 3, 2, 2, 2>), grid, dim3(256), 0, s, g);
-            else hipLaunchKernelGGL((gemm_kernel<64, 64, 3>), grid, dim3(256), 0, s, g);
-        }
-    } else {
-        return CUT3R_ERR_ARG;
-    }
+    hipLaunchKernelGGL(p.k.fn, p.grid, dim3(p.k.block), 0, (hipStream_t)stream, g);
     return cut3r_check_launch();
+}
+
+// the 64 x 64 pair kernels of the one-window (M = 768 / 769) decoder: state-side + image-side projection of a layer in ONE launch of 2 x 156
+// tiles.  ep: the compile-time epilogue both problems agreed on (fc1: 2, residual projections: 3 -- also the LayerNorm fold's producer), else
+// the run-time epilogue (fused RoPE of the image side next to the plain state side; LayerNorm fold consumer in either)
+static Kern<PairFn> pair64(bool wide, int am, int ep) {
+    if (wide) {
+        if (ep == 3) return {gemm_pair_kernel<64, 64, 3, 2, 4, 1, 3>, 512};
+        if (am) return {gemm_pair_kernel<64, 64, 3, 2, 4, 1, 0>, 512};
+        return {gemm_pair_kernel<64, 64, 3, 2, 4, 0, 0>, 512};
+    }
+    if (ep == 1) return {gemm_pair_kernel<64, 64, 3, 2, 2, 1, 1>, 256};
+    if (ep == 2) return {gemm_pair_kernel<64, 64, 3, 2, 2, 1, 2>, 256};
+    if (ep == 3) return {gemm_pair_kernel<64, 64, 3, 2, 2, 1, 3>, 256};
+    if (am) return {gemm_pair_kernel<64, 64, 3, 2, 2, 1, 0>, 256};
+    return {gemm_pair_kernel<64, 64, 3, 2, 2, 0, 0>, 256};
+}
+
+static int plan_pair(const cut3r_gemm_desc* d0, const cut3r_gemm_desc* d1, GemmPairArgs& a, Plan<PairFn>& p) {
+    // linears only, one problem each (no batch), same N and K so both take the same tile kernel
+    for (const cut3r_gemm_desc* d : {d0, d1})
+        if (d->conv_k == 3 || d->shuf || d->relu_in || (d->batch > 1)) return CUT3R_ERR_ARG;
+    if (d0->N != d1->N || d0->K != d1->K) return CUT3R_ERR_ARG;
+    const int M0 = d0->M, M1 = d1->M, N = d0->N;
+    const bool special = d0->ln_stats || d1->ln_stats || d0->stats_out || d1->stats_out || a.p[0].rope_cols || a.p[1].rope_cols;
+    // tile choice on the COMBINED grid (the two problems fill the chip together).  Kept as it is: the first descriptor's `tile` only, and the
+    // constants 128 and 85 where cut3r_gemm_tile_for reads CUT3R_GEMM_T256_MIN / CUT3R_GEMM_T256_FILL
+    int tile = d0->tile;
+    if (tile == 0)
+        tile = special ? 64 : tile_by_fill(N, tiles_of(M0, N, 256, 256) + tiles_of(M1, N, 256, 256), tiles_of(M0, N, 128, 128) + tiles_of(M1, N, 128, 128), 128, 85, true);
+    // a compile-time epilogue only when both problems qualify for the same one
+    const int am = tile_addr_mode(a.p[0]) == 1 && tile_addr_mode(a.p[1]) == 1;
+    const int e0 = gemm256_epi_mode(a.p[0]), e1 = gemm256_epi_mode(a.p[1]);
+    const int ep = (am && e0 == e1 && (e0 == 1 || e0 == 2 || e0 == 3)) ? e0 : 0;
+    if (special && tile != 64) return CUT3R_ERR_ARG;          // fused RoPE / LayerNorm fold ride the 64 x 64 pair kernels (the one-window schedule)
+    if ((d0->stats_out || d1->stats_out) && !producer_ok(true, am, ep)) return CUT3R_ERR_ARG;      // (the pair kernels have no stages variants)
+    int BM, BN, swz = 1;            // 1-D grid: tile (pid_m, pid_n) from the XCD-aware rasterisation of each problem
+    switch (tile) {
+        case 64: BM = 64, BN = 64; p.k = pair64(d0->K >= 2048, am, ep); break;
+        case 128: BM = 128, BN = 128; p.k = {gemm_pair_kernel<128, 128, 2, 4, 2>, 512}; break;
+        case 192128: BM = 192, BN = 128; p.k = {gemm_pair_kernel<192, 128, 2, 4, 2>, 512}; break;
+        case 256: BM = 256, BN = 256; p.k = {gemm256_pair_kernel, 512}; swz = 0; break;      // gemm256_body has its own tile order
+        default: return CUT3R_ERR_ARG;
+    }
+    a.p[0].swz = a.p[1].swz = swz;
+    a.p[0].prio = d0->stages == 12; a.p[1].prio = d1->stages == 12;
+    a.nblk0 = (int)tiles_of(M0, N, BM, BN);
+    p.grid = dim3(a.nblk0 + (unsigned)tiles_of(M1, N, BM, BN));
+    return CUT3R_OK;
 }
 
 extern "C" int cut3r_gemm_f16_pair(const cut3r_gemm_desc* d0, const cut3r_gemm_desc* d1, void* stream) {
     if (!d0 || !d1) return CUT3R_ERR_ARG;
     GemmPairArgs a;
+    Plan<PairFn> p;
     int rc = fill_args(d0, a.p[0]);
+    if (rc == CUT3R_OK) rc = fill_args(d1, a.p[1]);
+    if (rc == CUT3R_OK) rc = plan_pair(d0, d1, a, p);
     if (rc != CUT3R_OK) return rc;
-    rc = fill_args(d1, a.p[1]);
-    if (rc != CUT3R_OK) return rc;
-    // linears only, one problem each (no batch), same N and K so both take the same tile kernel
-    for (const cut3r_gemm_desc* d : {d0, d1})
-        if (d->conv_k == 3 || d->shuf || d->relu_in || (d->batch > 1)) return CUT3R_ERR_ARG;
-    if (d0->N != d1->N || d0->K != d1->K) return CUT3R_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    const bool special = d0->ln_stats || d1->ln_stats || d0->stats_out || d1->stats_out || a.p[0].rope_cols || a.p[1].rope_cols;
-    // tile choice on the COMBINED grid (the two problems fill the chip together)
-    int tile = d0->tile;
-    if (tile == 0) {
-        const long long t256 = (long long)((d0->M + 255) / 256 + (d1->M + 255) / 256) * ((d0->N + 255) / 256);
-        const long long rounds = (t256 + 255) / 256;
-        const bool fills = rounds == 1 || t256 * 100 >= rounds * 256 * 85;
-        const long long t128 = (long long)((d0->M + 127) / 128 + (d1->M + 127) / 128) * ((d0->N + 127) / 128);
-        tile = ((d0->N & 255) == 0 && t256 >= 128 && fills && !special) ? 256 : ((t128 >= 128 && !special) ? 128 : 64);
-    }
-    if (special && tile != 64) return CUT3R_ERR_ARG;          // fused RoPE / LayerNorm fold ride the 64 x 64 pair kernels (the one-window schedule)
-    if (tile == 64) {
-        // the one-window (M = 768 / 769) decoder: state-side + image-side projection of a layer in ONE launch of 2 x 156 tiles.  Compile-time
-        // epilogue when both problems qualify for the same one (fc1: 2, residual projections: 3 -- also the LayerNorm fold's producer), else
-        // the run-time epilogue (fused RoPE of the image side next to the plain state side; LayerNorm fold consumer in either).
-        const int n0 = ((d0->N + 63) / 64) * ((d0->M + 63) / 64), n1 = ((d1->N + 63) / 64) * ((d1->M + 63) / 64);
-        a.nblk0 = n0;
-        a.p[0].swz = a.p[1].swz = 1;             // 1-D grid: tile (pid_m, pid_n) from the XCD-aware rasterisation of each problem
-        const bool am = tile_addr_mode(a.p[0]) == 1 && tile_addr_mode(a.p[1]) == 1;
-        const int e0 = gemm256_epi_mode(a.p[0]), e1 = gemm256_epi_mode(a.p[1]);
-        const int ep = (am && e0 == e1 && (e0 == 1 || e0 == 2 || e0 == 3)) ? e0 : 0;
-        if ((d0->stats_out || d1->stats_out) && ep != 3) return CUT3R_ERR_ARG;
-        const dim3 grid(n0 + n1);
-        if (d0->K >= 2048) {
-            if (ep == 3) hipLaunchKernelGGL((gemm_pair_kernel<64, 64, 3, 2, 4, 1, 3>), grid, dim3(512), 0, s, a);
-            else if (am) hipLaunchKernelGGL((gemm_pair_kernel<64, 64, 3, 2, 4, 1, 0>), grid, dim3(512), 0, s, a);
-            else hipLaunchKernelGGL((gemm_pair_kernel<64, 64, 3, 2, 4, 0, 0>), grid, dim3(512), 0, s, a);
-        } else {
-            if (ep == 1) hipLaunchKernelGGL((gemm_pair_kernel<64, 64, 3, 2, 2, 1, 1>), grid, dim3(256), 0, s, a);
-            else if (ep == 2) hipLaunchKernelGGL((gemm_pair_kernel<64, 64, 3, 2, 2, 1, 2>), grid, dim3(256), 0, s, a);
-            else if (ep == 3) hipLaunchKernelGGL((gemm_pair_kernel<64, 64, 3, 2, 2, 1, 3>), grid, dim3(256), 0, s, a);
-            else if (am) hipLaunchKernelGGL((gemm_pair_kernel<64, 64, 3, 2, 2, 1, 0>), grid, dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((gemm_pair_kernel<64, 64, 3, 2, 2, 0, 0>), grid, dim3(256), 0, s, a);
-        }
-    } else if (tile == 256) {
-        const int n0 = ((d0->N + 255) / 256) * ((d0->M + 255) / 256), n1 = ((d1->N + 255) / 256) * ((d1->M + 255) / 256);
-        a.nblk0 = n0;
-        hipLaunchKernelGGL(gemm256_pair_kernel, dim3(n0 + n1), dim3(512), 0, s, a);
-    } else if (tile == 128) {
-        const int n0 = ((d0->N + 127) / 128) * ((d0->M + 127) / 128), n1 = ((d1->N + 127) / 128) * ((d1->M + 127) / 128);
-        a.nblk0 = n0;
-        a.p[0].swz = a.p[1].swz = 1;
-        hipLaunchKernelGGL((gemm_pair_kernel<128, 128, 2, 4, 2>), dim3(n0 + n1), dim3(512), 0, s, a);
-    } else if (tile == 192128) {
-        const int n0 = ((d0->N + 127) / 128) * ((d0->M + 191) / 192), n1 = ((d1->N + 127) / 128) * ((d1->M + 191) / 192);
-        a.nblk0 = n0;
-        a.p[0].swz = a.p[1].swz = 1;
-        hipLaunchKernelGGL((gemm_pair_kernel<192, 128, 2, 4, 2>), dim3(n0 + n1), dim3(512), 0, s, a);
-    } else {
-        return CUT3R_ERR_ARG;
-    }
+    hipLaunchKernelGGL(p.k.fn, p.grid, dim3(p.k.block), 0, (hipStream_t)stream, a);
     return cut3r_check_launch();
 }
 

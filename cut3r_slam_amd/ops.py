@@ -197,15 +197,12 @@ def rope_table(device, base, fwd=1.0, head_dim=64):
     return t
 
 
-def linear(A, W, out, bias=None, act=0, res1=None, res2=None, tile=0, rope=None, ln=None, emit=None):
-    """out[M,N] = act(A[M,K] @ W[N,K]^T + bias) (+res1)(+res2).  A,W fp16; out fp16|fp32 (any row stride).
-    rope = (positions int64 [M,2] contiguous, cols, base[, head_dim = 64 | 48]): 2-D RoPE fused on the first `cols` columns
-    (48-wide heads use the 128 x 192 tile).
-    LayerNorm fold (include/cut3r_hip.h, cut3r_gemm_desc):
-      ln = (stats fp32 [K/64, M, 2] (slab-major), colsum fp32 [N], eps): A holds the UN-normalised rows (fp16 copy of the residual stream), W the
-           gamma-folded panel, bias the folded d; the epilogue normalises per row from the slab statistics;
-      emit = (stats_out fp32 [N/64, M, 2], out16 fp16 [M, N]): an fp32 + fp32-residual GEMM also writes the fp16 copy of its
-           output and the slab statistics the next consumer needs."""
+def _launch(d, what):
+    check(_lib.load().cut3r_gemm_f16(C.byref(d), _stream()), what)
+
+
+def _linear_desc(A, W, out, bias, act, res1, tile, rope=None, ln=None, emit=None, *, res2=None, pair=False):
+    """the checks of one Linear and its descriptor: ops.linear, and each side of ops.linear_pair (pair: 64-wide heads only)"""
     _cuda(A, W, out, bias, res1, res2)
     _req(A.dtype == F16 and W.dtype == F16 and A.dim() == 2 and W.dim() == 2, "A,W must be 2-D fp16")
     M, K = A.shape
@@ -218,24 +215,17 @@ def linear(A, W, out, bias=None, act=0, res1=None, res2=None, tile=0, rope=None,
     for r in (res1, res2):
         if r is not None:
             _req(r.shape == (M, N), "residual shape")
+    d = GemmDesc()
     if rope is not None:
         pos, cols, base = rope[:3]
         hd = rope[3] if len(rope) > 3 else 64
         _req(pos.dtype == torch.int64 and pos.is_contiguous() and pos.numel() == 2 * M and pos.is_cuda, "rope positions int64 [M,2]")
-        _req(out.dtype == F16 and act == 0 and res1 is None and res2 is None and hd in (48, 64) and cols % hd == 0 and 0 < cols <= N
-             and N % hd == 0 and tile != 16, "fused rope: fp16 output, no activation / residual, whole heads of 64 or 48")
-    if tile == 16 and M > 64:           # skinny kernel: 64 rows per launch (row results do not depend on the chunking)
-        for m0 in range(0, M, 64):
-            sl = slice(m0, min(M, m0 + 64))
-            linear(A[sl], W, out[sl], bias, act, None if res1 is None else res1[sl], None if res2 is None else res2[sl], tile=16)
-        return out
-    d = GemmDesc()
+        _req(out.dtype == F16 and act == 0 and res1 is None and res2 is None and (hd == 64 or (hd == 48 and not pair)) and cols % hd == 0
+             and 0 < cols <= N and N % hd == 0 and tile != 16, "fused rope: fp16 output, no activation / residual, whole heads of 64 or 48")
+        tab = rope_table(out.device, base, 1.0, hd)
+        d.rope_pos, d.rope_table, d.rope_cols, d.rope_pmin, d.rope_npos, d.rope_d = pos.data_ptr(), tab.data_ptr(), int(cols), ROPE_PMIN, ROPE_NPOS, hd
     _fill_common(d, A, W, out, bias, res1, res2, act, tile)
     d.M, d.N, d.K, d.lda, d.ldb, d.ldc = M, N, K, A.stride(0), W.stride(0), out.stride(0)
-    if rope is not None:
-        tab = rope_table(out.device, base, 1.0, hd)
-        d.rope_pos, d.rope_table, d.rope_cols, d.rope_pmin, d.rope_npos = pos.data_ptr(), tab.data_ptr(), int(cols), ROPE_PMIN, ROPE_NPOS
-        d.rope_d = hd
     if ln is not None:
         st, cs, eps = ln
         _cuda(st, cs)
@@ -249,45 +239,28 @@ def linear(A, W, out, bias=None, act=0, res1=None, res2=None, tile=0, rope=None,
         _req(o16.dtype == F16 and o16.shape == (M, N) and o16.stride(1) == 1, "out16 fp16 [M,N]")
         _req(out.dtype == F32 and res1 is not None and res1.dtype == F32 and res2 is None and act == 0 and tile != 16, "emit: fp32 output with an fp32 residual")
         d.stats_out, d.out16, d.ld16 = so.data_ptr(), o16.data_ptr(), o16.stride(0)
-    lib = _lib.load()
-    check(lib.cut3r_gemm_f16(C.byref(d), _stream()), f"cut3r_gemm_f16 M={M} N={N} K={K}")
-    return out
-
-
-def _linear_desc(A, W, out, bias, act, res1, tile, rope=None, ln=None, emit=None):
-    _cuda(A, W, out, bias, res1)
-    _req(A.dtype == F16 and W.dtype == F16 and A.dim() == 2 and W.dim() == 2, "A,W must be 2-D fp16")
-    M, K = A.shape
-    N = W.shape[0]
-    _req(W.shape[1] == K and out.shape == (M, N), f"shape mismatch A{tuple(A.shape)} W{tuple(W.shape)} out{tuple(out.shape)}")
-    _req(A.stride(1) == 1 and W.stride(1) == 1 and out.stride(1) == 1, "unit inner strides required")
-    _req(out.dtype in (F16, F32), "out must be fp16 or fp32")
-    if bias is not None:
-        _req(bias.dtype == F32 and bias.numel() == N and bias.is_contiguous(), "bias fp32 [N]")
-    if res1 is not None:
-        _req(res1.shape == (M, N), "residual shape")
-    d = GemmDesc()
-    _fill_common(d, A, W, out, bias, res1, None, act, tile)
-    d.M, d.N, d.K, d.lda, d.ldb, d.ldc = M, N, K, A.stride(0), W.stride(0), out.stride(0)
-    if rope is not None:
-        pos, cols, base = rope[:3]
-        hd = rope[3] if len(rope) > 3 else 64
-        _req(pos.dtype == torch.int64 and pos.is_contiguous() and pos.numel() == 2 * M and pos.is_cuda and hd == 64 and out.dtype == F16, "pair rope: heads of 64")
-        tab = rope_table(out.device, base, 1.0, hd)
-        d.rope_pos, d.rope_table, d.rope_cols, d.rope_pmin, d.rope_npos, d.rope_d = pos.data_ptr(), tab.data_ptr(), int(cols), ROPE_PMIN, ROPE_NPOS, hd
-    if ln is not None:
-        st, cs, eps = ln
-        _cuda(st, cs)
-        _req(K % 64 == 0 and st.dtype == F32 and st.is_contiguous() and st.numel() == M * (K // 64) * 2 and cs.dtype == F32 and cs.numel() == N and bias is not None,
-             "ln: stats fp32 [K/64, M, 2], colsum fp32 [N], folded bias")
-        d.ln_stats, d.ln_colsum, d.ln_nslab, d.ln_eps = st.data_ptr(), cs.data_ptr(), K // 64, float(eps)
-    if emit is not None:
-        so, o16 = emit
-        _cuda(so, o16)
-        _req(N % 64 == 0 and so.dtype == F32 and so.is_contiguous() and so.numel() == M * (N // 64) * 2 and o16.dtype == F16 and o16.shape == (M, N)
-             and out.dtype == F32 and res1 is not None and res1.dtype == F32 and act == 0, "emit: stats_out fp32 [N/64, M, 2], out16 fp16 [M,N], fp32 out + residual")
-        d.stats_out, d.out16, d.ld16 = so.data_ptr(), o16.data_ptr(), o16.stride(0)
     return d
+
+
+def linear(A, W, out, bias=None, act=0, res1=None, res2=None, tile=0, rope=None, ln=None, emit=None):
+    """out[M,N] = act(A[M,K] @ W[N,K]^T + bias) (+res1)(+res2).  A,W fp16; out fp16|fp32 (any row stride).
+    rope = (positions int64 [M,2] contiguous, cols, base[, head_dim = 64 | 48]): 2-D RoPE fused on the first `cols` columns
+    (48-wide heads use the 128 x 192 tile).
+    LayerNorm fold (include/cut3r_hip.h, cut3r_gemm_desc):
+      ln = (stats fp32 [K/64, M, 2] (slab-major), colsum fp32 [N], eps): A holds the UN-normalised rows (fp16 copy of the residual stream), W the
+           gamma-folded panel, bias the folded d; the epilogue normalises per row from the slab statistics;
+      emit = (stats_out fp32 [N/64, M, 2], out16 fp16 [M, N]): an fp32 + fp32-residual GEMM also writes the fp16 copy of its
+           output and the slab statistics the next consumer needs."""
+    if tile == 16 and A.dim() == 2 and A.shape[0] > 64:           # skinny kernel: 64 rows per launch (row results do not depend on the chunking)
+        M = A.shape[0]
+        _linear_desc(A, W, out, bias, act, res1, tile, rope, res2=res2)       # the whole problem's checks (kept as it is: the chunks run without ln / emit)
+        for m0 in range(0, M, 64):
+            sl = slice(m0, min(M, m0 + 64))
+            linear(A[sl], W, out[sl], bias, act, None if res1 is None else res1[sl], None if res2 is None else res2[sl], tile=16)
+        return out
+    d = _linear_desc(A, W, out, bias, act, res1, tile, rope, ln, emit, res2=res2)
+    _launch(d, f"cut3r_gemm_f16 M={d.M} N={d.N} K={d.K}")
+    return out
 
 
 def linear_pair(p0, p1, act=0, tile=0):
@@ -297,8 +270,8 @@ def linear_pair(p0, p1, act=0, tile=0):
     the first one's only (both problems run the same tile kernel)."""
     x0 = p0[5] if len(p0) > 5 and p0[5] else {}
     x1 = p1[5] if len(p1) > 5 and p1[5] else {}
-    d0 = _linear_desc(p0[0], p0[1], p0[2], p0[3], act, p0[4], tile, **x0)
-    d1 = _linear_desc(p1[0], p1[1], p1[2], p1[3], act, p1[4], tile, **x1)
+    d0 = _linear_desc(p0[0], p0[1], p0[2], p0[3], act, p0[4], tile, pair=True, **x0)
+    d1 = _linear_desc(p1[0], p1[1], p1[2], p1[3], act, p1[4], tile, pair=True, **x1)
     _req(d0.N == d1.N and d0.K == d1.K, "pair: same N and K")
     lib = _lib.load()
     check(lib.cut3r_gemm_f16_pair(C.byref(d0), C.byref(d1), _stream()), f"cut3r_gemm_f16_pair M={d0.M}+{d1.M} N={d0.N} K={d0.K}")
@@ -323,8 +296,7 @@ def linear_batched(A, W, out, bias=None, act=0, res1=None, tile=0):
         d.res1, d.ldr1, d.res1_f16, d.strideR1 = res1.data_ptr(), res1.stride(1), int(res1.dtype == F16), res1.stride(0)
     d.M, d.N, d.K, d.lda, d.ldb, d.ldc = M, N, K, A.stride(1), W.stride(1), out.stride(1)
     d.batch, d.strideA, d.strideB, d.strideC = Z, A.stride(0), W.stride(0), out.stride(0)
-    lib = _lib.load()
-    check(lib.cut3r_gemm_f16(C.byref(d), _stream()), f"cut3r_gemm_f16 batched Z={Z} M={M} N={N} K={K}")
+    _launch(d, f"cut3r_gemm_f16 batched Z={Z} M={M} N={N} K={K}")
     return out
 
 
@@ -345,8 +317,7 @@ def conv3x3_nhwc(x, Wk, out, bias=None, stride=1, relu_in=False, act=0, res1=Non
     _fill_common(d, x, Wk, out, bias, r1, r2, act, tile)
     d.M, d.N, d.K, d.lda, d.ldb, d.ldc = M, Cout, 9 * Cin, Cin, 9 * Cin, Cout
     d.conv_k, d.H, d.W, d.Cin, d.conv_stride, d.Ho, d.Wo, d.relu_in = 3, H, Wd, Cin, stride, Ho, Wo, int(relu_in)
-    lib = _lib.load()
-    check(lib.cut3r_gemm_f16(C.byref(d), _stream()), f"cut3r_gemm_f16(conv3x3) M={M} N={Cout} K={9*Cin}")
+    _launch(d, f"cut3r_gemm_f16(conv3x3) M={M} N={Cout} K={9*Cin}")
     return out
 
 
@@ -363,8 +334,7 @@ def conv_transpose_nhwc(x, Wt, out, bias, s):
     _fill_common(d, x, Wt, out, bias, None, None, 0, 0)
     d.M, d.N, d.K, d.lda, d.ldb, d.ldc = Bn * H * Wd, s * s * Cout, Cin, Cin, Cin, Cout
     d.shuf, d.shuf_cout, d.shuf_Hin, d.shuf_Win = s, Cout, H, Wd
-    lib = _lib.load()
-    check(lib.cut3r_gemm_f16(C.byref(d), _stream()), "cut3r_gemm_f16(convT)")
+    _launch(d, "cut3r_gemm_f16(convT)")
     return out
 
 

@@ -247,6 +247,60 @@ def test_pair_refusals_leave_the_outputs_alone():
     _refused(lambda: raw(d0, d1), [g])
 
 
+def test_single_refusals_leave_the_outputs_alone():
+    """the refusal rules of cut3r_gemm_f16 (ops.linear refuses some of these calls itself; `raw` hands the descriptor to the C side): an
+    unknown tile, the exclusions of the skinny tile, the LayerNorm fold's producer anywhere but in the default kernels of tiles 64 / 128 / 256
+    with whole K-tiles and an fp32 residual, its consumer at tile 256 without a compile-time epilogue.  No kernel runs.
+    (tests/test_lnfold_gpu.py holds `ln` at tile 16 through ops.linear.  The skinny cases with `ln` / `emit` have 64 rows: above that ops.linear
+    launches 64-row chunks, and the chunks run without `ln` / `emit`.)"""
+    lib = _lib.load()
+    M, N, K = 130, 128, 192
+    A, W, b, _ = GF.operands(M, N, K, 1)
+    A, W, b = A.to(DEV), W.to(DEV), b.to(DEV)
+    At, Wt = torch.zeros(M, 200, dtype=F16, device=DEV), torch.zeros(N, 200, dtype=F16, device=DEV)      # a K tail: generic addressing
+    p = _consumer(M, K, N, 14)
+    pos = torch.zeros(M, 2, dtype=torch.int64, device=DEV)
+    x, x16 = torch.zeros(M, N, device=DEV), torch.zeros(M, N, dtype=F16, device=DEV)
+
+    def raw(d, **fields):
+        for k, v in fields.items():
+            setattr(d, k, v)
+        rc = lib.cut3r_gemm_f16(C.byref(d), ops._stream())
+        assert rc == 1, rc
+        raise ValueError("refused by cut3r_gemm_f16")
+
+    g = GF.rows_in([M], N, F16)
+    o = g.views[0]
+    _refused(lambda: ops.linear(A, W, o, b, tile=999), [g])
+    # the skinny tile: at most 64 rows, no relu_in, no fused RoPE, no LayerNorm fold on either side
+    _refused(lambda: raw(ops._linear_desc(A[:65], W, o[:65], b, 0, None, 16)), [g])
+    _refused(lambda: raw(ops._linear_desc(A[:64], W, o[:64], b, 0, None, 16), relu_in=1), [g])
+    _refused(lambda: ops.linear(A, W, o, b, tile=16, rope=(pos, 64, 100.0)), [g])
+    _refused(lambda: raw(ops._linear_desc(A[:64], W, o[:64], b, 0, None, 64, rope=(pos[:64], 64, 100.0)), tile=16), [g])
+    ln64 = (p["st"][:, :64].contiguous(), p["dc"], EPS)
+    _refused(lambda: raw(ops._linear_desc(p["x16"][:64], p["dWf"], o[:64], p["dd"], 0, None, 64, ln=ln64), tile=16), [g])
+
+    # the producer side of the LayerNorm fold
+    g32, g16 = GF.rows_in([M], N, F32), GF.rows_in([M], N, F16)
+    o32, o16 = g32.views[0], g16.views[0]
+    st = torch.full((N // 64, M, 2), float("nan"), device=DEV)
+    emit, emit64 = (st, o16), (st[:, :64].contiguous(), o16[:64])
+    _refused(lambda: ops.linear(A[:64], W, o32[:64], b, res1=x[:64], tile=16, emit=emit64), [g32, g16])
+    _refused(lambda: raw(ops._linear_desc(A[:64], W, o32[:64], b, 0, x[:64], 64, emit=emit64), tile=16), [g32, g16])
+    for tile in (128192, 192128, 256128, 12864):            # tiles without the producer's epilogue
+        _refused(lambda: ops.linear(A, W, o32, b, res1=x, tile=tile, emit=emit), [g32, g16])
+    for tile in (64, 128, 256):                             # generic addressing: no compile-time epilogue
+        _refused(lambda: ops.linear(At, Wt, o32, b, res1=x, tile=tile, emit=emit), [g32, g16])
+        _refused(lambda: ops.linear(A, W, o32, b, res1=x16, tile=tile, emit=emit), [g32, g16])         # an fp16 residual
+        _refused(lambda: raw(ops._linear_desc(A, W, o32, b, 0, x, tile, emit=emit), res1=x16.data_ptr(), res1_f16=1), [g32, g16])
+    assert bool(torch.isnan(st).all())
+
+    # the consumer side at tile 256 lives in the compile-time epilogues: N = 4 mod 8 has none
+    p = _consumer(M, K, 132, 16)
+    g = GF.rows_in([M], 132, F16)
+    _refused(lambda: ops.linear(p["x16"], p["dWf"], g.views[0], p["dd"], tile=256, ln=(p["st"], p["dc"], EPS)), [g])
+
+
 # ------------------------------------------------------------------------------------------------ 2. batched launches
 # (Z, M, N, K, tile, out, layout, bias, res1, act).  "odd" puts sC (fp16 outputs), sBias and sR1 (fp16 residuals) off the alignment that
 # gemm256_epi_mode asks of a compile-time epilogue (sC & 7, sBias & 3, sR1 & 7); "contig" and "embed" sit on the other side of it
