@@ -167,12 +167,22 @@ SIGNATURES = {
     "cut3r_depth_l1": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_ll, c_void_p],
     "cut3r_points_in_view": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p],
     "cut3r_mesh_vertex_visible": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p],
+    "cut3r_depth_cloud_workspace_bytes": [c_int, c_int, c_int],
+    "cut3r_depth_cloud_count": [c_void_p] + [c_int] * 5 + [c_float, c_void_p, c_ll, c_void_p, c_void_p],
+    "cut3r_depth_cloud_emit": [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_float, c_void_p, c_ll, c_void_p, c_void_p, c_ll, c_ll,
+                               c_void_p],
+    "cut3r_cloud_bounds_workspace_bytes": [c_int],
+    "cut3r_cloud_bounds": [c_void_p, c_int, c_void_p, c_void_p, c_ll, c_void_p],
+    "cut3r_voxel_downsample_workspace_bytes": [c_int],
+    "cut3r_voxel_downsample_count": [c_void_p, c_int, C.c_double, c_void_p, c_void_p, c_void_p, c_ll, c_void_p, c_void_p],
+    "cut3r_voxel_downsample_emit": [c_void_p, c_void_p, c_int, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_ll, c_ll, c_void_p],
 }
 RESTYPES = {"cut3r_ba_workspace_floats": c_ll, "cut3r_gs_workspace_bytes": c_ll, "cut3r_schur_mono_prior_workspace_floats": c_ll,
             "cut3r_knn3_grid_workspace_bytes": c_ll, "cut3r_tsdf_mesh_workspace_bytes": c_ll, "cut3r_tsdf_sparse_assign_workspace_bytes": c_ll,
             "cut3r_tsdf_sparse_mesh_workspace_bytes": c_ll, "cut3r_mesh_cdf_workspace_bytes": c_ll,
             "cut3r_nn_workspace_bytes": c_ll, "cut3r_icp_moments_workspace_bytes": c_ll, "cut3r_mesh_raster_workspace_bytes": c_ll,
-            "cut3r_depth_l1_workspace_bytes": c_ll}
+            "cut3r_depth_l1_workspace_bytes": c_ll, "cut3r_depth_cloud_workspace_bytes": c_ll, "cut3r_cloud_bounds_workspace_bytes": c_ll,
+            "cut3r_voxel_downsample_workspace_bytes": c_ll}
 
 _lib = None
 

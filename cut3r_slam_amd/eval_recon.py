@@ -12,6 +12,9 @@ viewpoints inside the room) and the clipped Chamfer distances of geometry_eval_u
   voxel_down_sample                            Open3D's PointCloud.voxel_down_sample (eval7_scenes_dense.py:238-250), output sorted by voxel
   sim3_from_trajectories                       the Sim(3) that run_replica.py:45-46 applies to the mesh before it is scored
 
+The evaluation against ground-truth DEPTH MAPS instead of a mesh (scripts/eval7_scenes_dense.py) is cut3r_slam_amd/eval_dense.py; it uses
+icp_point_to_point and chamfer_distance_RMSE from here and the GPU voxel downsample ops.voxel_downsample.
+
 Every nearest-neighbour distance is the fp64 sqrt of the kernel's exact fp32 squared distance; means are fp64.  Inputs: a tsdf.Mesh, a PLY
 path (tsdf.read_ply) or, for point sets, an [N,3] array or tensor.  CLI: python -m cut3r_slam_amd.eval_recon REC.ply GT.ply.
 """

@@ -5,10 +5,11 @@
                    --output outputs/room0 [--kf_every 10] [--ckpt_path checkpoints/cut3r_512_dpt_4_64.pth]
 
 Writes <output>/traj_kf.txt and <output>/intrinsics.npy exactly as the reference does (evo-compatible TUM rows); with --mesh also
-<output>/tsdf_mesh_w{W:.1f}.ply per --mesh-weight, the reference's post-run mesh (TSDF fusion on the GPU, cut3r_slam_amd/tsdf.py).  The
-Gaussian-splatting mapper and its viewers are out of scope: --droidvis/--gsvis/--gtdepthdir/--posedir/
---weights are accepted and ignored.  Without a checkpoint, `--synthetic-weights` runs the production-shape network with
-seeded random weights (throughput / plumbing runs only).
+<output>/tsdf_mesh_w{W:.1f}.ply per --mesh-weight, the reference's post-run mesh (TSDF fusion on the GPU, cut3r_slam_amd/tsdf.py); with
+--eval-dense --gtdepthdir G --gt-traj T also <output>/3D_eval_results.txt, the dense point-cloud metrics of the keyframe depths against
+the GT depth maps (scripts/eval7_scenes_dense.py, cut3r_slam_amd/eval_dense.py).  The viewers are out of scope:
+--droidvis/--gsvis/--posedir/--weights are accepted and ignored, and so is --gtdepthdir without --eval-dense.  Without a checkpoint,
+`--synthetic-weights` runs the production-shape network with seeded random weights (throughput / plumbing runs only).
 """
 import argparse
 import os
@@ -48,7 +49,7 @@ def main(argv=None):
     p.add_argument("--calib", type=str, required=True, help="path to calibration file")
     p.add_argument("--config", type=str, default=None, help="path to configuration file")
     p.add_argument("--output", default="outputs/demo", help="path to save output")
-    p.add_argument("--gtdepthdir", type=str, default=None)
+    p.add_argument("--gtdepthdir", type=str, default=None, help="ground-truth 16-bit depth PNGs (read by --eval-dense only)")
     p.add_argument("--weights", default=None)
     p.add_argument("--buffer", type=int, default=-1, help="number of keyframes to buffer (default: 1/5 of total frames + 150)")
     p.add_argument("--undistort", action="store_true")
@@ -88,7 +89,18 @@ def main(argv=None):
                    "'depth l1' in cm added to eval_recon_w{W:.1f}.txt")
     p.add_argument("--gt-unseen", type=str, default=None, help="[N,3] .npy of GT points that no view of --eval-2d may see")
     p.add_argument("--n-imgs", type=int, default=10, help="views of --eval-2d (scripts/eval_recon.py:238)")
+    p.add_argument("--eval-dense", action="store_true", help="score the keyframe depth maps against the GT depth maps of --gtdepthdir at the "
+                   "poses of --gt-traj (scripts/eval7_scenes_dense.py) -> <output>/3D_eval_results.txt")
+    p.add_argument("--gt-depth-scale", type=float, default=6553.5, help="raw units per metre of the --gtdepthdir PNGs")
+    p.add_argument("--gt-calib", type=str, default=None, help="calibration of the GT depth maps (default: --calib)")
+    p.add_argument("--dense-depth-trunc", type=float, default=4.5, help="depths at or beyond this are not scored (the reference's Kinect range)")
+    p.add_argument("--dense-source", choices=("auto", "tracker", "mapper"), default="auto",
+                   help="depth maps of --eval-dense; auto: the Gaussian map's keyframe renders with --gs, else the tracked keyframes")
     args = p.parse_args(argv)
+    if args.eval_dense and not (args.gtdepthdir and args.gt_traj):
+        p.error("--eval-dense needs --gtdepthdir and --gt-traj")
+    if args.gt_depth_scale <= 0 or args.dense_depth_trunc <= 0:
+        p.error("--gt-depth-scale and --dense-depth-trunc must be > 0")
     if args.gt_mesh and not args.mesh:
         p.error("--gt-mesh needs --mesh")
     if args.mesh_sparse and not args.mesh:
@@ -99,8 +111,8 @@ def main(argv=None):
         p.error("--gt-unseen needs --eval-2d")
     if args.n_imgs <= 0:
         p.error("--n-imgs must be > 0")
-    if args.gt_traj and not args.gt_mesh:
-        p.error("--gt-traj needs --gt-mesh")
+    if args.gt_traj and not (args.gt_mesh or args.eval_dense):
+        p.error("--gt-traj needs --gt-mesh or --eval-dense")
     os.makedirs(args.output, exist_ok=True)
 
     from cut3r_slam_amd import stream
@@ -205,6 +217,15 @@ def main(argv=None):
                     fh.write(f"{res}")
                 print(f"  vs {args.gt_mesh}: accuracy {res['accuracy']:.3f} cm, completion {res['completion']:.3f} cm, "
                       f"completion ratio {res['completion_ratio']:.2f} %" + (f", depth L1 {res['depth l1']:.3f} cm" if args.eval_2d else ""))
+    if args.eval_dense:
+        from cut3r_slam_amd import eval_dense as ED
+        est = ED.from_slam(slam, args.dense_source, stream.frame_timestamps(args.imagedir, args.start))
+        gt = ED.load_depth_dir(args.gtdepthdir, args.gt_depth_scale, args.gt_traj, args.gt_calib or args.calib)
+        res = ED.dense_metrics(est, gt, depth_trunc=args.dense_depth_trunc)
+        ED.write_results(args.output, res)
+        print(f"dense eval vs {args.gtdepthdir}: RMSE acc {res['RMSE_acc']:.5f}, RMSE comp {res['RMSE_comp']:.5f}, Chamfer "
+              f"{res['Chamfer_distance']:.5f} ({res['pairs']} frames, {res['n_est']} / {res['n_gt']} points, scale {res['scale']:.4f}) "
+              f"-> {args.output}/3D_eval_results.txt")
     print(f"{nframes} frames, {len(traj)} keyframes, {len(slam.graph.edges_numpy()[0])} graph edges in {time.time() - t0:.1f}s "
           f"-> {args.output}/traj_kf.txt")
     return 0

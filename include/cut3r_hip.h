@@ -594,6 +594,41 @@ int cut3r_points_in_view(const float* points, int N, const float* w2c, const flo
 int cut3r_mesh_vertex_visible(const float* verts, int V, const float* depth, const float* w2c, const float* K, int B, int H, int W, float eps,
                               float z_far, unsigned char* flags, void* stream);
 
+/* ---- Dense point clouds of depth maps (csrc/cloud.hip) ---------------------------------------------------------------------------------
+ * depth_cloud replaces Open3D's RGBDImage.create_from_color_and_depth + PointCloud.create_from_rgbd_image(project_valid_depth_only) +
+ * transform of scripts/eval7_scenes_dense.py:72-96, 111-147 for B in 1..16 views.  depth [B,H,W] fp32 metres and rgb [B,3,H,W] u8 (or
+ * NULL) on the device; c2w [B,12] (any 3x4 affine, row-major) and K [B,4] = fx fy cx cy of the sampling grid are HOST arrays of doubles.
+ * Grid pixel (i, j) of the H1 x W1 sampling grid reads source pixel (min(i H / H1, H - 1), min(j W / W1, W - 1)) in integer arithmetic
+ * (nearest-neighbour resampling by the exact floor); it is valid iff its depth d is finite, d > 0 and d < depth_trunc.  In fp64: z = d,
+ * x = (j - cx) z / fx, y = (i - cy) z / fy, each world coordinate ((r0 x + r1 y) + r2 z) + t, rounded once to fp32; the colour is the
+ * source pixel's.  Output order: by view, then row-major grid pixel; count -> scan -> emit, the same bits on every run, and B views in one
+ * launch give what B launches of one view give.  count fills counts [B] (device, valid pixels per view) and the workspace
+ * (cut3r_depth_cloud_workspace_bytes(B, H1, W1)); emit, with that workspace untouched, writes the n = sum(counts) points [n,3] fp32 and
+ * colors [n,3] u8 (colors and rgb both given or both NULL).  Refused: B outside 1..16, sizes <= 0, depth_trunc <= 0 or NaN, a non-finite
+ * c2w or K, fx or fy <= 0, capacity (the points the output buffers hold) < n. */
+long long cut3r_depth_cloud_workspace_bytes(int B, int H1, int W1);           /* -1 on bad sizes */
+int cut3r_depth_cloud_count(const float* depth, int B, int H, int W, int H1, int W1, float depth_trunc, void* workspace,
+                            long long workspace_bytes, long long* counts, void* stream);
+int cut3r_depth_cloud_emit(const float* depth, const unsigned char* rgb, int B, int H, int W, int H1, int W1, const double* c2w,
+                           const double* K, float depth_trunc, const void* workspace, long long workspace_bytes, float* points,
+                           unsigned char* colors, long long n, long long capacity, void* stream);
+/* out [7] fp32 (device) = min x y z, max x y z over the finite coordinates of points [N,3], and 1 when a coordinate is not finite (else 0):
+ * exact and independent of the order.  workspace: cut3r_cloud_bounds_workspace_bytes(N). */
+long long cut3r_cloud_bounds_workspace_bytes(int N);                          /* -1 when N <= 0 */
+int cut3r_cloud_bounds(const float* points, int N, float* out, void* workspace, long long workspace_bytes, void* stream);
+/* Open3D PointCloud.voxel_down_sample (eval7_scenes_dense.py:238-241).  lo, hi: HOST fp32 [3], the bounds of the points (cut3r_cloud_bounds).
+ * Voxel index per axis floor(((double)p - ((double)lo - voxel / 2)) / voxel); one output per occupied voxel, sorted by (ix, iy, iz) (a
+ * stable radix sort of the 63-bit key ix << 42 | iy << 21 | iz with the point index); the output point is the fp64 sum of the voxel's
+ * points in ascending point index, one add at a time, divided by their number and rounded once to fp32; the colour (u8 [N,3] in, or NULL)
+ * the same fp64 mean, floor(mean + 0.5); counts [M] int32 the points per voxel.  count sorts and writes *total = M (device); emit, with the
+ * workspace (cut3r_voxel_downsample_workspace_bytes(N)) untouched, writes the M outputs.  Refused: N <= 0, voxel <= 0 or not finite,
+ * non-finite or reversed bounds, an index >= 2^21 on some axis, M outside 1..N, capacity < M. */
+long long cut3r_voxel_downsample_workspace_bytes(int N);                      /* -1 when N <= 0 */
+int cut3r_voxel_downsample_count(const float* points, int N, double voxel, const float* lo, const float* hi, void* workspace,
+                                 long long workspace_bytes, long long* total, void* stream);
+int cut3r_voxel_downsample_emit(const float* points, const unsigned char* colors, int N, const void* workspace, long long workspace_bytes,
+                                float* out_points, unsigned char* out_colors, int* out_counts, long long M, long long capacity, void* stream);
+
 /* Measurement aid of bench.py's roofline (no reference counterpart; not on the product path): a bare MFMA loop (v_mfma_f32_16x16x32_f16,
  * 16 independent accumulator chains per wave, 8 waves per workgroup, `grid` workgroups, `iters` x 16 MFMAs per wave, operands = 16-byte
  * chunks of data[nhalf] fp16, nhalf a power of two >= 32768) with s_memtime / s_memrealtime stamps around the loop.  stamps [grid,2] u64 =
