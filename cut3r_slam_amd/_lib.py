@@ -66,6 +66,7 @@ SIGNATURES = {
     "cut3r_colmean_batched": [c_void_p, c_int, c_ll, c_int, c_int, c_int, c_void_p, c_ll, c_void_p],
     "cut3r_upsample2x_nhwc": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
     "cut3r_dpt_final": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
+    "cut3r_conv3x3_dpt_final": [C.POINTER(GemmDesc), c_void_p, c_void_p, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p],
     "cut3r_postprocess_pts": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "cut3r_postprocess_pose": [c_void_p, c_int, c_void_p, c_void_p],
     "cut3r_patch_overlap": [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p],

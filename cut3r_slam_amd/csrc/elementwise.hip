@@ -1,6 +1,7 @@
 // Memory-bound kernels of the ViT path on gfx950: RoPE-2D, LayerNorm(+adaLN), patch im2col, casts, column mean,
 // bilinear x2 upsample, DPT output activations.  All are HBM-bound: coalesced 8/16-byte accesses, one pass.
 #include "common.h"
+#include "dpt_tail.h"
 #include "../../include/cut3r_hip.h"
 
 namespace {
@@ -423,7 +424,7 @@ __global__ __launch_bounds__(256) void dpt_final_kernel(const h16* __restrict__ 
             }
         }
         if (mode == 0) {
-            act_pts_conf(a0, a1, a2, a3, true, false, pts, conf, p);
+            dpt_pts_conf<false>(a0, a1, a2, a3, pts + 3 * p, conf + p);
         } else {
             const float eps = 1e-6f;
             float o[3] = {a0, a1, a2};
@@ -458,31 +459,19 @@ __global__ __launch_bounds__(256) void dpt_final_coalesced_kernel(const h16* __r
     const size_t nwaves = ((size_t)gridDim.x * blockDim.x) >> 6;
     for (size_t p0 = wave_global * ppw; p0 < (size_t)P; p0 += nwaves * ppw) {
         const size_t p = p0 + sub;
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+        float a[4] = {0.f, 0.f, 0.f, 0.f};
         if (p < (size_t)P) {
             const half8_t v = *reinterpret_cast<const half8_t*>(in + p * Cin + chunk * 8);
 #pragma unroll
-            for (int e = 0; e < 8; e++) {
-                const float xv = (float)v[e];
-                a0 = fmaf(xv, wr[0][e], a0);
-                a1 = fmaf(xv, wr[1][e], a1);
-                a2 = fmaf(xv, wr[2][e], a2);
-                a3 = fmaf(xv, wr[3][e], a3);
-            }
+            for (int o = 0; o < 4; o++) a[o] = dpt_dot8(v, wr[o]);
         }
-        for (int o = lpp >> 1; o > 0; o >>= 1) {
-            a0 += __shfl_xor(a0, o, 64);
-            a1 += __shfl_xor(a1, o, 64);
-            a2 += __shfl_xor(a2, o, 64);
-            a3 += __shfl_xor(a3, o, 64);
-        }
+        dpt_lane_sum(a, lpp);
         if (chunk == 0 && p < (size_t)P) {
-            a0 += b0; a1 += b1; a2 += b2; a3 += b3;
             if (mode == 0) {
-                act_pts_conf(a0, a1, a2, a3, true, false, pts, conf, p);
+                dpt_bias_pts_conf(a, b0, b1, b2, b3, pts + 3 * p, conf + p);
             } else {
                 const float eps = 1e-6f;
-                const float o3[3] = {a0, a1, a2};
+                const float o3[3] = {a[0] + b0, a[1] + b1, a[2] + b2};
 #pragma unroll
                 for (int e = 0; e < 3; e++) {
                     const float sg = 1.0f / (1.0f + expf(-o3[e]));

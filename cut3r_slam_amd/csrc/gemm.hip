@@ -28,12 +28,14 @@
 //   192128  192 x 128, 8                     fast addressing 1, or 2 with epilogues 1 / 4; 1-D order            3: 3-deep ring
 //   256128  256 x 128, 8                     generic                                                            3: 3-deep ring
 //   12864   128 x 64, 4                      generic                                                            3: 3-deep ring
+//   cut3r_conv3x3_dpt_final: tile 192128, fast addressing 2, epilogue 7 (the DPT output stage: final 1x1 convolution + activations), only.
 //   stages 12 (any tile): the default kernel with s_setprio(1) around the MFMA cluster.  Any other tile is refused.
 //   Addressing: 0 generic, 1 plain operands with whole K-tiles, 2 3x3 convolution with a power-of-two Cin >= 64 (tile_addr_mode).  Epilogues:
 //   see gemm256_body.  The LayerNorm fold's producer runs only in the default kernels of tiles 64 / 128 / 256 (addressing 1, epilogue 3), its
 //   consumer in any tile but 16 (at tile 256: epilogues 1 / 2 / 6).  Pairs (cut3r_gemm_f16_pair): tiles 64, 128, 192128, 256; no stages variants.
 #include <cstdlib>
 #include "common.h"
+#include "dpt_tail.h"
 #include "../../include/cut3r_hip.h"
 
 namespace {
@@ -58,6 +60,9 @@ struct GemmArgs {
     // LayerNorm folded into the GEMMs (see "LayerNorm fold" below): consumer side (ln_stats != null) and producer side (stats_out != null)
     const float* ln_stats; const float* ln_c; int ln_nslab; float ln_eps;
     float* stats_out; h16* out16; int ld16;
+    // DPT output stage in the epilogue (EPI 7): final 1x1 weights fp32 [4][128] and bias [4]; points / confidence of view v = gm / (Ho*Wo)
+    // go to dpt_pts + v * dpt_pts_vs + pixel * 3 and dpt_conf + v * dpt_conf_vs + pixel (element strides); C is not written
+    const float* dpt_w; const float* dpt_b; float* dpt_pts; float* dpt_conf; long long dpt_pts_vs, dpt_conf_vs;
 };
 
 DEVINL half8_t relu8(half8_t v) {
@@ -511,7 +516,62 @@ DEVINL void gemm_tile_body(const GemmArgs& g, const int bx, const int by, const 
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     f32x4 b4 = zero4;
     if (bias && col_ok && plain) b4 = *reinterpret_cast<const f32x4*>(bias + gn);
-    if constexpr (EPI != 0) {
+    if constexpr (EPI == 7) {
+        // DPT output stage (head.2 + head.4 + activations): the tile holds all BN = 128 channels of its BM pixels, so the final 1x1
+        // convolution and the point / confidence activations run on the staged tile and the fp16 convolution output never reaches HBM.
+        // What the tail needs of an accumulator is the fp16 rounding of bias + ReLU -- exactly what the unfused store would have written --
+        // so THAT is staged: the whole tile fits the dead ring in one pass (192 x 136 fp16), the accumulators die at the one barrier and
+        // the final weights of a lane's channels fit in registers.  Then the lane layout of dpt_final_coalesced_kernel at Cin = 128:
+        // 16 lanes per pixel, lane `chunk` owns channels chunk * 8 .. + 7.  After the butterfly all 16 lanes of a pixel hold the same
+        // four totals, so lane `chunk` = i takes the pixel of iteration i and the activations (expm1, three divisions, exp: ~150
+        // instructions) are issued once for the tile's ITER7 pixels per lane group, not once per pixel.
+        constexpr int RPP7 = NTHR / 16, ITER7 = BM / RPP7;              // pixels per sweep of the workgroup, sweeps
+        constexpr int HPAD = BN + 8;                                    // fp16 row stride: 272 B (staging writes of a wave hit 64 different banks)
+        constexpr int H_BYTES = BM * HPAD * 2;
+        static_assert(BN == 128 && NTHR == 4 * BN && BM % RPP7 == 0 && ITER7 <= 16, "the DPT epilogue maps 16 lanes to a 128-channel pixel");
+        static_assert(H_BYTES + 4 * BN * 4 <= LDS_BYTES, "no room for the fp16 tile and the final weights in the ring");
+        h16* hs = reinterpret_cast<h16*>(smem);
+        float* fwl = reinterpret_cast<float*>(smem + H_BYTES);
+        fwl[tid] = g.dpt_w[tid];             // final weights [4][128]: through LDS (visible after the staging barrier), read at the point of use
+        float cb[NT];
+#pragma unroll
+        for (int j = 0; j < NT; j++) cb[j] = bias[wn * WN + j * 16 + fr];
+#pragma unroll
+        for (int i = 0; i < MT; i++)
+#pragma unroll
+            for (int j = 0; j < NT; j++)
+#pragma unroll
+                for (int e = 0; e < 4; e++)
+                    hs[(wm * WM + i * 16 + fq * 4 + e) * HPAD + wn * WN + j * 16 + fr] = (h16)fmaxf(acc[i][j][e] + cb[j], 0.f);
+        __syncthreads();
+        const int chunk = lane & 15, prow = tid >> 4;
+        float fw[4][8];
+#pragma unroll
+        for (int o = 0; o < 4; o++) {
+            const f32x4 lo = *reinterpret_cast<const f32x4*>(fwl + o * BN + chunk * 8), hi = *reinterpret_cast<const f32x4*>(fwl + o * BN + chunk * 8 + 4);
+#pragma unroll
+            for (int e = 0; e < 4; e++) { fw[o][e] = lo[e]; fw[o][4 + e] = hi[e]; }
+        }
+        float mine[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < ITER7; i++) {
+            // (every lane runs the arithmetic: the sums are 16-lane butterflies; rows past M hold the accumulators of zero operands)
+            const half8_t hv = *reinterpret_cast<const half8_t*>(hs + (prow + i * RPP7) * HPAD + chunk * 8);
+            float a[4];
+#pragma unroll
+            for (int o = 0; o < 4; o++) a[o] = dpt_dot8(hv, fw[o]);
+            dpt_lane_sum16(a);
+            if (chunk == i) { mine[0] = a[0]; mine[1] = a[1]; mine[2] = a[2]; mine[3] = a[3]; }
+        }
+        const int gm = m0 + prow + chunk * RPP7;
+        if (chunk < ITER7 && gm < M) {
+            const int hw = g.Ho * g.Wo;
+            const int view = gm / hw, pix = gm - view * hw;
+            dpt_bias_pts_conf(mine, g.dpt_b[0], g.dpt_b[1], g.dpt_b[2], g.dpt_b[3], g.dpt_pts + (size_t)view * g.dpt_pts_vs + (size_t)pix * 3,
+                              g.dpt_conf + (size_t)view * g.dpt_conf_vs + pix);
+        }
+        return;
+    } else if constexpr (EPI != 0) {
         // compile-time epilogue (the EPI codes of gemm256_body): plain row-major output, bias present, vector-aligned rows
         constexpr bool F16OUT = EPI != 3, RES = (EPI == 3 || EPI == 5);
         const int gnc = col_ok ? gn : 0;
@@ -1555,6 +1615,7 @@ static int fill_args(const cut3r_gemm_desc* d, GemmArgs& g) {
     // LayerNorm fold: consumer (ln_stats + ln_colsum) and producer (stats_out + out16) sides
     g.ln_stats = d->ln_stats; g.ln_c = d->ln_colsum; g.ln_nslab = d->ln_nslab; g.ln_eps = d->ln_eps;
     g.stats_out = d->stats_out; g.out16 = (h16*)d->out16; g.ld16 = d->ld16;
+    g.dpt_w = g.dpt_b = nullptr; g.dpt_pts = g.dpt_conf = nullptr; g.dpt_pts_vs = g.dpt_conf_vs = 0;
     if ((d->ln_stats != nullptr) != (d->ln_colsum != nullptr) || (d->stats_out != nullptr) != (d->out16 != nullptr)) return CUT3R_ERR_ARG;
     if (d->ln_stats) {
         if (!d->bias || d->conv_k == 3 || d->shuf || d->relu_in || batch_of(d) != 1 || d->ln_nslab * 64 != d->K || !(d->ln_eps > 0.f) ||
@@ -1758,6 +1819,41 @@ static int plan_pair(const cut3r_gemm_desc* d0, const cut3r_gemm_desc* d1, GemmP
     a.nblk0 = (int)tiles_of(M0, N, BM, BN);
     p.grid = dim3(a.nblk0 + (unsigned)tiles_of(M1, N, BM, BN));
     return CUT3R_OK;
+}
+
+// head.2 (3x3, 128 -> 128, ReLU) with head.4 and the output activations in its epilogue: ONE instance, the 192 x 128 tile with fast 3x3
+// addressing, whatever the size of the problem (its rows are the bits of every other tile kernel).  Everything it cannot serve is refused
+// before the launch.
+static int plan_dpt_final(const cut3r_gemm_desc* d, GemmArgs& g, Plan<TileFn>& p) {
+    const bool fast3 = d->conv_k == 3 && d->conv_stride == 1 && (g.K % BK) == 0 && g.Cin >= 64 && (g.Cin & (g.Cin - 1)) == 0 && g.K == 9 * g.Cin;
+    if (!fast3 || g.N != 128 || !g.out_f16 || g.act != 2 || g.res1 || g.res2 || g.shuf || g.relu_in || batch_of(d) != 1) return CUT3R_ERR_ARG;
+    if (g.rope_cols || g.ln_stats || g.stats_out || !g.bias || ((uintptr_t)g.bias & 15)) return CUT3R_ERR_ARG;
+    if (g.Ho != g.H || g.Wo != g.W || g.Ho <= 0 || g.Wo <= 0 || g.M % (g.Ho * g.Wo) != 0) return CUT3R_ERR_ARG;
+    if (!g.dpt_w || !g.dpt_b || !g.dpt_pts || !g.dpt_conf || ((uintptr_t)g.dpt_w & 15)) return CUT3R_ERR_ARG;
+    // (the points and the confidence are stored one float at a time: 4-byte alignment)
+    if ((((uintptr_t)g.dpt_b | (uintptr_t)g.dpt_pts | (uintptr_t)g.dpt_conf) & 3) || g.dpt_pts_vs < 0 || g.dpt_conf_vs < 0) return CUT3R_ERR_ARG;
+    g.swz = 1;
+    g.prio = 0;
+    p.k = {gemm_kernel<192, 128, 2, 4, 2, 2, 7>, 512};
+    p.grid = tile_grid(g.M, g.N, 192, 128, true, 1);
+    return CUT3R_OK;
+}
+
+extern "C" int cut3r_conv3x3_dpt_final(const cut3r_gemm_desc* d, const float* w, const float* b, int mode, float* pts, long long pts_view_stride,
+                                       float* conf, long long conf_view_stride, void* stream) {
+    if (!d || mode != 0) return CUT3R_ERR_ARG;
+    cut3r_gemm_desc dd = *d;
+    dd.C = const_cast<void*>(d->A);          // (the convolution output is not written: any aligned non-null pointer passes fill_args)
+    GemmArgs g;
+    Plan<TileFn> p;
+    int rc = fill_args(&dd, g);
+    if (rc != CUT3R_OK) return rc;
+    g.C = nullptr;
+    g.dpt_w = w; g.dpt_b = b; g.dpt_pts = pts; g.dpt_conf = conf; g.dpt_pts_vs = pts_view_stride; g.dpt_conf_vs = conf_view_stride;
+    rc = plan_dpt_final(&dd, g, p);
+    if (rc != CUT3R_OK) return rc;
+    hipLaunchKernelGGL(p.k.fn, p.grid, dim3(p.k.block), 0, (hipStream_t)stream, g);
+    return cut3r_check_launch();
 }
 
 extern "C" int cut3r_gemm_f16_pair(const cut3r_gemm_desc* d0, const cut3r_gemm_desc* d1, void* stream) {

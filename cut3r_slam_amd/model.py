@@ -96,6 +96,7 @@ class Cut3rModel:
         # DPT head of view i (all windows) on a third stream while the recurrent decoder works on view i+1: the decoder's
         # mid-size kernels leave matrix and memory pipes idle that the head's large convolutions can use
         self.head_overlap = _os.environ.get("CUT3R_HEAD_OVERLAP", "1") != "0"
+        self.dpt_fuse = _os.environ.get("CUT3R_DPT_FUSE", "1") != "0"          # head.2 + head.4 + activations in one launch
         # windows per DPT-head pass of a view (the head's convolutions at the coarse pyramid levels have few output tiles)
         self.head_chunk = max(1, int(_os.environ.get("CUT3R_HEAD_CHUNK", "28")))      # measured at 28 windows: 8 -> 4806, 14 -> 4867, 28 -> 4932 frames/s
         # LayerNorm folded into the GEMMs (round 4): the fp32 + residual projections (attn.proj, cross_attn.proj, mlp.fc2) also write an fp16
@@ -695,8 +696,9 @@ class Cut3rModel:
         out = self._up2(out, p + ".up")
         return self._conv1(out, p + ".out_conv")
 
-    def _dpt(self, p, toks16: List[torch.Tensor], B, nh, nw):
-        """toks16: 4 fp16 tensors [B*nh*nw, C_i] (NHWC token maps).  Returns fp16 [B*H*W, last_dim] features."""
+    def _dpt(self, p, toks16: List[torch.Tensor], B, nh, nw, last=True):
+        """toks16: 4 fp16 tensors [B*nh*nw, C_i] (NHWC token maps).  Returns fp16 [B*H*W, last_dim] features (last=False: the
+        input of head.2, for a caller that runs head.2 together with the output stage)."""
         a = p + ".act_postprocess"
         t = [x.view(B, nh, nw, -1) for x in toks16]
         l0 = self._convT(self._conv1(t[0], a + ".0.0"), a + ".0.1")
@@ -712,17 +714,29 @@ class Cut3rModel:
         p1 = self._fusion(p + ".scratch.refinenet1", p2, L[0])
         o = self._conv3(p1, p + ".head.0")
         o = self._up2(o, p + ".head.up")
-        o = self._conv3(o, p + ".head.2", act=2)
+        if last:
+            o = self._conv3(o, p + ".head.2", act=2)
         return o
 
+    def _dpt_fused(self, p):
+        """head.2 + head.4 + activations in one launch (CUT3R_DPT_FUSE=0: the two launches, for A/B runs)"""
+        L = self.w[p + ".head.2"]
+        return self.dpt_fuse and L.b is not None and ops.conv3x3_dpt_final_ok(L.w.shape[1] // 9, L.npad, self.w[p + ".head.4.w"])
+
     def _dpt_pts(self, p, toks16, B, nh, nw, H, W, key_pts, key_conf, res, out=None):
-        o = self._dpt(p, toks16, B, nh, nw)
+        """out = (pts [B,H,W,3], conf [B,H,W]): contiguous, or -- on the fused path only -- contiguous views a constant stride apart"""
+        fused = self._dpt_fused(p)
+        o = self._dpt(p, toks16, B, nh, nw, last=not fused)
         if out is None:
             pts = torch.empty((B, H, W, 3), dtype=F32, device=self.device)
             conf = torch.empty((B, H, W), dtype=F32, device=self.device)
         else:
             pts, conf = out
-        ops.dpt_final(o.view(B * H * W, -1), self.w[p + ".head.4.w"], self.w[p + ".head.4.b"], 0, pts, conf)
+        if fused:
+            L = self.w[p + ".head.2"]
+            ops.conv3x3_dpt_final(o, L.w, L.b, self.w[p + ".head.4.w"], self.w[p + ".head.4.b"], pts, conf)
+        else:
+            ops.dpt_final(o.view(B * H * W, -1), self.w[p + ".head.4.w"], self.w[p + ".head.4.b"], 0, pts, conf)
         if res is not None:
             res[key_pts], res[key_conf] = pts, conf
 
@@ -931,11 +945,16 @@ class Cut3rModel:
                             t = self.buf("head.view." + name, (nb, N, dim), F16)
                             t.copy_(src[c0:c1, i])
                             tk.append(t.view(nb * N, dim))
-                        pv = self.buf("head.view.pts", (nb, H, W, 3), F32)
-                        cv = self.buf("head.view.conf", (nb, H, W), F32)
-                        self._dpt_pts("downstream_head.dpt_self", tk, nb, nh, nw, H, W, None, None, None, out=(pv, cv))
-                        head_pts.view(Wn, V, H, W, 3)[c0:c1, i].copy_(pv)
-                        head_conf.view(Wn, V, H, W)[c0:c1, i].copy_(cv)
+                        pd, cd = head_pts.view(Wn, V, H, W, 3)[c0:c1, i], head_conf.view(Wn, V, H, W)[c0:c1, i]
+                        if self._dpt_fused("downstream_head.dpt_self"):
+                            # the fused output stage writes view i of windows c0..c1 in place (view stride = one window)
+                            self._dpt_pts("downstream_head.dpt_self", tk, nb, nh, nw, H, W, None, None, None, out=(pd, cd))
+                        else:
+                            pv = self.buf("head.view.pts", (nb, H, W, 3), F32)
+                            cv = self.buf("head.view.conf", (nb, H, W), F32)
+                            self._dpt_pts("downstream_head.dpt_self", tk, nb, nh, nw, H, W, None, None, None, out=(pv, cv))
+                            pd.copy_(pv)
+                            cd.copy_(cv)
             # the state ping-pong: make st[cs] hold the new state for the next view
             cs = 0 if new_state is st[0] else 1
             if return_taps:

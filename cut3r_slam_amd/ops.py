@@ -432,6 +432,38 @@ def dpt_final(x, w, b, mode, pts, conf=None):
     check(lib.cut3r_dpt_final(_p(x), P, Cin, _p(w), _p(b), mode, _p(pts), _p(conf), _stream()), "cut3r_dpt_final")
 
 
+def conv3x3_dpt_final_ok(Cin, Cout, w):
+    """the shapes cut3r_conv3x3_dpt_final serves: a 3x3 convolution Cin -> 128 (Cin a power of two >= 64) and a final weight [4, 128]"""
+    return Cout == 128 and Cin >= 64 and (Cin & (Cin - 1)) == 0 and tuple(w.shape) == (4, 128)
+
+
+def conv3x3_dpt_final(x, Wk, bias, w, b, pts, conf):
+    """3x3 / pad 1 / stride 1 convolution + ReLU (head.2), final 1x1 convolution (head.4) and the point / confidence activations in
+    ONE launch: the bits of conv3x3_nhwc(act=2) followed by dpt_final(mode 0), without the fp16 [B,H,W,128] tensor in between.
+    x fp16 [B,H,W,Cin] contiguous; Wk fp16 [128, 9*Cin]; bias fp32 [128]; w fp32 [4,128]; b fp32 [4]; pts fp32 [B,H,W,3] and
+    conf fp32 [B,H,W]: every view contiguous, any stride between views (a slice of a larger tensor)."""
+    _cuda(x, Wk, bias, w, b, pts, conf)
+    _req(x.dtype == F16 and x.dim() == 4 and x.is_contiguous(), "x must be contiguous NHWC fp16")
+    Bn, H, Wd, Cin = x.shape
+    _req(Wk.dtype == F16 and Wk.dim() == 2 and Wk.shape[1] == 9 * Cin and Wk.is_contiguous(), "Wk must be fp16 [Cout, 9*Cin]")
+    Cout = Wk.shape[0]
+    _req(w.dtype == F32 and w.dim() == 2 and w.is_contiguous() and conv3x3_dpt_final_ok(Cin, Cout, w), "conv3x3_dpt_final serves Cin = 2^k >= 64, Cout = 128, w [4,128]")
+    _req(bias is not None and bias.dtype == F32 and bias.numel() == Cout and bias.is_contiguous(), "conv3x3_dpt_final bias")
+    _req(b.dtype == F32 and b.numel() == 4 and b.is_contiguous(), "conv3x3_dpt_final b")
+    for t, shape, per_view in ((pts, (Bn, H, Wd, 3), H * Wd * 3), (conf, (Bn, H, Wd), H * Wd)):
+        _req(t.dtype == F32 and tuple(t.shape) == shape and Bn > 0 and t[0].is_contiguous() and (Bn == 1 or t.stride(0) >= per_view),
+             "conv3x3_dpt_final destinations: fp32 [B,H,W,3] / [B,H,W], contiguous views that do not overlap")
+    M = Bn * H * Wd
+    d = GemmDesc()
+    d.A, d.B, d.bias = x.data_ptr(), Wk.data_ptr(), bias.data_ptr()
+    d.act, d.out_f16, d.batch = 2, 1, 1
+    d.M, d.N, d.K, d.lda, d.ldb, d.ldc = M, Cout, 9 * Cin, Cin, 9 * Cin, Cout
+    d.conv_k, d.H, d.W, d.Cin, d.conv_stride, d.Ho, d.Wo = 3, H, Wd, Cin, 1, H, Wd
+    check(_lib.load().cut3r_conv3x3_dpt_final(C.byref(d), _p(w), _p(b), 0, _p(pts), pts.stride(0) if Bn > 1 else H * Wd * 3, _p(conf),
+                                              conf.stride(0) if Bn > 1 else H * Wd, _stream()),
+          f"cut3r_conv3x3_dpt_final M={M} K={9*Cin}")
+
+
 def postprocess_pts(raw, pos_z, pts, conf=None):
     _cuda(raw, pts, conf)
     P, nch = raw.shape

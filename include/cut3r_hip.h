@@ -153,6 +153,15 @@ int cut3r_upsample2x_nhwc(const void* in, void* out, int B, int H, int W, int C,
  * in: fp16 [P,Cin]; w: fp32 [nout,Cin]; b: fp32 [nout] */
 int cut3r_dpt_final(const void* in, int P, int Cin, const float* w, const float* b, int mode, float* pts, float* conf,
                     void* stream);
+/* head.2 + head.4 + activations in one launch: the 3x3 convolution described by `d` exactly as for cut3r_gemm_f16 (conv_k = 3, stride 1,
+ * Cin a power of two >= 64, N = 128 output channels, bias, act = 2 (ReLU), out_f16 = 1, no residual, batch 1; d->C is ignored: the fp16
+ * output is never written), then on the fp16-rounded output the final 1x1 convolution w fp32 [4,128] (16-B aligned), b fp32 [4] and the
+ * mode 0 activations of cut3r_dpt_final, in the convolution's epilogue.  Pixel q of view v (v = row / (Ho*Wo)) goes to
+ * pts + v * pts_view_stride + 3 q and conf + v * conf_view_stride + q (element strides), so a view can be written straight into a slice
+ * of a larger tensor.  Same bits as cut3r_gemm_f16 followed by cut3r_dpt_final.  Any other problem, mode 1 or a destination that is not
+ * 4-byte aligned is refused with CUT3R_ERR_ARG before the launch. */
+int cut3r_conv3x3_dpt_final(const cut3r_gemm_desc* d, const float* w, const float* b, int mode, float* pts, long long pts_view_stride,
+                            float* conf, long long conf_view_stride, void* stream);
 /* postprocess on raw fp32 [P,4|3] maps (linear head path, pos_z option: linear_head.py:316) */
 int cut3r_postprocess_pts(const float* raw, int P, int nch, int pos_z, float* pts, float* conf, void* stream);
 /* camera pose activation (heads/postprocess.py:30-63): in fp32 [B,7] -> out [B,7] (t*expm1|t|/|t|, unit quat w>=0) */
