@@ -17,6 +17,7 @@
 // attn_kernel is this structure (all head widths; the only form for 16, 32 and 128); attn_pipe_kernel below is the software-pipelined
 // LDS-DMA form that serves the 48- and 64-wide heads by default.
 #include <atomic>
+#include <cmath>
 #include <cstdlib>
 #include <type_traits>
 #include "common.h"
@@ -701,28 +702,38 @@ __global__ __launch_bounds__(64 * NW, (QB == 1 ? 2 : 1)) void attn_pipe_kernel(c
 
 std::atomic<int> g_attn_variant{[] { const char* e = getenv("CUT3R_ATTN_PIPE"); return e ? atoi(e) : 1; }()};
 
+// cut3r_attention_kernel_for's rule with the two tuning knobs read once: the ONE place that decides which instance serves a problem
+int attn_instance(int B, int H, int Nq, int D) {
+    static const long long nw4_min = [] { const char* e = getenv("CUT3R_ATTN_NW4_MIN"); return e ? atoll(e) : 384LL; }();
+    if (D != 16 && D != 32 && D != 48 && D != 64 && D != 128) return 0;
+    // the pipelined form (attn_pipe_kernel) is the default for the network's head widths at every size: measured round 4
+    // (profiles/r04/attn_pipe_bench.txt) 665 vs 624 TF/s on the encoder shape, 521-533 vs 476-511 on the decoder's 64-wide heads,
+    // 444-465 vs 444-447 on its 48-wide ones, and 13.4 vs 19.1 us for ONE window's launch.  Same bits as attn_kernel, so the choice
+    // is free; cut3r_attention_variant(0) / CUT3R_ATTN_PIPE=0 selects attn_kernel (tests, A/B runs)
+    if ((D == 48 || D == 64) && g_attn_variant.load(std::memory_order_relaxed) != 0) return 104;
+    const long long blocks128 = (long long)B * H * ((Nq + 127) / 128);
+    return (blocks128 >= nw4_min || D >= 128) ? 4 : 2;
+}
+
 template <int D>
 int launch_attn(const AttnArgs& a, int B, int H, hipStream_t s) {
-    const long long blocks128 = (long long)B * H * ((a.Nq + 127) / 128);
-    static const long long nw4_min = [] { const char* e = getenv("CUT3R_ATTN_NW4_MIN"); return e ? atoll(e) : 384LL; }();
+    const int inst = attn_instance(B, H, a.Nq, D);
     if constexpr (D == 48 || D == 64) {
-        // the pipelined form (attn_pipe_kernel) is the default for the network's head widths at every size: measured round 4
-        // (profiles/r04/attn_pipe_bench.txt) 665 vs 624 TF/s on the encoder shape, 521-533 vs 476-511 on the decoder's 64-wide heads,
-        // 444-465 vs 444-447 on its 48-wide ones, and 13.4 vs 19.1 us for ONE window's launch.  Same bits as attn_kernel, so the choice
-        // is free; cut3r_attention_variant(0) / CUT3R_ATTN_PIPE=0 selects attn_kernel (tests, A/B runs)
-        if (g_attn_variant.load(std::memory_order_relaxed) != 0) {
+        if (inst == 104) {
             const int nblk = (a.Nq + 127) / 128, HB = H * B;
             dim3 grid((unsigned)(((HB + 7) / 8) * 8 * nblk));
             hipLaunchKernelGGL((attn_pipe_kernel<D, 1, 4, 4>), grid, dim3(256), 0, s, a, nblk, HB, H);
             return cut3r_check_launch();
         }
     }
-    if (blocks128 >= nw4_min || D >= 128) {
+    if (inst == 4) {
         dim3 grid((a.Nq + 127) / 128, H, B);
         hipLaunchKernelGGL((attn_kernel<D, 4>), grid, dim3(256), 0, s, a);
-    } else {
+    } else if (inst == 2) {
         dim3 grid((a.Nq + 63) / 64, H, B);
         hipLaunchKernelGGL((attn_kernel<D, 2>), grid, dim3(128), 0, s, a);
+    } else {
+        return CUT3R_ERR_ARG;
     }
     return cut3r_check_launch();
 }
@@ -734,6 +745,11 @@ extern "C" int cut3r_attention_variant(int v) {
     return g_attn_variant.exchange(v ? 1 : 0, std::memory_order_relaxed);
 }
 
+extern "C" int cut3r_attention_kernel_for(int B, int H, int Nq, int D) {
+    if (B <= 0 || H <= 0 || Nq <= 0) return 0;
+    return attn_instance(B, H, Nq, D);
+}
+
 extern "C" int cut3r_attention_f16(const void* q, const void* k, const void* v, void* out, int B, int H, int Nq, int Nk, int D,
                                    long long q_sb, long long q_sn, long long k_sb, long long k_sn, long long v_sb, long long v_sn,
                                    long long o_sb, long long o_sn, float scale, void* stream) {
@@ -742,6 +758,9 @@ extern "C" int cut3r_attention_f16(const void* q, const void* k, const void* v, 
     if ((uintptr_t)out & 7) return CUT3R_ERR_ARG;
     if ((q_sn | k_sn | v_sn | q_sb | k_sb | v_sb) & 7) return CUT3R_ERR_ARG;   // 16-B vector loads
     if ((o_sn | o_sb) & 3) return CUT3R_ERR_ARG;
+    // both kernels take a tile's maximum over the RAW scores and scale it afterwards, which is the maximum of the scaled scores only for
+    // scale > 0; a NaN or infinite scale has no softmax at all
+    if (!(scale > 0.f) || !std::isfinite(scale)) return CUT3R_ERR_ARG;
     AttnArgs a;
     a.q = (const h16*)q; a.k = (const h16*)k; a.v = (const h16*)v; a.o = (h16*)out;
     a.Nq = Nq; a.Nk = Nk;

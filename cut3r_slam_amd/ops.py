@@ -356,6 +356,11 @@ def gemv(X, W, out, bias=None, act=0, res=None, silu_in=False):
 
 
 # ------------------------------------------------------------------------------------------------ attention
+def attention_kernel_for(B, H, Nq, D):
+    """The kernel instance `attention` launches for this problem: 100 * pipelined + waves per workgroup (104, 4 or 2; 0 = none)."""
+    return _lib.load().cut3r_attention_kernel_for(int(B), int(H), int(Nq), int(D))
+
+
 def attention(q, k, v, out, scale):
     """q [B,Nq,H,D], k/v [B,Nk,H,D] fp16 views with unit d-stride and head stride D; out [B,Nq,H,D] fp16."""
     _cuda(q, k, v, out)
@@ -365,6 +370,7 @@ def attention(q, k, v, out, scale):
         _req(t.dtype == F16 and t.dim() == 4 and t.stride(3) == 1 and t.stride(2) == D, "attention operands: fp16 (B,N,H,D) views")
     _req(k.shape == (B, Nk, H, D) and v.shape == (B, Nk, H, D) and out.shape == (B, Nq, H, D), "attention shapes")
     _req(D in (16, 32, 48, 64, 128), f"unsupported head dim {D}")
+    _req(0.0 < float(scale) < float("inf"), f"attention scale must be finite and > 0, got {scale}")
     lib = _lib.load()
     check(lib.cut3r_attention_f16(_p(q), _p(k), _p(v), _p(out), B, H, Nq, Nk, D, q.stride(0), q.stride(1), k.stride(0),
                                   k.stride(1), v.stride(0), v.stride(1), out.stride(0), out.stride(1), float(scale),

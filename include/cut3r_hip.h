@@ -122,7 +122,7 @@ int cut3r_gemv_f16w(const float* X, int ldx, const void* W, int ldw, const float
  * replaces F.scaled_dot_product_attention(q,k,v, scale) (no mask, p=0) at croco/models/blocks.py:139-145 and
  * dust3r/blocks.py:123-129,233-239.  fp16 q/k/v, fp32 online softmax, fp16 out.
  * Element (b,n,h,d) of q lives at q + b*q_sb + n*q_sn + h*D + d (same for k,v with their strides; out likewise).
- * D in {16,32,48,64,128}. */
+ * D in {16,32,48,64,128}.  scale must be finite and > 0 (anything else: bad argument, nothing is launched). */
 int cut3r_attention_f16(const void* q, const void* k, const void* v, void* out, int B, int H, int Nq, int Nk, int D,
                         long long q_sb, long long q_sn, long long k_sb, long long k_sn, long long v_sb, long long v_sn,
                         long long o_sb, long long o_sn, float scale, void* stream);
@@ -131,6 +131,11 @@ int cut3r_attention_f16(const void* q, const void* k, const void* v, void* out, 
  * Both give the same bits (tests/test_kernels_gpu.py); the switch exists for that test and for A/B timing.  v < 0 only queries.
  * Returns the previous setting.  (No reference counterpart: a tuning knob of this library.) */
 int cut3r_attention_variant(int v);
+/* the kernel instance cut3r_attention_f16 launches for this problem, as 100 * pipelined + waves per workgroup: 104 the pipelined
+ * kernel (48- and 64-wide heads while cut3r_attention_variant is 1), 4 or 2 the register-staged kernel with 128 or 64 query rows per
+ * workgroup (4 when B * H * ceil(Nq / 128) >= 384 or D = 128).  0: no instance (unsupported D, empty problem).  Host only, launches
+ * nothing; the launcher itself asks this function, so the rule exists once.  (No reference counterpart.) */
+int cut3r_attention_kernel_for(int B, int H, int Nq, int D);
 
 /* ---- elementwise / layout helpers of the ViT path -------------------------------------------------------------- */
 /* PatchEmbed conv 16x16/s16 as im2col (src/dust3r/patch_embed.py:18-32): img fp32 [B,C,H,W] -> fp16 [B*(H/P)*(W/P), C*P*P],
