@@ -17,11 +17,11 @@ head runs once per window over all views (it does not feed the recurrence), and 
 from __future__ import annotations
 
 import gc
-
 import math
+import os
 import re
-from dataclasses import dataclass
-from typing import Dict, List, Optional
+from dataclasses import dataclass, field
+from typing import Dict, List, NamedTuple, Optional
 
 import torch
 
@@ -29,6 +29,14 @@ from . import ops
 from .config import Cut3rConfig, production_config, state_dict_schema
 
 F16, F32 = torch.float16, torch.float32
+
+
+def _env_flag(name: str, default: bool) -> bool:
+    return os.environ.get(name, "1" if default else "0") != "0"
+
+
+def _env_int(name: str, default: int) -> int:
+    return int(os.environ.get(name, str(default)))
 
 
 @dataclass
@@ -55,6 +63,53 @@ class _Lin:
         self.k = self.w.shape[1]
 
 
+class _Stream(NamedTuple):
+    """A residual stream of the decoder with its companions of the LayerNorm fold: the GEMM that fills `x` writes them beside it"""
+    x: torch.Tensor                          # fp32 [M,C]
+    x16: Optional[torch.Tensor] = None       # fp16 copy of x
+    st: Optional[torch.Tensor] = None        # slab statistics of its rows, fp32 [C/64, M, 2]
+
+
+@dataclass
+class _Block:
+    """One decoder block at work: weights `p`.*, buffers `tag`.*, x fp32 [B*Nx,C] (queries, residual) and y fp32 [B*Ny,C] (keys / values)
+    -> out fp32 [B*Nx,C]; B = independent sequences (tracking windows batched through the decoder).  Built by Cut3rModel._block, which
+    fills in every field; read by Cut3rModel._dec_layer."""
+    p: str
+    tag: str
+    x: _Stream
+    y: _Stream
+    out: _Stream
+    xpos: Optional[torch.Tensor]             # int64 [B,Nx,2] | None (pose memory: no positions)
+    ypos: Optional[torch.Tensor]
+    heads: int
+    B: int
+    pre_ln: bool = False                     # norm1(x) and norm_y(y) are already in `ln16` / `y16` (_dual_norms)
+    # derived sizes
+    C: int = field(init=False)
+    Nx: int = field(init=False)
+    Ny: int = field(init=False)
+    D: int = field(init=False)               # head width
+    # LayerNorms that run inside the projection behind them (decided in _block)
+    fold_x: bool = field(init=False, default=False)        # norm1 inside qkv
+    fold_y: bool = field(init=False, default=False)        # norm_y inside projk|projv
+    fold_o: bool = field(init=False, default=False)        # norm2 inside projq, norm3 inside fc1
+    emit: Optional[tuple] = field(init=False, default=None)     # (stats, fp16 copy) of `out` the three residual projections write, when fold_o
+    # work buffers `<tag>.<field>`, fp16
+    ln16: Optional[torch.Tensor] = field(init=False, default=None)   # [B*Nx,C] norm1 / norm2 / norm3 of the x side
+    y16: Optional[torch.Tensor] = field(init=False, default=None)    # [B*Ny,C] norm_y(y)
+    qkv: Optional[torch.Tensor] = field(init=False, default=None)    # [B*Nx,3C]
+    attn: Optional[torch.Tensor] = field(init=False, default=None)   # [B,Nx,heads,D] self-attention output
+    q: Optional[torch.Tensor] = field(init=False, default=None)      # [B,Nx,heads,D] cross-attention queries
+    kv: Optional[torch.Tensor] = field(init=False, default=None)     # [B*Ny,2C] cross-attention keys | values
+    cattn: Optional[torch.Tensor] = field(init=False, default=None)  # [B,Nx,heads,D] cross-attention output
+    mlp_h: Optional[torch.Tensor] = field(init=False, default=None)  # [B*Nx,hidden]
+
+    def __post_init__(self):
+        self.C = self.x.x.shape[1]
+        self.Nx, self.Ny, self.D = self.x.x.shape[0] // self.B, self.y.x.shape[0] // self.B, self.C // self.heads
+
+
 class Cut3rModel:
     def __init__(self, cfg: Cut3rConfig, state_dict: Dict[str, torch.Tensor], device="cuda:0", minimal: bool = False):
         """minimal=True computes only what the SLAM trackers consume (pts3d_in_self_view, conf_self, camera_pose:
@@ -71,53 +126,23 @@ class Cut3rModel:
                 raise ValueError(f"{k}: shape {tuple(state_dict[k].shape)} != schema {tuple(shp)}")
         self._buf: Dict[tuple, torch.Tensor] = {}
         self._graphs: Dict[tuple, tuple] = {}
-        import os as _os
-        self.use_graphs = _os.environ.get("CUT3R_GRAPHS", "1") != "0"
-        # the state-side and image-side decoder blocks of a layer are independent (both read the previous layer's
-        # pair, model.py:669-692): issue them on two streams so the captured graph has two parallel branches
-        self.dual_stream = _os.environ.get("CUT3R_DUAL_STREAM", "1") != "0"
-        self.dual_ln = _os.environ.get("CUT3R_DUAL_LN", "1") != "0"            # shared-statistics LayerNorm of the decoder inputs
-        # the seven projections of a decoder layer as pair launches (state + image problem in one grid: cut3r_gemm_f16_pair).
-        # OFF by default: measured -5 % end to end (97.4 -> 102.8 ms per 400-frame step, same box, interleaved runs): the pair
-        # launches are 30-40 % faster than the two launches they replace, but they join the two blocks at every projection, and
-        # the step loses the overlap of one block's MFMA-bound GEMMs with the other block's VALU-bound attention / LayerNorm
-        self.pair_gemm = _os.environ.get("CUT3R_PAIR_GEMM", "0") != "0"
-        # The one-window schedule (round 4) was measured with a layer as pair launches on the 64 x 64 pair kernels (`_dec_layer_pair`, with the
-        # LayerNorm fold and the fused RoPE): 24.5 vs 23.6 ms per window -- slower as well.  A one-window launch costs ~6.5 us before its
-        # first K-tile whatever its size (a + b K fit of the kernel trace), so fewer, fuller launches only help if the chain gets shorter,
-        # and the pair form joins the two blocks seven times per layer.  `pair_rows` > 0 turns the pair form on below that many rows.
-        self.pair_rows = int(_os.environ.get("CUT3R_PAIR_ROWS", "0"))
-        # RoPE in the q/k projection epilogue: 0 off, 1 heads of 64 (default), 2 also heads of 48.  Bit-identical to the stand-alone
-        # kernel.  Through the run-time epilogue of round 1 it lost 2.5 % end to end; as a compile-time epilogue of the 256x256 kernel
-        # (a wave's 64-column slab is one head) it gains 1.0 % (5703 -> 5761 frames/s, interleaved runs); 48-wide heads straddle the
-        # slabs and keep the stand-alone launch
-        self.fused_rope = int(_os.environ.get("CUT3R_FUSED_ROPE", "1"))      # RoPE in the q/k projection epilogue (D = 64)
-        self.rope48_rows = int(_os.environ.get("CUT3R_ROPE48_ROWS", "0"))     # 48-wide heads: fused below this many GEMM rows (0: never -- measured round 4 at one window: 28.4 vs 23.7 ms per window, the 128 x 192 tile puts 72 workgroups on 256 CUs)
-        # DPT head of view i (all windows) on a third stream while the recurrent decoder works on view i+1: the decoder's
-        # mid-size kernels leave matrix and memory pipes idle that the head's large convolutions can use
-        self.head_overlap = _os.environ.get("CUT3R_HEAD_OVERLAP", "1") != "0"
-        self.dpt_fuse = _os.environ.get("CUT3R_DPT_FUSE", "1") != "0"          # head.2 + head.4 + activations in one launch
-        # windows per DPT-head pass of a view (the head's convolutions at the coarse pyramid levels have few output tiles)
-        self.head_chunk = max(1, int(_os.environ.get("CUT3R_HEAD_CHUNK", "28")))      # measured at 28 windows: 8 -> 4806, 14 -> 4867, 28 -> 4932 frames/s
-        # LayerNorm folded into the GEMMs (round 4): the fp32 + residual projections (attn.proj, cross_attn.proj, mlp.fc2) also write an fp16
-        # copy of the residual stream and its per-row slab statistics; qkv / projq / projk|projv / fc1 read that copy through gamma-folded
-        # weights and normalise in their epilogue (include/cut3r_hip.h, cut3r_gemm_desc).  The LayerNorm launches in front of them
-        # disappear, except where the input has no producer GEMM (first encoder block, first decoder layer of a view, pose memory).
-        # Economics, measured (tools/bench_lnfold.py, bench probe passes): the producers pay for the extra fp16 stream
-        # (+7.5 us per tile round at N = 1024, HBM), the consumers for the row parameters (+1.2 us per tile).  Per DECODER block (28 windows)
-        # that is 35 us against 58 us of LayerNorm launches -- a net win, and at one window every removed launch is latency (24.4 -> 23.6 ms
-        # per window); per ENCODER block 200 us against 2 x 109 us -- nothing, while the encoder GEMMs (the dominant kernel) run 5-6 % slower.
-        # So: 1 (default) = decoder only, 2 = encoder as well, 0 = off.
-        self.ln_fold = int(_os.environ.get("CUT3R_LN_FOLD", "1"))
+        # schedule knobs (CUT3R_*): read once here, plain attributes afterwards (tests and tools set them on a constructed model)
+        self.use_graphs = _env_flag("CUT3R_GRAPHS", True)            # hipGraph capture / replay per input signature (_graphed)
+        self.dual_stream = _env_flag("CUT3R_DUAL_STREAM", True)      # state-side and image-side block of a layer on two capture streams
+        self.dual_ln = _env_flag("CUT3R_DUAL_LN", True)              # shared-statistics LayerNorm of the decoder inputs (_dual_norms)
+        self.pair_gemm = _env_flag("CUT3R_PAIR_GEMM", False)         # every decoder layer as pair launches: -5 % end to end ("Pair GEMM")
+        self.pair_rows = _env_int("CUT3R_PAIR_ROWS", 0)              # pair launches below this many rows: slower at one window too (one-window schedule)
+        self.fused_rope = _env_int("CUT3R_FUSED_ROPE", 1)            # RoPE in the q / k projection epilogue: 0 off, 1 heads of 64, 2 also heads of 48 ("RoPE")
+        self.rope48_rows = _env_int("CUT3R_ROPE48_ROWS", 0)          # 48-wide heads: fused below this many GEMM rows, 0 never (one-window schedule)
+        self.head_overlap = _env_flag("CUT3R_HEAD_OVERLAP", True)    # DPT head of view i on a third stream beside the decoder of view i+1
+        self.dpt_fuse = _env_flag("CUT3R_DPT_FUSE", True)            # head.2 + head.4 + activations in one launch
+        self.head_chunk = max(1, _env_int("CUT3R_HEAD_CHUNK", 28))   # windows per DPT-head pass of a view ("DPT head chunk")
+        # LayerNorm folded into the GEMMs: 0 off, 1 decoder only, 2 encoder as well ("LayerNorm fold").  The folded panels
+        # are built in _prep, so the value can be lowered on a constructed model but not raised
+        self.ln_fold = _env_int("CUT3R_LN_FOLD", 1)
         self._head_stream = None
         self._side = None
         self._head_side = None
-        # one-window schedule: key / value branches of a decoder layer on their own capture streams (CUT3R_KV_FORK; rows <= CUT3R_KV_FORK_ROWS).
-        # OFF: measured round 4 (tools/bench_wb1.py, profiles/r04/kvfork.log) 28.2 ms per window against 23.5 ms without -- every edge between
-        # two capture streams becomes a barrier packet pair in the hipGraph and 4 more of them per layer cost more than the overlap returns
-        self.kv_fork = _os.environ.get("CUT3R_KV_FORK", "0") != "0"
-        self.kv_fork_rows = int(_os.environ.get("CUT3R_KV_FORK_ROWS", "2048"))
-        self._kv_streams = None
         self._prep(state_dict)
 
     # ------------------------------------------------------------------ reference-compatible constructors
@@ -130,7 +155,6 @@ class Cut3rModel:
         """Load a reference checkpoint (ckpt['model'] = state_dict; ckpt['args'].model = constructor string,
         model.py:72-92).  Only weights_only loading is used; the constructor string is parsed, never eval'd."""
         import argparse
-        import os
         if not os.path.isfile(path):
             raise FileNotFoundError(f"{path}: no checkpoint (this runtime never fetches from a hub)")
         with torch.serialization.safe_globals([argparse.Namespace]):
@@ -283,17 +307,36 @@ class Cut3rModel:
         return t
 
     # ------------------------------------------------------------------ primitives
-    def _linear(self, x16, name, out, act=0, res1=None, res2=None, skinny=False, rope=None, ln=None, emit=None):
-        """skinny: the operand has ONE row per independent sequence (pose token of a tracking window): weight-streaming
-        kernel whose per-row result does not depend on how many windows are batched.
-        rope = (positions [B,N,2], cols): RoPE of the first `cols` output columns fused into the GEMM epilogue.
-        ln = slab statistics of the rows of `x16` (then x16 is the fp16 copy of the UN-normalised residual stream and the LayerNorm in front
-        of this Linear runs inside its epilogue through the folded panel `name@ln`); emit = (stats, x16) this GEMM writes for the next one."""
+    def _panel(self, name, rope=None, ln=None):
+        """the weight panel of Linear `name` with the rope / ln arguments as ops.linear and ops.linear_pair take them:
+        rope = (positions [B,N,2], cols, head width) -> + the RoPE base; ln = slab statistics -> the folded panel `name@ln`, its column sums, eps"""
         L = self.w[name + "@ln"] if ln is not None else self.w[name]
         if rope is not None:
             rope = (rope[0], rope[1], self.cfg.rope_freq, rope[2])
-        return ops.linear(x16, L.w, out, L.b, act, res1, res2, tile=16 if skinny else 0, rope=rope,
-                          ln=(ln, L.c, self.cfg.ln_eps) if ln is not None else None, emit=emit)
+        if ln is not None:
+            ln = (ln, L.c, self.cfg.ln_eps)
+        return L, rope, ln
+
+    def _linear(self, x16, name, out, act=0, res1=None, res2=None, skinny=False, rope=None, ln=None, emit=None):
+        """skinny: the operand has ONE row per independent sequence (pose token of a tracking window): weight-streaming
+        kernel whose per-row result does not depend on how many windows are batched.
+        rope = (positions [B,N,2], cols, head width): RoPE of the first `cols` output columns fused into the GEMM epilogue.
+        ln = slab statistics of the rows of `x16` (then x16 is the fp16 copy of the UN-normalised residual stream and the LayerNorm in front
+        of this Linear runs inside its epilogue through the folded panel `name@ln`); emit = (stats, x16) this GEMM writes for the next one."""
+        L, rope, ln = self._panel(name, rope, ln)
+        return ops.linear(x16, L.w, out, L.b, act, res1, res2, tile=16 if skinny else 0, rope=rope, ln=ln, emit=emit)
+
+    def _project(self, probs, act=0):
+        """one projection step of a decoder layer, probs = the keyword arguments of `_linear` per block: one block -> ops.linear; the state-side
+        and the image-side block -> both problems in ONE grid (ops.linear_pair; same rows, bit for bit)"""
+        if len(probs) == 1:
+            return self._linear(act=act, **probs[0])
+
+        def prob(x16, name, out, res1=None, skinny=False, rope=None, ln=None, emit=None):
+            assert not skinny, "the pair kernels have no one-row-per-sequence form"
+            L, rope, ln = self._panel(name, rope, ln)
+            return (x16, L.w, out, L.b, res1, dict(rope=rope, ln=ln, emit=emit))
+        ops.linear_pair(prob(**probs[0]), prob(**probs[1]), act)
 
     def _folded(self, name):
         return self.ln_fold and (name + "@ln") in self.w
@@ -302,21 +345,6 @@ class Cut3rModel:
         """the fp16 copy + slab statistics that belong to the fp32 residual buffer `x` ([M,C], C % 64 == 0): (x16, stats [C/64, M, 2])"""
         M, Cc = x.shape
         return self.buf(tag + ".x16", (M, Cc), F16), self.buf(tag + ".xst", (Cc // 64, M, 2), F32)
-
-    def _linear_pair(self, x0, name0, out0, x1, name1, out1, act=0, res0=None, res1=None, ex0=None, ex1=None):
-        """the same projection of the state-side and the image-side decoder block in ONE launch (ops.linear_pair); ex = per-problem extras:
-        rope = (pos, cols, D) fused RoPE, ln = slab statistics (the operand is then the un-normalised fp16 copy, folded panel `name@ln`),
-        emit = (stats, fp16 copy) the projection writes"""
-        def prob(x, name, out, res, ex):
-            ex = dict(ex or {})
-            L = self.w[name + "@ln"] if ex.get("ln") is not None else self.w[name]
-            if ex.get("ln") is not None:
-                ex["ln"] = (ex["ln"], L.c, self.cfg.ln_eps)
-            if ex.get("rope") is not None:
-                r = ex["rope"]
-                ex["rope"] = (r[0], r[1], self.cfg.rope_freq, r[2])
-            return (x, L.w, out, L.b, res, {k: v for k, v in ex.items() if v is not None})
-        ops.linear_pair(prob(x0, name0, out0, res0, ex0), prob(x1, name1, out1, res1, ex1), act)
 
     def _fuse_rope(self, pos, D, rows):
         """the GEMM-fused RoPE covers head dimension 64 with one position row per GEMM row; 48-wide heads (the state side of the decoder)
@@ -349,12 +377,12 @@ class Cut3rModel:
         ops.attention(q, k, v, a, D ** -0.5)
         self._linear(a.view(B * N, Cc), p + ".proj", out, res1=res, skinny=sk, emit=emit)
 
-    def _mlp(self, tag, x_ln16, p, out, res, skinny=False, ln=None, emit=None):
+    def _mlp(self, tag, x_ln16, p, out, res, ln=None, emit=None):
         M = x_ln16.shape[0]
         hdim = self.w[p + ".fc1"].npad
         h = self.buf(tag + ".mlp_h", (M, hdim), F16)
-        self._linear(x_ln16, p + ".fc1", h, act=1, skinny=skinny, ln=ln)
-        self._linear(h, p + ".fc2", out, res1=res, skinny=skinny, emit=emit)
+        self._linear(x_ln16, p + ".fc1", h, act=1, ln=ln)
+        self._linear(h, p + ".fc2", out, res1=res, emit=emit)
 
     # ------------------------------------------------------------------ encoder
     def _encode(self, img: torch.Tensor):
@@ -446,182 +474,107 @@ class Cut3rModel:
             feat, _, pos = self._encode(img)
         return feat, pos, im_shape
 
-    # ------------------------------------------------------------------ decoder block
-    def _dec_block(self, tag, p, x, y, xpos, ypos, heads, out, B=1, pre_ln=False, xs=None, ys=None, os_=None, kv_stream=None, kv_only=False):
-        """x fp32 [B*Nx,C], y fp32 [B*Ny,C] -> out fp32 [B*Nx,C]   (dust3r/blocks.py:292-297).  B = independent
-        sequences (tracking windows batched through the decoder).  pre_ln: norm1(x) and norm_y(y) are already in this
-        block's `.ln16` / `.y16` buffers (`_dual_norms`).
-        LayerNorm fold: xs / ys = (fp16 copy, slab statistics) of x / y as the GEMMs that produced them wrote them (norm1 and norm_y then run
-        inside the qkv / projk|projv epilogues); os_ = the pair that belongs to `out`: the three residual projections of this block write
-        it (norm2 -> projq and norm3 -> fc1 read it here, the next layer's norm1 / norm_y read what fc2 leaves)."""
-        Cc = x.shape[1]
-        Nx, Ny = x.shape[0] // B, y.shape[0] // B
-        D = Cc // heads
-        ln16 = self.buf(tag + ".ln16", (B * Nx, Cc), F16)
-        y16 = self.buf(tag + ".y16", (B * Ny, Cc), F16)
-        kv = self.buf(tag + ".kv", (B * Ny, 2 * Cc), F16)
-        kv4 = kv.view(B, Ny, 2, heads, D)
-        k, v = kv4[:, :, 0], kv4[:, :, 1]
-        if os_ is not None and not (Nx > 1 and self._folded(p + ".mlp.fc1")):
-            os_ = None
-        em = (os_[1], os_[0]) if os_ is not None else None          # (stats, fp16 copy) the residual projections write
-        if xs is not None and not (Nx > 1 and self._folded(p + ".attn.qkv")):
-            xs = None
-        if ys is not None and not (Ny > 1 and self._folded(p + ".cross_attn.projkv")):
-            ys = None
+    # ------------------------------------------------------------------ decoder layer
+    def _block(self, p, tag, x, y, out, xpos, ypos, heads, B=1, fresh=False, pre_ln=False):
+        """One decoder block as `_dec_layer` takes it, with its work buffers `<tag>.*` and -- here and nowhere else -- which of its LayerNorms
+        run folded into the projection behind them: the fold is on, the panel `name@ln` exists, the stream carries valid companions and the
+        operand has more than one row per sequence (the skinny kernel has no folded form).  fresh: the companions of x and y were written
+        by the GEMMs that filled them (those of `out` are written by this block itself); pre_ln: see _Block."""
+        s = _Block(p, tag, x, y, out, xpos, ypos, heads, B, pre_ln)
+        C, Nx, Ny, D = s.C, s.Nx, s.Ny, s.D
+        can = lambda t, n, name: bool(t.x16 is not None and n > 1 and self._folded(p + name))
+        s.fold_x = fresh and can(x, Nx, ".attn.qkv")                   # norm1 inside qkv
+        s.fold_y = fresh and can(y, Ny, ".cross_attn.projkv")          # norm_y inside projk|projv
+        s.fold_o = can(out, Nx, ".mlp.fc1")                            # norm2 inside projq, norm3 inside fc1
+        s.emit = (out.st, out.x16) if s.fold_o else None               # (stats, fp16 copy) the three residual projections write
+        s.ln16 = self.buf(tag + ".ln16", (B * Nx, C), F16)
+        s.y16 = self.buf(tag + ".y16", (B * Ny, C), F16)
+        s.qkv = self.buf(tag + ".qkv", (B * Nx, 3 * C), F16)
+        s.attn = self.buf(tag + ".attn", (B, Nx, heads, D), F16)
+        s.q = self.buf(tag + ".q", (B, Nx, heads, D), F16)
+        s.kv = self.buf(tag + ".kv", (B * Ny, 2 * C), F16)
+        s.cattn = self.buf(tag + ".cattn", (B, Nx, heads, D), F16)
+        s.mlp_h = self.buf(tag + ".mlp_h", (B * Nx, self.w[p + ".mlp.fc1"].npad), F16)
+        return s
 
-        def kv_branch():          # depends only on y (the other stream's previous layer): norm_y -> projk|projv -> RoPE(k)
-            fuse_k = Ny > 1 and self._fuse_rope(ypos, D, B * Ny)
-            if ys is not None:
-                self._linear(ys[0], p + ".cross_attn.projkv", kv, rope=(ypos, Cc, D) if fuse_k else None, ln=ys[1])
-            else:
-                if not pre_ln:
-                    self._ln(y, p + ".norm_y", out16=y16)
-                self._linear(y16, p + ".cross_attn.projkv", kv, skinny=(Ny == 1), rope=(ypos, Cc, D) if fuse_k else None)
-            if ypos is not None and not fuse_k:
-                self._rope(k, ypos)
+    def _pair_carries(self, rows):
+        """What the pair launches may carry: below `pair_rows` rows (the one-window schedule) they run on the 64 x 64 pair kernels, which take
+        the LayerNorm fold and the fused RoPE of 64-wide heads; a forced pair form (`pair_gemm`) on a larger batch runs the plain 128 / 256
+        pair kernels -- no fold, no fused RoPE, LayerNorm and RoPE launches instead.  rows = the largest operand of the layer."""
+        return rows <= self.pair_rows
 
-        if kv_only:               # the key / value branch alone (it depends on y only): run by the caller on its own capture stream
-            kv_branch()
-            return None
-        if xs is not None:
-            self._self_attn(tag, xs[0], B, Nx, heads, xpos, p + ".attn", out, x, ln=xs[1], emit=em)
-        else:
-            if not pre_ln:
-                self._ln(x, p + ".norm1", out16=ln16)
-            self._self_attn(tag, ln16, B, Nx, heads, xpos, p + ".attn", out, x, emit=em)
-        q = self.buf(tag + ".q", (B, Nx, heads, D), F16)
-        fuse_q = Nx > 1 and self._fuse_rope(xpos, D, B * Nx)
-        if os_ is not None:
-            self._linear(os_[0], p + ".cross_attn.projq", q.view(B * Nx, Cc), rope=(xpos, Cc, D) if fuse_q else None, ln=os_[1])
-        else:
-            self._ln(out, p + ".norm2", out16=ln16)
-            self._linear(ln16, p + ".cross_attn.projq", q.view(B * Nx, Cc), skinny=(Nx == 1), rope=(xpos, Cc, D) if fuse_q else None)
-        if xpos is not None and not fuse_q:
-            self._rope(q, xpos)
-        if kv_stream is not None:
-            torch.cuda.current_stream().wait_stream(kv_stream)      # the branch ran beside the self-attention half (forked by the caller)
-        else:
-            kv_branch()      # (forking it from INSIDE this block's stream was tried: nested forks crash hipGraph capture_end on ROCm 7.2)
-        a = self.buf(tag + ".cattn", (B, Nx, heads, D), F16)
-        ops.attention(q, k, v, a, D ** -0.5)
-        self._linear(a.view(B * Nx, Cc), p + ".cross_attn.proj", out, res1=out, skinny=(Nx == 1), emit=em)
-        if os_ is not None:
-            self._mlp(tag, os_[0], p + ".mlp", out, out, ln=os_[1], emit=em)
-        else:
-            self._ln(out, p + ".norm3", out16=ln16)
-            self._mlp(tag, ln16, p + ".mlp", out, out, skinny=(Nx == 1))
-        return out
+    def _dec_layer(self, blocks, fork=False):
+        """The decoder block (dust3r/blocks.py:292-297: x += attn(norm1 x); x += cross_attn(norm2 x, norm_y y); x += mlp(norm3 x)) for ONE block,
+        or for the state-side and the image-side block of a layer together (model.py:669-692: both read the previous layer's pair, so they
+        are independent).  Together, each of the seven projections is one pair launch (`_project`) while LayerNorm, RoPE and attention stay
+        per block (different token counts and head widths) -- under graph capture with `fork` on the two capture streams.  Same kernels, same
+        row arithmetic: the results do not depend on the form."""
+        pair = len(blocks) == 2
+        assert not pair or all(s.Nx > 1 and s.Ny > 1 for s in blocks), "pair launches need more than one row per sequence"
+        carry = pair and self._pair_carries(max(s.B * max(s.Nx, s.Ny) for s in blocks))
+        assert not pair or carry or not any(s.fold_x or s.fold_y or s.fold_o for s in blocks), "the plain pair kernels take no LayerNorm fold"
+        # RoPE of q / k in the projection's epilogue (else a launch behind it): `_fuse_rope`; the pair kernels: heads of 64
+        fuse = lambda s, pos, n: bool(n > 1 and self._fuse_rope(pos, s.D, s.B * n) and (not pair or (carry and s.D == 64)))
+        fuse_x, fuse_y = (lambda s: fuse(s, s.xpos, s.Nx)), (lambda s: fuse(s, s.ypos, s.Ny))
 
-    def _dec_layer_pair(self, l, a, s_a, b, s_b, pos_img, pos_state, Wn, fork=False, xs=None, os_=None):
-        """Decoder layer l for BOTH streams: image block (a, s_a) -> b and state block (s_a, a) -> s_b (model.py:669-692, both
-        read the previous layer's pair).  The seven projections of a block run as seven PAIR launches (state + image problem in
-        one grid, ops.linear_pair); RoPE of the 48-wide state heads / attention stay per side (different token counts and head widths: 16 x 48
-        state heads, 12 x 64 image heads) and, under graph capture with `fork`, on two streams.  Same kernels and row arithmetic as
-        `_dec_block`: bit-identical results.
-        This is the ONE-WINDOW schedule's form of a layer (round 4): at M = 768 / 769 rows every launch is latency, the two capture streams of
-        `_dec_block` overlap poorly (kernel trace: one kernel running 59 % of the time, two 34 %), and one launch of 2 x 156 tiles of 64 x 64
-        fills the 256 CUs where each problem alone leaves 100 idle.  xs = ((a16, a_stats), (s16, s_stats)) | None and os_ likewise for
-        (b, s_b): the LayerNorm fold (norm1 / norm_y / norm2 / norm3 inside the projections' epilogues)."""
-        cfg = self.cfg
-        Cc = a.shape[1]
-        ps, pi = f"dec_blocks_state.{l}", f"dec_blocks.{l}"
-        Ni, Ns = a.shape[0] // Wn, s_a.shape[0] // Wn
-        hs, hi = cfg.state_dec_num_heads, cfg.dec_num_heads
-        Ds, Di = Cc // hs, Cc // hi
-        S = dict(tag="decs", p=ps, x=s_a, y=a, xpos=pos_state, ypos=pos_img, heads=hs, D=Ds, out=s_b, Nx=Ns, Ny=Ni)
-        I = dict(tag="deci", p=pi, x=a, y=s_a, xpos=pos_img, ypos=pos_state, heads=hi, D=Di, out=b, Nx=Ni, Ny=Ns)
-        for sd in (S, I):
-            t, Nx, Ny, h, D = sd["tag"], sd["Nx"], sd["Ny"], sd["heads"], sd["D"]
-            sd["ln16"] = self.buf(t + ".ln16", (Wn * Nx, Cc), F16)
-            sd["y16"] = self.buf(t + ".y16", (Wn * Ny, Cc), F16)
-            sd["qkv"] = self.buf(t + ".qkv", (Wn * Nx, 3 * Cc), F16)
-            sd["att"] = self.buf(t + ".attn", (Wn, Nx, h, D), F16)
-            sd["q"] = self.buf(t + ".q", (Wn, Nx, h, D), F16)
-            sd["kv"] = self.buf(t + ".kv", (Wn * Ny, 2 * Cc), F16)
-            sd["catt"] = self.buf(t + ".cattn", (Wn, Nx, h, D), F16)
-            sd["h"] = self.buf(t + ".mlp_h", (Wn * Nx, self.w[sd["p"] + ".mlp.fc1"].npad), F16)
-        fold_in = xs is not None and self._folded(pi + ".attn.qkv") and self._folded(ps + ".attn.qkv")
-        fold_out = os_ is not None and self._folded(pi + ".mlp.fc1") and self._folded(ps + ".mlp.fc1")
-        if fold_in:
-            (I["x16"], I["xst"]), (S["x16"], S["xst"]) = xs          # image tokens a, state tokens s_a
-        if fold_out:
-            (I["o16"], I["ost"]), (S["o16"], S["ost"]) = os_
-        em = (lambda sd: {"emit": (sd["ost"], sd["o16"])}) if fold_out else (lambda sd: None)
-        # fused RoPE where the head width is 64 and the tokens have a position row each
-        small = Wn * max(Ni, Ns) <= self.pair_rows          # the 64 x 64 pair kernels carry the fused RoPE / the fold; large batches run plain pairs
-        fr = lambda pos, D, rows: bool(small and self.fused_rope and pos is not None and D == 64 and pos.is_contiguous() and pos.numel() == 2 * rows)
-
-        def both(fn):
-            """fn(side) for the state and the image side; on two capture streams when forking"""
-            if fork:
+        def each(fn, need=lambda s: True):
+            """a step that runs per block: fn(block) for those that need it"""
+            todo = [s for s in blocks if need(s)]
+            if fork and len(todo) == 2:
                 cur = torch.cuda.current_stream()
                 self._side.wait_stream(cur)
                 with torch.cuda.stream(self._side):
-                    fn(S)
-                fn(I)
+                    fn(todo[0])
+                fn(todo[1])
                 cur.wait_stream(self._side)
             else:
-                fn(S)
-                fn(I)
+                for s in todo:
+                    fn(s)
 
-        if not fold_in:
-            if self.dual_ln and Cc in (768, 1024, 1536):
-                self._dual_norms(l, a, s_a)
-            else:
-                both(lambda sd: (self._ln(sd["x"], sd["p"] + ".norm1", out16=sd["ln16"]), self._ln(sd["y"], sd["p"] + ".norm_y", out16=sd["y16"])))
+        rows = lambda t: t.view(-1, t.shape[-2] * t.shape[-1])        # [B,N,heads,D] -> [B*N,C]
+        skx, sky = (lambda s: s.Nx == 1), (lambda s: s.Ny == 1)
         # ---- self attention
-        for sd in (S, I):
-            sd["fq"] = fr(sd["xpos"], sd["D"], Wn * sd["Nx"])
-            sd["fk"] = fr(sd["ypos"], sd["D"], Wn * sd["Ny"])
-        ex = lambda sd: {"rope": (sd["xpos"], 2 * Cc, sd["D"]) if sd["fq"] else None, "ln": sd["xst"] if fold_in else None}
-        self._linear_pair(S["x16"] if fold_in else S["ln16"], ps + ".attn.qkv", S["qkv"], I["x16"] if fold_in else I["ln16"], pi + ".attn.qkv", I["qkv"],
-                          ex0=ex(S), ex1=ex(I))
+        each(lambda s: self._ln(s.x.x, s.p + ".norm1", out16=s.ln16), lambda s: not (s.fold_x or s.pre_ln))
+        self._project([dict(x16=s.x.x16 if s.fold_x else s.ln16, name=s.p + ".attn.qkv", out=s.qkv, skinny=skx(s),
+                            rope=(s.xpos, 2 * s.C, s.D) if fuse_x(s) else None, ln=s.x.st if s.fold_x else None) for s in blocks])
 
-        def self_attn(sd):
-            v5 = sd["qkv"].view(Wn, sd["Nx"], 3, sd["heads"], sd["D"])
+        def self_attn(s):
+            v5 = s.qkv.view(s.B, s.Nx, 3, s.heads, s.D)
             q, k, v = v5[:, :, 0], v5[:, :, 1], v5[:, :, 2]
-            if sd["xpos"] is not None and not sd["fq"]:
-                ops.rope_2d_pair(q, sd["xpos"], k, sd["xpos"], cfg.rope_freq, 1.0)
-            ops.attention(q, k, v, sd["att"], sd["D"] ** -0.5)
-        both(self_attn)
-        self._linear_pair(S["att"].view(Wn * Ns, Cc), ps + ".attn.proj", S["out"], I["att"].view(Wn * Ni, Cc), pi + ".attn.proj", I["out"],
-                          res0=S["x"], res1=I["x"], ex0=em(S), ex1=em(I))
-        # ---- cross attention
-        if not fold_out:
-            both(lambda sd: self._ln(sd["out"], sd["p"] + ".norm2", out16=sd["ln16"]))
-        ex = lambda sd: {"rope": (sd["xpos"], Cc, sd["D"]) if sd["fq"] else None, "ln": sd["ost"] if fold_out else None}
-        self._linear_pair(S["o16"] if fold_out else S["ln16"], ps + ".cross_attn.projq", S["q"].view(Wn * Ns, Cc),
-                          I["o16"] if fold_out else I["ln16"], pi + ".cross_attn.projq", I["q"].view(Wn * Ni, Cc), ex0=ex(S), ex1=ex(I))
-        # projk|projv of the state block reads the image tokens (a), that of the image block the state tokens (s_a): different row counts,
-        # same N and K -- one pair launch; the key half gets the fused RoPE where the heads are 64 wide
-        exk = lambda sd, other: {"rope": (sd["ypos"], Cc, sd["D"]) if sd["fk"] else None, "ln": other["xst"] if fold_in else None}
-        self._linear_pair(I["x16"] if fold_in else S["y16"], ps + ".cross_attn.projkv", S["kv"], S["x16"] if fold_in else I["y16"], pi + ".cross_attn.projkv", I["kv"],
-                          ex0=exk(S, I), ex1=exk(I, S))
+            if s.xpos is not None and not fuse_x(s):
+                ops.rope_2d_pair(q, s.xpos, k, s.xpos, self.cfg.rope_freq, 1.0)
+            ops.attention(q, k, v, s.attn, s.D ** -0.5)
+        each(self_attn)
+        self._project([dict(x16=rows(s.attn), name=s.p + ".attn.proj", out=s.out.x, res1=s.x.x, skinny=skx(s), emit=s.emit) for s in blocks])
+        # ---- cross attention: queries from x, keys / values from y
+        each(lambda s: self._ln(s.out.x, s.p + ".norm2", out16=s.ln16), lambda s: not s.fold_o)
+        self._project([dict(x16=s.out.x16 if s.fold_o else s.ln16, name=s.p + ".cross_attn.projq", out=rows(s.q), skinny=skx(s),
+                            rope=(s.xpos, s.C, s.D) if fuse_x(s) else None, ln=s.out.st if s.fold_o else None) for s in blocks])
+        rope_q = lambda s: s.xpos is not None and not fuse_x(s)
+        norm_y = lambda s: not (s.fold_y or s.pre_ln)
 
-        def cross_attn(sd):
-            kv4 = sd["kv"].view(Wn, sd["Ny"], 2, sd["heads"], sd["D"])
+        def q_rope_and_norm_y(s):
+            if rope_q(s):
+                self._rope(s.q, s.xpos)
+            if norm_y(s):
+                self._ln(s.y.x, s.p + ".norm_y", out16=s.y16)
+        each(q_rope_and_norm_y, lambda s: rope_q(s) or norm_y(s))
+        self._project([dict(x16=s.y.x16 if s.fold_y else s.y16, name=s.p + ".cross_attn.projkv", out=s.kv, skinny=sky(s),
+                            rope=(s.ypos, s.C, s.D) if fuse_y(s) else None, ln=s.y.st if s.fold_y else None) for s in blocks])
+
+        def cross_attn(s):
+            kv4 = s.kv.view(s.B, s.Ny, 2, s.heads, s.D)
             k, v = kv4[:, :, 0], kv4[:, :, 1]
-            if not sd["fq"] or not sd["fk"]:
-                qq = sd["q"] if not sd["fq"] else None
-                kk = k if not sd["fk"] else None
-                if qq is not None and kk is not None:
-                    ops.rope_2d_pair(qq, sd["xpos"], kk, sd["ypos"], cfg.rope_freq, 1.0)
-                elif qq is not None:
-                    self._rope(qq, sd["xpos"])
-                elif kk is not None:
-                    self._rope(kk, sd["ypos"])
-            ops.attention(sd["q"], k, v, sd["catt"], sd["D"] ** -0.5)
-        both(cross_attn)
-        self._linear_pair(S["catt"].view(Wn * Ns, Cc), ps + ".cross_attn.proj", S["out"], I["catt"].view(Wn * Ni, Cc), pi + ".cross_attn.proj", I["out"],
-                          res0=S["out"], res1=I["out"], ex0=em(S), ex1=em(I))
+            if s.ypos is not None and not fuse_y(s):
+                self._rope(k, s.ypos)
+            ops.attention(s.q, k, v, s.cattn, s.D ** -0.5)
+        each(cross_attn)
+        self._project([dict(x16=rows(s.cattn), name=s.p + ".cross_attn.proj", out=s.out.x, res1=s.out.x, skinny=skx(s), emit=s.emit) for s in blocks])
         # ---- MLP
-        if not fold_out:
-            both(lambda sd: self._ln(sd["out"], sd["p"] + ".norm3", out16=sd["ln16"]))
-        ex = lambda sd: {"ln": sd["ost"] if fold_out else None}
-        self._linear_pair(S["o16"] if fold_out else S["ln16"], ps + ".mlp.fc1", S["h"], I["o16"] if fold_out else I["ln16"], pi + ".mlp.fc1", I["h"], act=1,
-                          ex0=ex(S), ex1=ex(I))
-        self._linear_pair(S["h"], ps + ".mlp.fc2", S["out"], I["h"], pi + ".mlp.fc2", I["out"], res0=S["out"], res1=I["out"], ex0=em(S), ex1=em(I))
+        each(lambda s: self._ln(s.out.x, s.p + ".norm3", out16=s.ln16), lambda s: not s.fold_o)
+        self._project([dict(x16=s.out.x16 if s.fold_o else s.ln16, name=s.p + ".mlp.fc1", out=s.mlp_h, skinny=skx(s),
+                            ln=s.out.st if s.fold_o else None) for s in blocks], act=1)
+        self._project([dict(x16=s.mlp_h, name=s.p + ".mlp.fc2", out=s.out.x, res1=s.out.x, skinny=skx(s), emit=s.emit) for s in blocks])
 
     def _dual_norms(self, l, a, s_a):
         """The four input norms of decoder layer l in two launches: the image tokens `a` feed norm1 of the image block and
@@ -642,11 +595,11 @@ class Cut3rModel:
         x = self.buf("memr.x", (B, 2 * D), F32)
         self._linear(gfeat16, "pose_retriever.proj_q", x[:, :D], skinny=True)
         x[:, D:] = self.masked_token
-        a, b = x, self.buf("memr.x2", (B, 2 * D), F32)
+        a, b, m = _Stream(x), _Stream(self.buf("memr.x2", (B, 2 * D), F32)), _Stream(mem)
         for i in range(2):
-            self._dec_block("memr", f"pose_retriever.read_blocks.{i}", a, mem, None, None, cfg.dec_num_heads, b, B)
+            self._dec_layer([self._block(f"pose_retriever.read_blocks.{i}", "memr", a, m, b, None, None, cfg.dec_num_heads, B)])
             a, b = b, a
-        return a[:, D:]
+        return a.x[:, D:]
 
     def _mem_update(self, mem, gfeat16, pose_out, out, B=1):
         """mem [B*size, 2D], pose_out [B, D] -> out (new memory)  (model.py:204-215)"""
@@ -655,9 +608,9 @@ class Cut3rModel:
         f = self.buf("memw.f", (B, 2 * D), F32)
         self._linear(gfeat16, "pose_retriever.proj_q", f[:, :D], skinny=True)
         f[:, D:] = pose_out
-        tmp = self.buf("memw.tmp", tuple(mem.shape), F32)
-        self._dec_block("memw", "pose_retriever.write_blocks.0", mem, f, None, None, cfg.dec_num_heads, tmp, B)
-        self._dec_block("memw", "pose_retriever.write_blocks.1", tmp, f, None, None, cfg.dec_num_heads, out, B)
+        m, f, tmp, o = _Stream(mem), _Stream(f), _Stream(self.buf("memw.tmp", tuple(mem.shape), F32)), _Stream(out)
+        self._dec_layer([self._block("pose_retriever.write_blocks.0", "memw", m, f, tmp, None, None, cfg.dec_num_heads, B)])
+        self._dec_layer([self._block("pose_retriever.write_blocks.1", "memw", tmp, f, o, None, None, cfg.dec_num_heads, B)])
         return out
 
     # ------------------------------------------------------------------ heads
@@ -808,18 +761,21 @@ class Cut3rModel:
         pos_state = self.state_pos.expand(Wn, -1, -1).contiguous()
         taps = {"enc_feat": feat[0]} if return_taps else None
 
+        # a layer as pair launches (`pair_gemm`, or `pair_rows` at few rows) instead of one block per capture stream; what they carry: _pair_carries
+        small = self._pair_carries(Wn * max(N + 1, S))
+        pair = self.pair_gemm or small
+        # LayerNorm fold: every residual buffer of the decoder has its fp16 copy + slab statistics, written by the GEMM that fills it
+        fold = self.ln_fold and D % 64 == 0 and self._folded("dec_blocks.0.attn.qkv") and (small or not pair)
+
+        def stream(name, rows):
+            x = self.buf(name, (rows, D), F32)
+            return _Stream(x, *self._xs(name, x)) if fold else _Stream(x)
+        st = [stream("dec.state0", Wn * S), stream("dec.state1", Wn * S)]
+        im = [stream("dec.img0", Wn * (N + 1)), stream("dec.img1", Wn * (N + 1))]
         # state init (model.py:538-568, 705-711): identical for every window
-        st = [self.buf("dec.state0", (Wn * S, D), F32), self.buf("dec.state1", (Wn * S, D), F32)]
         s0 = self.buf("dec.s0", (S, D), F32)
         self._linear(self.register_tokens16, "decoder_embed_state", s0)
-        st[0].view(Wn, S, D).copy_(s0[None].expand(Wn, -1, -1))
-        im = [self.buf("dec.img0", (Wn * (N + 1), D), F32), self.buf("dec.img1", (Wn * (N + 1), D), F32)]
-        # LayerNorm fold: every residual buffer of the decoder has its fp16 copy + slab statistics, written by the GEMM that fills it
-        fold = self.ln_fold and D % 64 == 0 and self._folded("dec_blocks.0.attn.qkv")
-        xs_of = {}
-        if fold:
-            for t_, nm in ((st[0], "dec.state0"), (st[1], "dec.state1"), (im[0], "dec.img0"), (im[1], "dec.img1")):
-                xs_of[t_.data_ptr()] = self._xs(nm, t_)
+        st[0].x.view(Wn, S, D).copy_(s0[None].expand(Wn, -1, -1))
         msz = self.mem0.shape[0]
         mem = [self.buf("dec.mem0", (Wn * msz, 2 * D), F32), self.buf("dec.mem1", (Wn * msz, 2 * D), F32)]
         mem[0].view(Wn, msz, 2 * D).copy_(self.mem0[None].expand(Wn, -1, -1))
@@ -853,7 +809,7 @@ class Cut3rModel:
             ops.colmean_batched(feat[:, i], g32)                 # global feature of view i, every window, one launch
             ops.cast_f16(g32, g16)
             a, b = im[0], im[1]
-            a3 = a.view(Wn, N + 1, D)
+            a3 = a.x.view(Wn, N + 1, D)
             if i == 0:
                 a3[:, 0] = self.pose_token
             else:
@@ -863,66 +819,42 @@ class Cut3rModel:
             # after the window's last view the recurrent state and the pose memory are never read again (the next window
             # re-initialises both, model.py:819-822): their final updates are skipped unless the caller asked for them
             dead_tail = (i == V - 1) and not return_taps
+            # LayerNorm fold: the first layer's inputs come from decoder_embed / the state carry (LayerNorm launches); from the second layer of
+            # a view on they were written by the previous layer's fc2 together with their fp16 copies and slab statistics
+            fresh = False
             for l in range(Ld):
-                # LayerNorm fold: from the second layer of a view on, the inputs of a layer were written by the previous layer's fc2 together
-                # with their fp16 copies and slab statistics (the first layer's inputs come from decoder_embed / the state carry: LayerNorm launches)
-                small = Wn * (N + 1) <= self.pair_rows
-                pair = self.pair_gemm or small
-                use_fold = fold and (small or not pair)        # (a forced pair form on a large batch runs the plain 128 / 256 pair kernels)
-                xa, xsa = (xs_of[a.data_ptr()], xs_of[s_a.data_ptr()]) if (use_fold and l > 0) else (None, None)
-                xb, xsb = (xs_of[b.data_ptr()], xs_of[s_b.data_ptr()]) if use_fold else (None, None)
-                if dead_tail and l == Ld - 1:
-                    self._dec_block("deci", f"dec_blocks.{l}", a, s_a, pos_img, pos_state, cfg.dec_num_heads, b, Wn, xs=xa, ys=xsa, os_=xb)
-                    s_a, s_b = s_b, s_a
-                    a, b = b, a
-                    continue
-                if pair:
-                    self._dec_layer_pair(l, a, s_a, b, s_b, pos_img, pos_state, Wn, fork=fork, xs=(xa, xsa) if xa is not None else None,
-                                         os_=(xb, xsb) if xb is not None else None)
+                last = dead_tail and l == Ld - 1          # only the image block still feeds the heads
+                pre = bool(not last and self.dual_ln and D in (768, 1024, 1536) and not (fold and fresh))
+                if pre:
+                    self._dual_norms(l, a.x, s_a.x)
+                image = self._block(f"dec_blocks.{l}", "deci", a, s_a, b, pos_img, pos_state, cfg.dec_num_heads, Wn, fresh, pre)
+                state = None if last else self._block(f"dec_blocks_state.{l}", "decs", s_a, a, s_b, pos_state, pos_img, cfg.state_dec_num_heads,
+                                                      Wn, fresh, pre)
+                if last:
+                    self._dec_layer([image])
+                elif pair:
+                    self._dec_layer([state, image], fork)
+                elif fork:
+                    cur = torch.cuda.current_stream()
+                    self._side.wait_stream(cur)
+                    with torch.cuda.stream(self._side):
+                        self._dec_layer([state])
+                    self._dec_layer([image])
+                    cur.wait_stream(self._side)
                 else:
-                    pre = self.dual_ln and D in (768, 1024, 1536) and xa is None
-                    if pre:
-                        self._dual_norms(l, a, s_a)
-                    if fork:
-                        cur = torch.cuda.current_stream()
-                        kvf = self.kv_fork and Wn * (N + 1) <= self.kv_fork_rows
-                        kS = kI = None
-                        if kvf:
-                            # one-window schedule: the key / value projections of both blocks (LayerNorm_y -> projk|projv -> RoPE: they read the
-                            # layer's INPUTS only) leave the two block chains and run on two more capture streams, forked here -- at the layer
-                            # level, siblings of the block streams -- and joined in front of each block's cross attention
-                            if self._kv_streams is None:
-                                self._kv_streams = (torch.cuda.Stream(), torch.cuda.Stream())
-                            kS, kI = self._kv_streams
-                            kS.wait_stream(cur)
-                            kI.wait_stream(cur)
-                            with torch.cuda.stream(kS):
-                                self._dec_block("decs", f"dec_blocks_state.{l}", s_a, a, pos_state, pos_img, cfg.state_dec_num_heads, s_b, Wn, pre_ln=pre,
-                                                xs=xsa, ys=xa, os_=xsb, kv_only=True)
-                            with torch.cuda.stream(kI):
-                                self._dec_block("deci", f"dec_blocks.{l}", a, s_a, pos_img, pos_state, cfg.dec_num_heads, b, Wn, pre_ln=pre, xs=xa, ys=xsa,
-                                                os_=xb, kv_only=True)
-                        self._side.wait_stream(cur)
-                        with torch.cuda.stream(self._side):
-                            self._dec_block("decs", f"dec_blocks_state.{l}", s_a, a, pos_state, pos_img, cfg.state_dec_num_heads, s_b, Wn, pre_ln=pre,
-                                            xs=xsa, ys=xa, os_=xsb, kv_stream=kS)
-                        self._dec_block("deci", f"dec_blocks.{l}", a, s_a, pos_img, pos_state, cfg.dec_num_heads, b, Wn, pre_ln=pre, xs=xa, ys=xsa, os_=xb,
-                                        kv_stream=kI)
-                        cur.wait_stream(self._side)
-                    else:
-                        self._dec_block("decs", f"dec_blocks_state.{l}", s_a, a, pos_state, pos_img, cfg.state_dec_num_heads, s_b, Wn, pre_ln=pre,
-                                        xs=xsa, ys=xa, os_=xsb)
-                        self._dec_block("deci", f"dec_blocks.{l}", a, s_a, pos_img, pos_state, cfg.dec_num_heads, b, Wn, pre_ln=pre, xs=xa, ys=xsa, os_=xb)
+                    self._dec_layer([state])
+                    self._dec_layer([image])
                 s_a, s_b = s_b, s_a
                 a, b = b, a
-                if l + 1 == h1 or l + 1 == h2:
-                    tk = tok1 if l + 1 == h1 else tok2
-                    tk[:, i].copy_(a.view(Wn, N + 1, D)[:, 1:])      # fp32 -> fp16 (round to nearest even), one strided copy
+                fresh = True
+                for tk, h in ((tok1, h1), (tok2, h2)):          # (a decoder of depth 2 taps the same layer twice)
+                    if l + 1 == h:
+                        tk[:, i].copy_(a.x.view(Wn, N + 1, D)[:, 1:])      # fp32 -> fp16 (round to nearest even), one strided copy
             # final norms (model.py:694-697): new state = dec_norm_state(state), img = dec_norm(img)
             if not dead_tail:
-                self._ln(s_a, "dec_norm_state", out32=s_b)
+                self._ln(s_a.x, "dec_norm_state", out32=s_b.x)
             new_state = s_b
-            self._ln(a, "dec_norm", out16=dn16, out32=dn32)
+            self._ln(a.x, "dec_norm", out16=dn16, out32=dn32)
             dn16v, dn32v = dn16.view(Wn, N + 1, D), dn32.view(Wn, N + 1, D)
             tok3[:, i].copy_(dn16v[:, 1:])
             if tok3_32 is not None:
@@ -958,7 +890,7 @@ class Cut3rModel:
             # the state ping-pong: make st[cs] hold the new state for the next view
             cs = 0 if new_state is st[0] else 1
             if return_taps:
-                states.append((new_state.view(Wn, S, D)[0].clone(), mem[cm].view(Wn, msz, 2 * D)[0].clone()))
+                states.append((new_state.x.view(Wn, S, D)[0].clone(), mem[cm].view(Wn, msz, 2 * D)[0].clone()))
         if return_taps:
             taps["states"] = states
 

@@ -194,26 +194,99 @@ def test_batched_windows_equal_individual_windows():
                 assert torch.allclose(a, b, rtol=1e-4, atol=1e-5), (w, v, k, float((a - b).abs().max()))
 
 
-def test_pair_launch_form_of_a_decoder_layer_gives_the_same_bits():
+KEYS = ("pts3d_in_self_view", "conf_self", "camera_pose")
+
+
+@pytest.mark.parametrize("use_graphs", [True, False], ids=["graphs", "eager"])
+def test_pair_launch_form_of_a_decoder_layer_gives_the_same_bits(use_graphs):
     """`Cut3rModel.pair_rows`: below that many rows a decoder layer runs as pair launches (state + image projection in one grid of 64 x 64
     tiles: cut3r_gemm_f16_pair with the LayerNorm fold, the fused RoPE of the 64-wide heads and the compile-time epilogues).  Same tile
-    body, same row arithmetic: every output equals the default form bit for bit, for one window and for three batched ones."""
+    body, same row arithmetic: every output equals the default form bit for bit, for one window and for three batched ones, captured
+    (LayerNorm / RoPE / attention of the two blocks on two streams) and eager.
+    `pair_gemm` with `pair_rows` = 0 forces the PLAIN pair form (128 / 256 pair kernels: no fold, no fused RoPE, LayerNorm and RoPE launches
+    instead); the fold changes bits, so that form is compared with the default form at `ln_fold` = 0."""
     cfg = Cut3rConfig(img_size=(64, 96), enc_embed_dim=256, enc_depth=2, enc_num_heads=4, dec_embed_dim=192, dec_depth=4,
                       dec_num_heads=3, state_dec_num_heads=4, state_size=30, local_mem_size=16, ray_enc_depth=1, head_type="dpt")
     sd = synth_state_dict(cfg, 5)
     g = torch.Generator().manual_seed(1)
     imgs = torch.randint(0, 256, (9, 3, 64, 96), generator=g, dtype=torch.uint8).to(DEV)
-    outs = []
-    for rows in (0, 10 ** 9):
+
+    def run(**knobs):
         model = Cut3rModel(cfg, sd, DEV, minimal=True)
-        model.pair_rows = rows
+        model.use_graphs = use_graphs
+        for k, v in knobs.items():
+            assert hasattr(model, k)
+            setattr(model, k, v)
         feats = model.encode_batch(imgs)
         wins = torch.stack([feats[0:3], feats[3:6], feats[6:9]], 0)
         res = {k: v.clone() for k, v in model.decode_windows(wins, 64, 96).items()}
         single, _ = model.decode_window(wins[1], 64, 96)
-        outs.append((res, [{k: v.clone() for k, v in p.items()} for p in single]))
+        return res, [{k: v.clone() for k, v in p.items()} for p in single]
+
+    for base, form in ((run(pair_rows=0), run(pair_rows=10 ** 9)),
+                       (run(ln_fold=0), run(ln_fold=0, pair_gemm=True, pair_rows=0))):
+        for k in KEYS:
+            assert torch.equal(base[0][k], form[0][k]), k
+            for v in range(3):
+                assert torch.equal(base[1][v][k], form[1][v][k]), (k, v)
+
+
+_WIDE = {}
+
+
+def _wide():
+    """the smallest configuration at which `_dual_norms` is live (decoder width 768: 12 image heads of 64, 16 state heads of 48)"""
+    if not _WIDE:
+        cfg = Cut3rConfig(img_size=(64, 96), enc_embed_dim=256, enc_depth=1, enc_num_heads=4, dec_embed_dim=768, dec_depth=2,
+                          dec_num_heads=12, state_dec_num_heads=16, state_size=30, local_mem_size=16, ray_enc_depth=1, head_type="dpt")
+        g = torch.Generator().manual_seed(2)
+        _WIDE.update(cfg=cfg, sd=synth_state_dict(cfg, 7), imgs=torch.randint(0, 256, (4, 3, 64, 96), generator=g, dtype=torch.uint8).to(DEV))
+    return _WIDE["cfg"], _WIDE["sd"], _WIDE["imgs"]
+
+
+@pytest.mark.parametrize("ln_fold", [0, 1])
+def test_dual_ln_and_dual_stream_do_not_change_a_bit(ln_fold):
+    """`dual_ln` (the four input norms of a layer in two shared-statistics launches) and `dual_stream` (the two blocks of a layer on two
+    capture streams) claim identical outputs: two windows of two views under graph capture, all four settings, with and without the
+    LayerNorm fold (which decides where the dual norms still run: every layer, or the first layer of a view only)."""
+    cfg, sd, imgs = _wide()
+    outs = {}
+    for dual_ln, dual_stream in ((True, True), (False, True), (True, False), (False, False)):
+        model = Cut3rModel(cfg, sd, DEV, minimal=True)
+        assert model.use_graphs
+        model.ln_fold, model.dual_ln, model.dual_stream = ln_fold, dual_ln, dual_stream
+        feats = model.encode_batch(imgs)
+        res = model.decode_windows(torch.stack([feats[0:2], feats[2:4]], 0), 64, 96)
+        outs[dual_ln, dual_stream] = {k: v.clone() for k, v in res.items()}
         del model
-    for k in ("pts3d_in_self_view", "conf_self", "camera_pose"):
-        assert torch.equal(outs[0][0][k], outs[1][0][k]), k
-        for v in range(3):
-            assert torch.equal(outs[0][1][v][k], outs[1][1][v][k]), (k, v)
+    for knobs, res in outs.items():
+        for k in KEYS:
+            assert torch.equal(outs[True, True][k], res[k]), (knobs, k)
+
+
+def test_the_removed_kv_fork_variable_is_ignored():
+    """CUT3R_KV_FORK selected a schedule that is gone: a model built with it set decodes a window to the same bits"""
+    cfg = Cut3rConfig(img_size=(64, 96), enc_embed_dim=256, enc_depth=2, enc_num_heads=4, dec_embed_dim=192, dec_depth=4,
+                      dec_num_heads=3, state_dec_num_heads=4, state_size=30, local_mem_size=16, ray_enc_depth=1, head_type="dpt")
+    sd = synth_state_dict(cfg, 5)
+    g = torch.Generator().manual_seed(1)
+    imgs = torch.randint(0, 256, (3, 3, 64, 96), generator=g, dtype=torch.uint8).to(DEV)
+
+    def run():
+        model = Cut3rModel(cfg, sd, DEV, minimal=True)
+        preds, _ = model.decode_window(model.encode_batch(imgs), 64, 96)
+        return [{k: v.clone() for k, v in p.items()} for p in preds]
+
+    base = run()
+    old = os.environ.get("CUT3R_KV_FORK")
+    os.environ["CUT3R_KV_FORK"] = "1"
+    try:
+        forked = run()
+    finally:
+        if old is None:
+            del os.environ["CUT3R_KV_FORK"]
+        else:
+            os.environ["CUT3R_KV_FORK"] = old
+    for a, b in zip(base, forked):
+        for k in KEYS:
+            assert torch.equal(a[k], b[k]), k
