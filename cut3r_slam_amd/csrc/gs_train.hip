@@ -11,6 +11,10 @@
 //        gradient of the 6 pose increments follows                                                 gs_activate_bwd_kernel    (1 launch)
 //     -> pose gradient through exp() (forward-mode duals), Adam of the increments, optional fold   gs_pose_step_kernel       (1 launch)
 //     -> Adam of all Gaussian parameters                                                           gs_adam_kernel            (1 launch)
+//   with Training.compensate_exposure (gs_backend_per_frame.py:516, :992: colour image @ exposure_a + exposure_b before the colour losses):
+//     -> the compensated image the loss kernels read                                               exposure_fwd_kernel       (1 launch)
+//     -> colour gradient back through A (replaces the g_img += g_ssim launch) + 12 partial sums    exposure_bwd_kernel       (1 launch)
+//     -> fixed-order sum of the partial rows, Adam of A and b                                      gs_exposure_step_kernel   (1 launch)
 //
 // The pose gradient: p_cam = R_E y + t_E with y = T p and (t_E, q_E) = exp(tau, phi); q_cam = q_E * (q_T * q_g).  Both are linear in
 // R_E, t_E, q_E, so   dL/d delta_k = <dR_E/d delta_k, M> + <dt_E/d delta_k, s> + <dq_E/d delta_k, r>   with
@@ -225,7 +229,118 @@ __global__ void gs_refine_coef_kernel(const float* __restrict__ sums, float g_rg
     if (loss_acc) loss_acc[0] += g_rgb * ratio * sums[0] / (3.0f * na) + g_var * ratio * (sums[3] / nm - mean * mean);
 }
 
+// ---- per-view affine exposure (gs_backend_per_frame.py:516, :992: image = (image.permute(1,2,0) @ exposure_a + exposure_b).permute(2,0,1))
+// exposure_state: 40 floats per view -- [0:9] A row-major (A[i][j]: rendered channel i -> compensated channel j) | [9:12] b |
+// [12:24] Adam m | [24:36] Adam v | [36] steps | [37:40] zero.  One pixel per thread, 256 pixels per workgroup.
+__global__ __launch_bounds__(256) void exposure_fwd_kernel(const float* __restrict__ color, const float* __restrict__ es, int HW,
+                                                           float* __restrict__ out) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= HW) return;
+    const float c0 = color[p], c1 = color[(size_t)HW + p], c2 = color[2 * (size_t)HW + p];
+#pragma unroll
+    for (int j = 0; j < 3; j++) out[(size_t)j * HW + p] = fmaf(c2, es[6 + j], fmaf(c1, es[3 + j], fmaf(c0, es[j], es[9 + j])));
+}
+
+// g = g_out (+ g_out2) -> g_color = A g; partials (nullable) [gridDim.x, 12]: this workgroup's sums of color_i g_j (order of A) and of g_j.
+// No atomics: wave_sum, then the four waves in order -- the same inputs give the same bits.  g_color may be g_out or g_out2 itself
+// (every thread reads its own pixel of all inputs before it writes), so neither is __restrict__.
+__global__ __launch_bounds__(256) void exposure_bwd_kernel(const float* __restrict__ color, const float* g_out, const float* g_out2,
+                                                           const float* __restrict__ es, int HW, float* g_color,
+                                                           float* __restrict__ partials) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    float acc[12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) acc[k] = 0.f;
+    if (p < HW) {
+        float g[3];
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            g[j] = g_out[(size_t)j * HW + p];
+            if (g_out2) g[j] += g_out2[(size_t)j * HW + p];
+        }
+        if (partials) {
+#pragma unroll
+            for (int i = 0; i < 3; i++) {
+                const float c = color[(size_t)i * HW + p];
+#pragma unroll
+                for (int j = 0; j < 3; j++) acc[3 * i + j] = c * g[j];
+            }
+#pragma unroll
+            for (int j = 0; j < 3; j++) acc[9 + j] = g[j];
+        }
+#pragma unroll
+        for (int i = 0; i < 3; i++) g_color[(size_t)i * HW + p] = fmaf(es[3 * i + 2], g[2], fmaf(es[3 * i + 1], g[1], es[3 * i] * g[0]));
+    }
+    if (!partials) return;
+    __shared__ float part[4][12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) {
+        const float v = wave_sum(acc[k]);
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 12)
+        partials[(size_t)blockIdx.x * 12 + threadIdx.x] = ((part[0][threadIdx.x] + part[1][threadIdx.x]) + part[2][threadIdx.x]) + part[3][threadIdx.x];
+}
+
+// one wave: lane l adds the partial rows l, l + 64, ... in order, wave_sum gives every lane the 12 gradients, lane k < 12 takes the
+// torch.optim.Adam step of parameter k with the arithmetic of gs_pose_step_kernel (betas 0.9 / 0.999, eps 1e-8, step count in the state)
+__global__ __launch_bounds__(64) void gs_exposure_step_kernel(float* __restrict__ es, const float* __restrict__ partials, int rows, float lr) {
+    const int lane = threadIdx.x;
+    const float step = es[36] + 1.0f;
+    float g[12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) g[k] = 0.f;
+    for (int r = lane; r < rows; r += 64) {
+#pragma unroll
+        for (int k = 0; k < 12; k++) g[k] += partials[(size_t)r * 12 + k];
+    }
+    float mine = 0.f;
+#pragma unroll
+    for (int k = 0; k < 12; k++) {
+        const float s = wave_sum(g[k]);
+        if (lane == k) mine = s;
+    }
+    if (lane >= 12) return;
+    const float b1 = 0.9f, b2 = 0.999f;
+    const float bc1 = 1.0f - powf(b1, step), bc2 = 1.0f - powf(b2, step);
+    const float m = b1 * es[12 + lane] + (1.0f - b1) * mine;
+    const float v = b2 * es[24 + lane] + (1.0f - b2) * mine * mine;
+    es[12 + lane] = m; es[24 + lane] = v;
+    es[lane] -= (lr / bc1) * m / (sqrtf(v) / sqrtf(bc2) + 1e-8f);
+    if (lane == 0) es[36] = step;
+}
+
 }  // namespace
+
+static bool exposure_size_ok(int H, int W) { return H > 0 && W > 0 && (long long)H * W <= 2147483647LL; }
+
+extern "C" int cut3r_exposure_forward(const float* color, const float* exposure_state, int H, int W, float* out, void* stream) {
+    if (!color || !exposure_state || !out || !exposure_size_ok(H, W)) return CUT3R_ERR_ARG;
+    const int HW = H * W;
+    hipLaunchKernelGGL(exposure_fwd_kernel, dim3((unsigned)(((long long)HW + 255) / 256)), dim3(256), 0, (hipStream_t)stream, color, exposure_state, HW,
+                       out);
+    return cut3r_check_launch();
+}
+
+extern "C" long long cut3r_exposure_partial_rows(int H, int W) {
+    return exposure_size_ok(H, W) ? ((long long)H * W + 255) / 256 : -1;
+}
+
+extern "C" int cut3r_exposure_backward(const float* color, const float* g_out, const float* g_out2, const float* exposure_state, int H, int W,
+                                       float* g_color, float* partials, void* stream) {
+    if (!color || !g_out || !exposure_state || !g_color || !exposure_size_ok(H, W)) return CUT3R_ERR_ARG;
+    const int HW = H * W;
+    hipLaunchKernelGGL(exposure_bwd_kernel, dim3((unsigned)cut3r_exposure_partial_rows(H, W)), dim3(256), 0, (hipStream_t)stream, color, g_out, g_out2,
+                       exposure_state, HW, g_color, partials);
+    return cut3r_check_launch();
+}
+
+extern "C" int cut3r_gs_exposure_step(float* exposure_state, const float* partials, int rows, float lr, void* stream) {
+    if (!exposure_state || !partials || rows <= 0) return CUT3R_ERR_ARG;
+    hipLaunchKernelGGL(gs_exposure_step_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, exposure_state, partials, rows, lr);
+    return cut3r_check_launch();
+}
 
 extern "C" int cut3r_gs_activate(int P, const float* theta, const float* pose_state, float* means, float* scales, float* rots, float* opac,
                                  float* shs, void* stream) {

@@ -628,8 +628,8 @@ class GSMapper:
         views = [self.viewpoints[k] for k in current_window]
         N = len(views)
         exposure = bool(self.config["Training"].get("compensate_exposure", False))
-        if self.fused and not graph and not densify and not exposure and iters > 0 and len(self.gaussians) > 0 and N > 0:
-            return self._fused_trainer().optimization(views, iters, optimize_pose)
+        if self.fused and not graph and not densify and iters > 0 and len(self.gaussians) > 0 and N > 0:
+            return self._fused_trainer().optimization(views, iters, optimize_pose, exposure=exposure)
         use_graph = ((graph if graph is not None else (self.use_graphs and iters >= self.graph_min_iters)) and not densify and iters >= 8
                      and len(self.gaussians) > 0)
         opt = self._pose_optimizer(views, exposure, capturable=use_graph) if optimize_pose else None
@@ -690,8 +690,8 @@ class GSMapper:
         if not views or len(self.gaussians) == 0:
             return None
         exposure = bool(self.config["Training"].get("compensate_exposure", False))
-        if self.fused and not exposure and iteration_total > 0:
-            return self._fused_trainer().global_BA(iteration_total, densify, densify_every, opacity_reset, seed)
+        if self.fused and iteration_total > 0:
+            return self._fused_trainer().global_BA(iteration_total, densify, densify_every, opacity_reset, seed, exposure=exposure)
         opt = self._pose_optimizer(views, exposure)
         rng = random.Random(seed)
         tr, op = self.config["Training"], self.config["opt_params"]
@@ -957,11 +957,17 @@ class GSMapper:
     @torch.no_grad()
     def eval_rendering_kf(self):
         """eval_utils.py:110-150 over the mapper's own keyframes: PSNR on the pixels with a ground-truth colour (gt > 0) and SSIM per
-        view -> dict(mean_psnr, mean_ssim, per_view)"""
+        view -> dict(mean_psnr, mean_ssim, per_view).  With Training.compensate_exposure the rendering goes through the view's
+        exposure model before the clamp (eval_utils.py:127)"""
+        exposure = bool(self.config["Training"].get("compensate_exposure", False))
         rows = []
         for k in sorted(self.viewpoints):
             v = self.viewpoints[k]
-            img = torch.clamp(render(v, self.gaussians, self.background)["render"], 0.0, 1.0)
+            img = render(v, self.gaussians, self.background)["render"]
+            if exposure:
+                from .gs_step import apply_exposure
+                img = apply_exposure(img, v)
+            img = torch.clamp(img, 0.0, 1.0)
             gt = v.original_image
             mask = gt > 0
             mse = ((img[mask] - gt[mask]) ** 2).mean() if mask.any() else torch.zeros((), device=self.device)

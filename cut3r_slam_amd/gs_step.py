@@ -8,6 +8,12 @@ _refine_coef for the scalar algebra between their two passes) -> cut3r_gs_render
 cut3r_gs_activate_backward (gradient of theta accumulated over the views, 16 pose sums per view) -> cut3r_gs_pose_step; then ONE
 cut3r_gs_adam over all Gaussian parameters.
 
+With Training.compensate_exposure (gs_backend_per_frame.py:516, :992) three launches per rendered view join them: cut3r_exposure_forward
+between the rasteriser and the colour losses (pixel loss and SSIM then read the compensated image), cut3r_exposure_backward in place of
+the `g_img += g_ssim` launch (the colour gradient back through A, and per-workgroup partial sums of the 12 exposure gradients), and
+cut3r_gs_exposure_step after the pose step (Adam on A and b, state of ES floats per view, new per call like the reference's optimiser).
+Without the flag the launches are the ones above.
+
 The rasteriser's one host read per pass (the instance count) is taken in the FIRST iteration of a call only: later iterations run in
 capacity mode (1.5 x the largest count seen + a margin, overflow flagged on the device).  The flag is read once at the end of the call; if
 it is set, parameters, moments and poses are restored from the snapshot taken at the start and the whole call is redone with exact
@@ -25,6 +31,7 @@ from . import gaussian_rasterizer as GR
 from ._lib import check
 
 PS = 32            # floats of pose state per view (include/cut3r_hip.h)
+ES = 40            # floats of exposure state per view: A [9] row-major | b [3] | Adam m [12] | v [12] | steps | 3 x zero
 
 
 def _p(t):
@@ -43,6 +50,26 @@ _IDENTITY16 = _arr([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1])
 _ZERO3 = _arr([0, 0, 0])
 
 
+def load_exposures(views, device):
+    """[N, ES] from the views' exposure_a / exposure_b, moments and step count zero (the reference creates a new optimiser per call)"""
+    es = torch.zeros(len(views), ES, dtype=torch.float32, device=device)
+    for k, v in enumerate(views):
+        es[k, 0:9] = v.exposure_a.detach().reshape(-1)
+        es[k, 9:12] = v.exposure_b.detach()
+    return es
+
+
+def apply_exposure(color, view):
+    """color [3,H,W] through the view's affine exposure model (cut3r_exposure_forward) -> a new [3,H,W] tensor"""
+    if color.dtype != torch.float32 or color.dim() != 3 or color.shape[0] != 3 or not color.is_cuda:
+        raise ValueError("apply_exposure: color must be a dense fp32 [3,H,W] tensor on the GPU")
+    color = color.contiguous()
+    es = load_exposures([view], color.device)
+    out = torch.empty_like(color)
+    check(_lib.load().cut3r_exposure_forward(_p(color), _p(es), color.shape[1], color.shape[2], _p(out), _s()), "exposure_forward")
+    return out
+
+
 class FusedTrainer:
     """workspaces + the two loops; one instance per GSMapper (buffers are re-sized when the number of Gaussians or the image size changes)"""
 
@@ -54,6 +81,7 @@ class FusedTrainer:
         self._cap = 0
         self.capacity = (1.5, 16384)             # capacity-mode iterations: factor on the largest instance count of iteration 0 + margin
         self.redone = 0                          # calls that overflowed their capacity and were redone from the snapshot
+        self.exposure_state = None               # [N, ES] of the last optimization / global_BA call with exposure=True (else None)
 
     # ------------------------------------------------------------------ buffers
     def _buffers(self, P, H, W):
@@ -76,6 +104,7 @@ class FusedTrainer:
             self.n_contrib, self.aux = i(2, H, W), f(2, H, W)
             self.smap, self.sd1, self.sd2, self.sd3 = f(3, H, W), f(3, H, W), f(3, H, W), f(3, H, W)
             self.g_img, self.g_ssim, self.g_depth = f(3, H, W), f(3, H, W), f(1, H, W)
+            self.img_x = f(3, H, W)                    # the exposure-compensated colour image (exposure=True)
             self.zero_img = torch.zeros(3, H, W, dtype=torch.float32, device=dev)
             gx, gy = (W + 15) // 16, (H + 15) // 16
             self.ranges = i(gy * gx, 2)
@@ -179,6 +208,28 @@ class FusedTrainer:
             v.cam_trans_delta.data.copy_(ps[k, 7:10])
             v.cam_rot_delta.data.copy_(ps[k, 10:13])
 
+    @staticmethod
+    def _store_exposures(views, es):
+        for k, v in enumerate(views):
+            v.exposure_a.data.copy_(es[k, 0:9].view(3, 3))
+            v.exposure_b.data.copy_(es[k, 9:12])
+
+    def _compensate(self, es_v):
+        """the rendered colour image through one view's exposure model -> self.img_x (what the colour losses then read)"""
+        H, W = self._shape[1:]
+        check(self.lib.cut3r_exposure_forward(_p(self.img["color"]), _p(es_v), H, W, _p(self.img_x), _s()), "exposure_forward")
+        return self.img_x
+
+    def _colour_gradient(self, es_v, partials_v):
+        """g_img <- d loss / d rendered colour.  Without exposure: g_img + g_ssim.  With it: A (g_img + g_ssim), and the partial sums of the
+        12 exposure gradients into partials_v (None: the exposure stays fixed)"""
+        if es_v is None:
+            self.g_img.add_(self.g_ssim)
+            return
+        H, W = self._shape[1:]
+        check(self.lib.cut3r_exposure_backward(_p(self.img["color"]), _p(self.g_img), _p(self.g_ssim), _p(es_v), H, W, _p(self.g_img),
+                                               _p(partials_v), _s()), "exposure_backward")
+
     # ------------------------------------------------------------------ the two loops
     def _run(self, body, iters, views, snapshot):
         """iteration 0 with exact instance counts, the others in capacity mode; one overflow read at the end, redo from the snapshot if set"""
@@ -196,8 +247,9 @@ class FusedTrainer:
             for it in range(iters):
                 body(it, True)
 
-    def optimization(self, views, iters, optimize_pose=True):
-        """GSMapper.optimization without densification / exposure compensation; returns the loss of the last iteration (float)"""
+    def optimization(self, views, iters, optimize_pose=True, exposure=False):
+        """GSMapper.optimization without densification; returns the loss of the last iteration (float).  exposure: the colour losses read
+        the rendering through each view's affine exposure model, whose 12 parameters step with the poses (only if optimize_pose)"""
         mp, gm, lib = self.mp, self.mp.gaussians, self.lib
         P = len(gm)
         H, W = self._image_size(views)
@@ -207,6 +259,10 @@ class FusedTrainer:
         ps = self._load_poses(views)
         sums = torch.zeros(N, 16, dtype=torch.float32, device=self.dev) if optimize_pose else None
         lr = mp.config["opt_params"]["pose_lr"]
+        es = self.exposure_state = load_exposures(views, self.dev) if exposure else None
+        elr = mp.config["opt_params"].get("exposure_lr", 0.0005)
+        rows = int(lib.cut3r_exposure_partial_rows(H, W))
+        partials = torch.empty(N, rows, 12, dtype=torch.float32, device=self.dev) if exposure and optimize_pose else None
         self.ssim_scale.fill_(-0.2 * g / (3 * H * W))
         saved = {}
 
@@ -214,8 +270,11 @@ class FusedTrainer:
             if restore:
                 gm.theta.data.copy_(saved["theta"]); gm.m.copy_(saved["m"]); gm.v.copy_(saved["v"]); ps.copy_(saved["ps"])
                 gm.steps = saved["steps"]
+                if es is not None:
+                    es.copy_(saved["es"])
             else:
-                saved.update(theta=gm.theta.detach().clone(), m=gm.m.clone(), v=gm.v.clone(), ps=ps.clone(), steps=gm.steps)
+                saved.update(theta=gm.theta.detach().clone(), m=gm.m.clone(), v=gm.v.clone(), ps=ps.clone(), steps=gm.steps,
+                             es=es.clone() if es is not None else None)
         snapshot()
         for v in views:                                   # the keyframe's own depth normals (constant while its depth stays)
             gc = getattr(v, "_gt_normal", None)
@@ -236,18 +295,19 @@ class FusedTrainer:
             for k, v in enumerate(views):
                 cam, im = self._cam(v), self.img
                 counts.append(self._render(v, ps[k], exact))
+                col = self._compensate(es[k]) if es is not None else im["color"]
                 K = cam["K"]
-                check(lib.cut3r_pixel_loss_forward(_p(im["color"]), _p(v.original_image), _p(im["depth"]), _p(v.depth), _p(v._gt_normal[1]), H, W,
+                check(lib.cut3r_pixel_loss_forward(_p(col), _p(v.original_image), _p(im["depth"]), _p(v.depth), _p(v._gt_normal[1]), H, W,
                                                    K[0], K[1], K[2], K[3], _p(self.sums), _s()), "pixel_loss_forward")
                 check(lib.cut3r_gs_map_coef(_p(self.sums), 0.8, float(mp.lambda_depth), float(mp.lambda_normal), g, H, W, _p(self.coef),
                                             _p(self.loss_acc) if final else None, _s()), "gs_map_coef")
-                check(lib.cut3r_pixel_loss_backward(_p(im["color"]), _p(v.original_image), _p(im["depth"]), _p(v.depth), _p(v._gt_normal[1]), H, W,
+                check(lib.cut3r_pixel_loss_backward(_p(col), _p(v.original_image), _p(im["depth"]), _p(v.depth), _p(v._gt_normal[1]), H, W,
                                                     K[0], K[1], K[2], K[3], _p(self.coef), _p(self.g_img), _p(self.g_depth), _s()), "pixel_loss_backward")
-                check(lib.cut3r_ssim_forward(_p(im["color"]), _p(v.original_image), 3, H, W, _p(self.smap), _p(self.sd1), _p(self.sd2), _p(self.sd3),
+                check(lib.cut3r_ssim_forward(_p(col), _p(v.original_image), 3, H, W, _p(self.smap), _p(self.sd1), _p(self.sd2), _p(self.sd3),
                                              _s()), "ssim_forward")
-                check(lib.cut3r_ssim_backward(_p(im["color"]), _p(v.original_image), _p(self.sd1), _p(self.sd2), _p(self.sd3), 3, H, W,
+                check(lib.cut3r_ssim_backward(_p(col), _p(v.original_image), _p(self.sd1), _p(self.sd2), _p(self.sd3), 3, H, W,
                                               _p(self.ssim_scale), _p(self.g_ssim), _s()), "ssim_backward")
-                self.g_img.add_(self.g_ssim)
+                self._colour_gradient(es[k] if es is not None else None, partials[k] if partials is not None else None)
                 if final:                                 # the reported loss: the two terms that have no sums kernel, in tensor operations
                     vis = self.radii > 0
                     sc = self.scales
@@ -261,6 +321,9 @@ class FusedTrainer:
             if sums is not None:
                 for k in range(N):
                     check(lib.cut3r_gs_pose_step(_p(ps[k]), _p(sums[k]), 0.0, None, lr * 2, lr * 10, 1, _s()), "gs_pose_step")
+            if partials is not None:
+                for k in range(N):
+                    check(lib.cut3r_gs_exposure_step(_p(es[k]), _p(partials[k]), rows, elr, _s()), "gs_exposure_step")
             if final:
                 last[0] = self.loss_acc[0] + extra
             return counts
@@ -269,6 +332,8 @@ class FusedTrainer:
         gm._steps_dev_stale = True
         if optimize_pose:
             self._store_poses(views, ps)
+            if es is not None:
+                self._store_exposures(views, es)
         return float(last[0]) if last[0] is not None else None
 
     def pose_refine(self, views, iters, alpha_th=0.5):
@@ -313,11 +378,12 @@ class FusedTrainer:
             check(lib.cut3r_gs_pose_step(_p(ps[k]), _p(sums[k]), 0.0, None, 0.0, 0.0, 2, _s()), "gs_pose_step (fold)")
         self._store_poses(views, ps)
 
-    def global_BA(self, iteration_total, densify=True, densify_every=None, opacity_reset=True, seed=0):
-        """GSMapper.global_BA (gs_backend_per_frame.py:946-1058) without exposure compensation: one randomly drawn keyframe per iteration,
+    def global_BA(self, iteration_total, densify=True, densify_every=None, opacity_reset=True, seed=0, exposure=False):
+        """GSMapper.global_BA (gs_backend_per_frame.py:946-1058): one randomly drawn keyframe per iteration,
         colour + (inverse depth) + depth-normal agreement + the rendered-normal term (cut3r_normal_agree_*), densification statistics
         (cut3r_gs_densify_stats), clone / split / prune and opacity resets at the reference's iterations, position learning-rate decay.
-        The instance count is read every iteration (the set of Gaussians changes under densification)."""
+        The instance count is read every iteration (the set of Gaussians changes under densification).  exposure: the colour losses read
+        the rendering through the drawn view's exposure model, which steps with its pose (moments kept over the iterations of the call)."""
         import random
         from .gs_mapper import depth_to_normal, position_lr
         mp, lib = self.mp, self.lib
@@ -333,6 +399,10 @@ class FusedTrainer:
         w_d, w_n = (mp.lambda_depth / 10, mp.lambda_normal) if densify_every is not None else (0.0, mp.lambda_normal / 2)
         self._buffers(len(gm), H, W)
         self.ssim_scale.fill_(-0.2 / (3 * H * W))
+        es = self.exposure_state = load_exposures(views, self.dev) if exposure else None
+        elr = op.get("exposure_lr", 0.0005)
+        rows = int(lib.cut3r_exposure_partial_rows(H, W))
+        partials = torch.empty(rows, 12, dtype=torch.float32, device=self.dev) if exposure else None
         g_nrm = torch.empty(3, H, W, dtype=torch.float32, device=self.dev)
         last = None
         for iteration in range(iteration_total):
@@ -353,17 +423,18 @@ class FusedTrainer:
             if final:
                 self.loss_acc.zero_()
             self._render(v, ps[k], True)
-            check(lib.cut3r_pixel_loss_forward(_p(im["color"]), _p(v.original_image), _p(im["depth"]), _p(v.depth), _p(v._gt_normal[1]), H, W, K[0], K[1],
+            col = self._compensate(es[k]) if es is not None else im["color"]
+            check(lib.cut3r_pixel_loss_forward(_p(col), _p(v.original_image), _p(im["depth"]), _p(v.depth), _p(v._gt_normal[1]), H, W, K[0], K[1],
                                                K[2], K[3], _p(self.sums), _s()), "pixel_loss_forward")
             check(lib.cut3r_gs_map_coef(_p(self.sums), 0.8, float(w_d), float(w_n), 1.0, H, W, _p(self.coef), _p(self.loss_acc) if final else None, _s()),
                   "gs_map_coef")
-            check(lib.cut3r_pixel_loss_backward(_p(im["color"]), _p(v.original_image), _p(im["depth"]), _p(v.depth), _p(v._gt_normal[1]), H, W, K[0], K[1],
+            check(lib.cut3r_pixel_loss_backward(_p(col), _p(v.original_image), _p(im["depth"]), _p(v.depth), _p(v._gt_normal[1]), H, W, K[0], K[1],
                                                 K[2], K[3], _p(self.coef), _p(self.g_img), _p(self.g_depth), _s()), "pixel_loss_backward")
-            check(lib.cut3r_ssim_forward(_p(im["color"]), _p(v.original_image), 3, H, W, _p(self.smap), _p(self.sd1), _p(self.sd2), _p(self.sd3), _s()),
+            check(lib.cut3r_ssim_forward(_p(col), _p(v.original_image), 3, H, W, _p(self.smap), _p(self.sd1), _p(self.sd2), _p(self.sd3), _s()),
                   "ssim_forward")
-            check(lib.cut3r_ssim_backward(_p(im["color"]), _p(v.original_image), _p(self.sd1), _p(self.sd2), _p(self.sd3), 3, H, W, _p(self.ssim_scale),
+            check(lib.cut3r_ssim_backward(_p(col), _p(v.original_image), _p(self.sd1), _p(self.sd2), _p(self.sd3), 3, H, W, _p(self.ssim_scale),
                                           _p(self.g_ssim), _s()), "ssim_backward")
-            self.g_img.add_(self.g_ssim)
+            self._colour_gradient(es[k] if es is not None else None, partials)
             if final:
                 check(lib.cut3r_normal_agree_forward(_p(im["normal"]), _p(im["depth"]), H, W, K[0], K[1], K[2], K[3], _p(self.nvis), _s()), "normal_agree_forward")
                 last = self.loss_acc[0] + 0.2 * (1.0 - self.smap.mean()) + w_n * self.nvis[0] / (H * W)
@@ -399,7 +470,11 @@ class FusedTrainer:
             if densify and "position_lr_final" in op:
                 gm.lr[0, 0:3] = position_lr(op, iteration)
             check(lib.cut3r_gs_pose_step(_p(ps[k]), _p(sums[k]), 0.0, None, lr * 2, lr * 10, 1, _s()), "gs_pose_step")
+            if es is not None:
+                check(lib.cut3r_gs_exposure_step(_p(es[k]), _p(partials), rows, elr, _s()), "gs_exposure_step")
         self._store_poses(views, ps)
+        if es is not None:
+            self._store_exposures(views, es)
         return float(last) if last is not None else None
 
     def reinit_loop(self, iteration_total, seed=0):

@@ -176,12 +176,15 @@ def gs_wall_window(H: int = 384, W: int = 512, focal: float = 440.0, n_views: in
     return packet, torch.stack(imgs), cfg
 
 
-def gs_mapper_window_leg(H: int = 384, W: int = 512, device="cuda:0", use_graphs: bool = False, fused: bool = True):
+def gs_mapper_window_leg(H: int = 384, W: int = 512, device="cuda:0", use_graphs: bool = False, fused: bool = True, exposure: bool = False):
     """one synthetic 6-keyframe window through GSMapper.run with the reference's iteration counts (gs_backend_per_frame.py:776-862: 100
-    initial, per new keyframe 50 pose-refine + 20 window + 50 single-view, 10 per view global) -> timing / quality figures"""
+    initial, per new keyframe 50 pose-refine + 20 window + 50 single-view, 10 per view global) -> timing / quality figures.
+    exposure: with Training.compensate_exposure, as six of the reference's seven configurations run"""
     import time
     from . import gs_mapper as GM
     packet, imgs, cfg = gs_wall_window(H, W, device=device)
+    if exposure:
+        cfg["Training"]["compensate_exposure"] = True
     n = len(packet["viz_idx"])
     times = []
     for _ in range(2):                                # the first pass pays the one-time costs of the process (code objects, allocator pools)
@@ -202,7 +205,8 @@ def gs_mapper_window_leg(H: int = 384, W: int = 512, device="cuda:0", use_graphs
             ps.append(float(-10 * torch.log10(((r - imgs[k].float() / 255) ** 2).mean())))
     renders = 100 + (n - 1) * (50 + 50) + sum(20 * min(k + 1, 10) for k in range(1, n)) + 10 * n
     return {"config": f"synthetic wall, {n} keyframes at {W}x{H}, one Gaussian per stride-2 pixel of the first keyframe, the reference's iteration counts"
-                      + (", iterations without densification replayed from a captured hipGraph" if use_graphs else ""),
+                      + (", iterations without densification replayed from a captured hipGraph" if use_graphs else "")
+                      + (", exposure compensation on" if exposure else ""),
             "trainer": "tape-free (gs_step.FusedTrainer: direct C-ABI calls)" if fused else "tensor-op formulation with autograd",
             "seconds": round(dt, 3), "seconds_first_pass_in_process": round(times[0], 3), "ms_per_keyframe": round(1e3 * dt / n, 1),
             "realtime_budget_ms_per_keyframe_at_30fps_kf_every_10": 333.3, "render_iterations": renders,

@@ -424,7 +424,20 @@ int cut3r_gs_preprocess_backward(int P, const float* means, const float* scales,
  *                      :262; ratio NULL: factor 1), Adam (lr_trans for tau, lr_rot for phi), fold != 0: T <- exp(delta) T, delta <- 0.
  *   adam:              GaussianMap.step over n = 14 P elements with the per-column rates lr14 [14] and host-side bias corrections.
  *   map_coef / refine_coef: the scalar algebra between cut3r_pixel_loss_forward / cut3r_refine_loss_forward and their backward passes
- *                      (upstream gradient g, resp. g_rgb / g_var); loss_acc (nullable) += the weighted loss value. */
+ *                      (upstream gradient g, resp. g_rgb / g_var); loss_acc (nullable) += the weighted loss value.
+ * Exposure compensation (Training.compensate_exposure, gs_backend_per_frame.py:516, :992: a per-view affine colour model between the
+ * rasteriser's colour image and the losses, its 12 parameters in the same torch.optim.Adam as the pose increments, :467-475, :959-967).
+ * exposure_state: 40 floats per view -- [0:9] A row-major (A[i][j] = exposure_a[i, j], i the rendered channel, j the compensated one),
+ * [9:12] b, [12:24] / [24:36] Adam moments, [36] steps, [37:40] zero.
+ *   exposure_forward:  color [3,H,W] -> out [3,H,W], out[j,p] = b[j] + sum_i color[i,p] A[i][j] (fp32).
+ *   exposure_backward: g = g_out + g_out2 (g_out2 nullable) -> g_color[i,p] = sum_j A[i][j] g[j,p].  g_color MAY be g_out or g_out2
+ *                      itself (the same pointer, not a shifted overlap); it must not overlap color.  partials (nullable: a frozen exposure)
+ *                      [cut3r_exposure_partial_rows(H, W), 12]: one row per workgroup, sum_p color[i,p] g[j,p] in the order of A, then
+ *                      sum_p g[j,p]; every row is written (no zeroing needed), without atomics: the same inputs give the same bits.
+ *   exposure_partial_rows: the number of those rows (-1 for a size the launchers refuse: 1 is a valid count).
+ *   gs_exposure_step:  the 12 gradients = the sum of the `rows` partial rows in a fixed order, then one torch.optim.Adam step of A and b
+ *                      (betas 0.9 / 0.999, eps 1e-8, step size lr / bc1, the step count kept in the state).
+ * H * W must fit an int. */
 int cut3r_gs_activate(int P, const float* theta, const float* pose_state, float* means, float* scales, float* rots, float* opac, float* shs,
                       void* stream);
 int cut3r_gs_activate_backward(int P, const float* theta, const float* pose_state, const float* d_means, const float* d_scales,
@@ -438,6 +451,11 @@ int cut3r_gs_map_coef(const float* sums, float w_rgb, float w_depth, float w_nor
                       void* stream);
 int cut3r_gs_refine_coef(const float* sums, float g_rgb, float g_var, int H, int W, float* coef, float* ratio_out, float* loss_acc,
                          void* stream);
+int cut3r_exposure_forward(const float* color, const float* exposure_state, int H, int W, float* out, void* stream);
+long long cut3r_exposure_partial_rows(int H, int W);
+int cut3r_exposure_backward(const float* color, const float* g_out, const float* g_out2, const float* exposure_state, int H, int W,
+                            float* g_color, float* partials, void* stream);
+int cut3r_gs_exposure_step(float* exposure_state, const float* partials, int rows, float lr, void* stream);
 /* simple_knn._C.distCUDA2 (call sites hislam2/gaussian/scene/gaussian_model.py:191,313; the extension is not vendored in the
  * reference tree): points [P,3] -> out [P], the mean squared distance to the 3 nearest other points.  P >= 4.
  * workspace: cut3r_knn3_chunks(P) * P * 3 floats (the candidates are searched in that many chunks, merged by a second kernel). */

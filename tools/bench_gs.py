@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Gaussian rasteriser micro-benchmark (csrc/gs.hip): forward and forward+backward time of one 640x480 view of a synthetic room of
 P Gaussians (SH degree 0, as the GS mapper runs it), HIP events on the current stream.
-usage: python tools/bench_gs.py [--points 50000 200000 800000] [--size 480 640]"""
+usage: python tools/bench_gs.py [--points 50000 200000 800000] [--size 480 640] [--exposure]"""
 import argparse
 import math
 import os
@@ -15,6 +15,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--points", type=int, nargs="+", default=[50000, 200000, 800000])
 ap.add_argument("--size", type=int, nargs=2, default=[480, 640])
 ap.add_argument("--iters", type=int, default=20)
+ap.add_argument("--exposure", action="store_true", help="the mapper leg with Training.compensate_exposure")
 args = ap.parse_args()
 DEV = "cuda:0"
 H, W = args.size
@@ -90,8 +91,8 @@ for P in args.points:
 if os.environ.get("CUT3R_BENCH_GS_MAPPER", "1") == "1":
     import time
     from cut3r_slam_amd import synth, gs_mapper as GM
-    r = synth.gs_mapper_window_leg(384, 512, DEV)
-    print(f"mapper, one 6-keyframe window at 512x384: {r['seconds']:.2f} s = {r['ms_per_keyframe']:.0f} ms per keyframe, about {r['render_iterations']} "
+    r = synth.gs_mapper_window_leg(384, 512, DEV, exposure=args.exposure)
+    print(f"mapper, one 6-keyframe window at 512x384{', exposure compensation on' if args.exposure else ''}: {r['seconds']:.2f} s = {r['ms_per_keyframe']:.0f} ms per keyframe, about {r['render_iterations']} "
           f"forward+backward renders ({r['ms_per_render_iteration']:.2f} ms each incl. losses and optimiser), {r['gaussians']} Gaussians, "
           f"PSNR {r['psnr_db']:.1f} dB")
     # a long loop over a fixed set of Gaussians (a final refinement): eager vs one captured iteration replayed
