@@ -139,6 +139,8 @@ SIGNATURES = {
     "cut3r_exposure_partial_rows": [c_int, c_int],
     "cut3r_exposure_backward": [c_void_p] * 4 + [c_int, c_int, c_void_p, c_void_p, c_void_p],
     "cut3r_gs_exposure_step": [c_void_p, c_void_p, c_int, c_float, c_void_p],
+    "cut3r_gs_pose_backward": [c_int] + [c_void_p] * 6 + [c_int, c_int] + [c_float] * 4 + [c_void_p] * 7,
+    "cut3r_gs_pose_partial_rows": [c_int],
     "cut3r_knn3_chunks": [c_int],
     "cut3r_knn3_mean_dist2": [c_void_p, c_int, c_void_p, c_void_p, c_void_p],
     "cut3r_knn3_grid_workspace_bytes": [c_int],
@@ -188,7 +190,7 @@ RESTYPES = {"cut3r_ba_workspace_floats": c_ll, "cut3r_gs_workspace_bytes": c_ll,
             "cut3r_tsdf_sparse_mesh_workspace_bytes": c_ll, "cut3r_mesh_cdf_workspace_bytes": c_ll,
             "cut3r_nn_workspace_bytes": c_ll, "cut3r_icp_moments_workspace_bytes": c_ll, "cut3r_mesh_raster_workspace_bytes": c_ll,
             "cut3r_depth_l1_workspace_bytes": c_ll, "cut3r_depth_cloud_workspace_bytes": c_ll, "cut3r_cloud_bounds_workspace_bytes": c_ll,
-            "cut3r_voxel_downsample_workspace_bytes": c_ll, "cut3r_exposure_partial_rows": c_ll}
+            "cut3r_voxel_downsample_workspace_bytes": c_ll, "cut3r_exposure_partial_rows": c_ll, "cut3r_gs_pose_partial_rows": c_ll}
 
 _lib = None
 

@@ -531,20 +531,12 @@ __global__ __launch_bounds__(GS_BATCH) void gs_render_bwd_kernel(const unsigned*
     }
 }
 
-// Per-Gaussian backward: the projection again, on dual numbers seeded with (mean, scale, quaternion), contracted with the record
-// gradients; SH colour by its (linear) basis.  Replaces backward.cu:21-143,145-628.
-__global__ __launch_bounds__(64) void gs_preprocess_bwd_kernel(int P, const float* __restrict__ means, const float* __restrict__ scales,
-                                                               const float* __restrict__ rots, const float* __restrict__ opac,
-                                                               const float* __restrict__ shs, int use_sh, GsCam cam,
-                                                               const float* __restrict__ geom, const float* __restrict__ dgeom,
-                                                               float* __restrict__ d_means, float* __restrict__ d_scales,
-                                                               float* __restrict__ d_rots, float* __restrict__ d_opac, float* __restrict__ d_shs,
-                                                               float* __restrict__ d_colors, float* __restrict__ d_means2D) {
-    const int i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= P) return;
-    const float* rec = geom + (size_t)i * GS_REC;
-    if (!(rec[G_RADIUS] > 0.f)) return;                                        // culled in the forward pass: every gradient stays 0
-    const float* dg = dgeom + (size_t)i * GS_REC;
+// The projection again for Gaussian i, on dual numbers seeded with (mean, scale, quaternion), contracted with its record gradients dg:
+// gin[0:3] = d/d mean, [3:6] = d/d scale, [6:10] = d/d quaternion (without the SH colour's share of d/d mean).  Returns the value of
+// the opacity factor (GsProj::coef).  Every result leaves through an empty asm: all eleven are complete and opaque at that point, whatever
+// the caller goes on to read.
+DEVINL float gs_project_bwd(int i, const float* __restrict__ means, const float* __restrict__ scales, const float* __restrict__ rots,
+                            const float* __restrict__ opac, const GsCam& cam, const float* __restrict__ dg, float* gin) {
     typedef Dual<10> D;
     D mean[3], sc[3], rt[4];
 #pragma unroll
@@ -552,7 +544,6 @@ __global__ __launch_bounds__(64) void gs_preprocess_bwd_kernel(int P, const floa
 #pragma unroll
     for (int k = 0; k < 4; k++) { rt[k] = D(rots[4 * i + k]); rt[k].d[6 + k] = 1.f; }
     const GsProj<D> o = gs_project<D>(mean, sc, rt, cam);
-    float gin[10];
 #pragma unroll
     for (int k = 0; k < 10; k++) gin[k] = 0.f;
     auto acc = [&](const D& f, float gf) {
@@ -568,38 +559,127 @@ __global__ __launch_bounds__(64) void gs_preprocess_bwd_kernel(int P, const floa
 #pragma unroll
     for (int k = 0; k < 6; k++) acc(o.cp[k], dg[G_CP + k]);
     acc(o.rp[0], dg[G_RP]); acc(o.rp[1], dg[G_RP + 1]);
-    d_opac[i] = dg[G_OP] * o.coef.v;
-    if (use_sh) {
-        typedef Dual<3> D3;
-        D3 m3[3], b[16];
+    float coef = o.coef.v;
+    asm volatile("" : "+v"(coef));
 #pragma unroll
-        for (int k = 0; k < 3; k++) { m3[k] = D3(means[3 * i + k]); m3[k].d[k] = 1.f; }
+    for (int k = 0; k < 10; k++) asm volatile("" : "+v"(gin[k]));
+    return coef;
+}
+
+// Per-Gaussian backward (gs_project_bwd; SH colour by its (linear) basis; replaces backward.cu:21-143,145-628) in two modes that run the
+// SAME instructions up to the per-Gaussian d_mean / d_scale / d_rot -- so those are the same bits in both.  (Two kernels that each inline
+// gs_project_bwd do NOT give the same bits: the compiler contracts multiply-adds by context, and their d_mean differed in the last place.)
+//   partials == NULL  (cut3r_gs_preprocess_backward, 64 threads per workgroup): the gradients go to d_means ... d_means2D.
+//   partials != NULL  (cut3r_gs_pose_backward, 256 threads per workgroup): the backward pass of a pose-only iteration against a FROZEN map
+//     (gs_backend_per_frame.py:123-177 pose_estimator) -- no per-Gaussian gradient is written; every Gaussian's 16 terms of the pose sums
+//     of gs_train.hip's header,  g y^T (9), g (3), g^q * conj(q_T * q_g) (4)  with y = R(q_T) x + t_T (the view's pose BEFORE its increment)
+//     and q_g the normalised quaternion of theta, are formed in fp64 and rounded to fp32 ONCE (~100 fp64 operations beside the ~10 x larger
+//     dual-number projection), so the fp32 sums are within n_visible * 2^-24 * sum |term| of the exact sums.  Culled Gaussians contribute
+//     exactly 0.  Reduction without atomics: wave_sum, the waves in order, one row of partials [gridDim.x, 16] per workgroup (every row
+//     written).  View-independent colour only (use_sh = 0: colour has no gradient to the mean).
+__global__ __launch_bounds__(256) void gs_preprocess_bwd_kernel(int P, const float* __restrict__ means, const float* __restrict__ scales,
+                                                                const float* __restrict__ rots, const float* __restrict__ opac,
+                                                                const float* __restrict__ shs, int use_sh, GsCam cam,
+                                                                const float* __restrict__ geom, const float* __restrict__ dgeom,
+                                                                float* __restrict__ d_means, float* __restrict__ d_scales,
+                                                                float* __restrict__ d_rots, float* __restrict__ d_opac, float* __restrict__ d_shs,
+                                                                float* __restrict__ d_colors, float* __restrict__ d_means2D,
+                                                                const float* __restrict__ theta, const float* __restrict__ ps,
+                                                                float* __restrict__ partials) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    float acc[16];
 #pragma unroll
-        for (int k = 0; k < 16; k++) b[k] = D3(0.f);
-        sh_basis<D3>(m3, cam.campos, cam.deg, b);
-        const int nb = (cam.deg + 1) * (cam.deg + 1);
-        const unsigned clampbits = __float_as_uint(rec[G_CLAMP]);
-        const float* sh = shs + (size_t)i * cam.K * 3;
-        float* dsh = d_shs + (size_t)i * cam.K * 3;
-        for (int ch = 0; ch < 3; ch++) {
-            const float gc = (clampbits >> ch) & 1u ? 0.f : dg[G_RGB + ch];    // clamped at 0 in the forward pass: no gradient
-            for (int k = 0; k < nb; k++) {
-                dsh[3 * k + ch] = gc * b[k].v;
-                const float w = gc * sh[3 * k + ch];
-                gin[0] += w * b[k].d[0]; gin[1] += w * b[k].d[1]; gin[2] += w * b[k].d[2];
+    for (int k = 0; k < 16; k++) acc[k] = 0.f;
+    // (i >= P, or culled in the forward pass: every gradient stays 0)
+    if (i < P && geom[(size_t)i * GS_REC + G_RADIUS] > 0.f) {
+        const float* rec = geom + (size_t)i * GS_REC;
+        const float* dg = dgeom + (size_t)i * GS_REC;
+        float gin[10];
+        const float coef = gs_project_bwd(i, means, scales, rots, opac, cam, dg, gin);
+        if (partials) {
+            const float* th = theta + (size_t)i * 14;
+            const V3<double> tT = {ps[0], ps[1], ps[2]};
+            const Q4<double> qT = {ps[3], ps[4], ps[5], ps[6]};
+            const V3<double> y = add(qrot(qT, V3<double>{th[0], th[1], th[2]}), tT);
+            const double g[3] = {gin[0], gin[1], gin[2]};
+            const double yv[3] = {y.x, y.y, y.z};
+#pragma unroll
+            for (int a = 0; a < 3; a++) {
+#pragma unroll
+                for (int b = 0; b < 3; b++) acc[3 * a + b] = (float)(g[a] * yv[b]);
+                acc[9 + a] = gin[a];
             }
+            const double qr = th[10], qx = th[11], qy = th[12], qz = th[13];
+            const double inv = 1.0 / fmax(sqrt(qr * qr + qx * qx + qy * qy + qz * qz), 1e-12);       // F.normalize
+            const Q4<double> gq = {qx * inv, qy * inv, qz * inv, qr * inv};
+            const Q4<double> gc = {gin[7], gin[8], gin[9], gin[6]};                                // d_rot (rxyz) as xyzw
+            const Q4<double> r = qmul(gc, qconj(qmul(qT, gq)));
+            acc[12] = (float)r.x; acc[13] = (float)r.y; acc[14] = (float)r.z; acc[15] = (float)r.w;
+        } else {
+            d_opac[i] = dg[G_OP] * coef;
+            if (use_sh) {
+                typedef Dual<3> D3;
+                D3 m3[3], b[16];
+#pragma unroll
+                for (int k = 0; k < 3; k++) { m3[k] = D3(means[3 * i + k]); m3[k].d[k] = 1.f; }
+#pragma unroll
+                for (int k = 0; k < 16; k++) b[k] = D3(0.f);
+                sh_basis<D3>(m3, cam.campos, cam.deg, b);
+                const int nb = (cam.deg + 1) * (cam.deg + 1);
+                const unsigned clampbits = __float_as_uint(rec[G_CLAMP]);
+                const float* sh = shs + (size_t)i * cam.K * 3;
+                float* dsh = d_shs + (size_t)i * cam.K * 3;
+                for (int ch = 0; ch < 3; ch++) {
+                    const float gc = (clampbits >> ch) & 1u ? 0.f : dg[G_RGB + ch];    // clamped at 0 in the forward pass: no gradient
+                    for (int k = 0; k < nb; k++) {
+                        dsh[3 * k + ch] = gc * b[k].v;
+                        const float w = gc * sh[3 * k + ch];
+                        gin[0] += w * b[k].d[0]; gin[1] += w * b[k].d[1]; gin[2] += w * b[k].d[2];
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int ch = 0; ch < 3; ch++) d_colors[3 * i + ch] = dg[G_RGB + ch];
+            }
+#pragma unroll
+            for (int k = 0; k < 3; k++) { d_means[3 * i + k] = gin[k]; d_scales[3 * i + k] = gin[3 + k]; }
+#pragma unroll
+            for (int k = 0; k < 4; k++) d_rots[4 * i + k] = gin[6 + k];
+            d_means2D[3 * i] = dg[G_XY] * 0.5f * (float)cam.W;                 // backward.cu:1002-1006: in NDC units, |.| sum in z
+            d_means2D[3 * i + 1] = dg[G_XY + 1] * 0.5f * (float)cam.H;
+            d_means2D[3 * i + 2] = dg[G_DEPTH];
         }
-    } else {
-#pragma unroll
-        for (int ch = 0; ch < 3; ch++) d_colors[3 * i + ch] = dg[G_RGB + ch];
     }
+    if (!partials) return;                                                     // (uniform: a kernel argument)
+    __shared__ float part[4][16];
+    const int wave = threadIdx.x >> 6;
 #pragma unroll
-    for (int k = 0; k < 3; k++) { d_means[3 * i + k] = gin[k]; d_scales[3 * i + k] = gin[3 + k]; }
+    for (int k = 0; k < 16; k++) {
+        const float v = wave_sum(acc[k]);
+        if ((threadIdx.x & 63) == 0) part[wave][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 16)
+        partials[(size_t)blockIdx.x * 16 + threadIdx.x] = ((part[0][threadIdx.x] + part[1][threadIdx.x]) + part[2][threadIdx.x]) + part[3][threadIdx.x];
+}
+
+// one wave: lane l adds the partial rows l, l + 64, ... in order, wave_sum folds the lanes, lane k < 16 WRITES pose_sums[k]
+__global__ __launch_bounds__(64) void gs_pose_sums_kernel(const float* __restrict__ partials, int rows, float* __restrict__ sums) {
+    const int lane = threadIdx.x;
+    float g[16];
 #pragma unroll
-    for (int k = 0; k < 4; k++) d_rots[4 * i + k] = gin[6 + k];
-    d_means2D[3 * i] = dg[G_XY] * 0.5f * (float)cam.W;                         // backward.cu:1002-1006: in NDC units, |.| sum in z
-    d_means2D[3 * i + 1] = dg[G_XY + 1] * 0.5f * (float)cam.H;
-    d_means2D[3 * i + 2] = dg[G_DEPTH];
+    for (int k = 0; k < 16; k++) g[k] = 0.f;
+    for (int r = lane; r < rows; r += 64) {
+#pragma unroll
+        for (int k = 0; k < 16; k++) g[k] += partials[(size_t)r * 16 + k];
+    }
+    float mine = 0.f;
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+        const float s = wave_sum(g[k]);
+        if (lane == k) mine = s;
+    }
+    if (lane < 16) sums[lane] = mine;
 }
 
 // ------------------------------------------------------------------------------------------------ simple_knn.distCUDA2
@@ -1159,7 +1239,28 @@ extern "C" int cut3r_gs_preprocess_backward(int P, const float* means, const flo
                                sh_coeffs);
     if (rc != CUT3R_OK) return rc;
     hipLaunchKernelGGL(gs_preprocess_bwd_kernel, dim3((P + 63) / 64), dim3(64), 0, (hipStream_t)stream, P, means, scales, rots, opacities, shs,
-                       shs ? 1 : 0, cam, geom, dgeom, d_means, d_scales, d_rots, d_opacities, d_shs, d_colors, d_means2D);
+                       shs ? 1 : 0, cam, geom, dgeom, d_means, d_scales, d_rots, d_opacities, d_shs, d_colors, d_means2D, (const float*)nullptr,
+                       (const float*)nullptr, (float*)nullptr);
+    return cut3r_check_launch();
+}
+
+extern "C" long long cut3r_gs_pose_partial_rows(int P) { return P > 0 ? ((long long)P + 255) / 256 : -1; }
+
+extern "C" int cut3r_gs_pose_backward(int P, const float* means, const float* scales, const float* rots, const float* opacities,
+                                      const float* viewmatrix_host, const float* projmatrix_host, int W, int H, float tanfovx, float tanfovy,
+                                      float kernel_size, float scale_modifier, const float* geom, const float* dgeom, const float* theta,
+                                      const float* pose_state, float* partials, float* pose_sums, void* stream) {
+    if (P <= 0 || !means || !scales || !rots || !opacities || !geom || !dgeom || !theta || !pose_state || !partials || !pose_sums)
+        return CUT3R_ERR_ARG;
+    GsCam cam;
+    const int rc = gs_fill_cam(cam, viewmatrix_host, projmatrix_host, nullptr, W, H, tanfovx, tanfovy, kernel_size, scale_modifier, 0, 1);
+    if (rc != CUT3R_OK) return rc;
+    const int rows = (int)cut3r_gs_pose_partial_rows(P);
+    hipStream_t s = (hipStream_t)stream;
+    float* const none = nullptr;                   // the pose mode of the per-Gaussian backward writes no per-Gaussian gradient
+    hipLaunchKernelGGL(gs_preprocess_bwd_kernel, dim3(rows), dim3(256), 0, s, P, means, scales, rots, opacities, (const float*)nullptr, 0, cam, geom,
+                       dgeom, none, none, none, none, none, none, none, theta, pose_state, partials);
+    hipLaunchKernelGGL(gs_pose_sums_kernel, dim3(1), dim3(64), 0, s, partials, rows, pose_sums);
     return cut3r_check_launch();
 }
 

@@ -10,12 +10,14 @@ rasteriser.  Mirrors, with the same names, argument meaning
   GSMapper.optimization  hislam2/gs_backend_per_frame.py:451-587
   GSMapper.add_new_view  hislam2/gs_backend_per_frame.py:87-121
   GSMapper.gaussian_reinit, finalize, save / load, eval_rendering_kf   :865-944, :1067-1102
+  GSMapper.pose_estimator  hislam2/gs_backend_per_frame.py:123-177 (a frame's pose against the frozen map: util/trajectory_filler.py)
+  GSMapper.eval_rendering  hislam2/gaussian/utils/eval_utils.py:14-105 (PSNR / SSIM / depth L1 of renderings of the whole sequence)
   GSMapper.global_BA     hislam2/gs_backend_per_frame.py:946-1062 (all keyframes, poses and Gaussians together, one random keyframe per
                          iteration, densification / opacity-reset / learning-rate schedule)
 
 The reference's backend cannot run here (CUDA rasteriser, open3d, munch): PARITY UNPINNED, covered by functional tests on a
 synthetic scene (tests/test_gs_mapper_gpu.py).  The rasteriser and the 3-NN search are the HIP kernels of csrc/gs.hip; the loss
-terms and the Adam updates are plain torch tensor arithmetic on the GPU.  Not built: GUI, Gaussian ply export and LPIPS (PSNR / SSIM of the keyframes,
+terms and the Adam updates are plain torch tensor arithmetic on the GPU.  Not built: GUI, Gaussian ply export and LPIPS (PSNR / SSIM of the keyframes and -- eval_rendering -- of the whole sequence,
 a safetensors checkpoint, -- cut3r_slam_amd/tsdf.py, fuse_mapper -- the TSDF mesh of the keyframe renders and -- eval_recon.py -- its
 reconstruction metrics are).
 `gaussain_update` (the map correction after a loop closure, :701-774) composes rotations consistently by default; see its docstring."""
@@ -458,6 +460,9 @@ class GSMapper:
         # optimization() / pose_refine() on the tape-free trainer of gs_step.py (direct C-ABI calls, ~4x fewer launches); False: the
         # tensor-op formulation below (the tests compare the two)
         self.fused = True
+        # pose_estimator()'s backward pass on the tape-free trainer: "fused" = cut3r_gs_pose_backward, "chain" = the three-call backward of
+        # pose_refine (tools/bench_fill.py measures both)
+        self.pose_backward = "fused"
         self._trainer = None
 
     def _fused_trainer(self):
@@ -974,6 +979,154 @@ class GSMapper:
             rows.append((k, float(20 * torch.log10(1.0 / torch.sqrt(mse.clamp_min(1e-12)))), float(ssim(img, gt))))
         n = max(1, len(rows))
         return {"mean_psnr": sum(r[1] for r in rows) / n, "mean_ssim": sum(r[2] for r in rows) / n, "per_view": rows}
+
+    # ---- poses of frames the map was not trained on (gs_backend_per_frame.py:123-177) and the rendering evaluation of the whole
+    #      sequence (gaussian/utils/eval_utils.py:14-105)
+    def _view_size(self):
+        """(H, W) of the mapper's views (None before the first one)"""
+        for v in self.viewpoints.values():
+            return int(v.image_height), int(v.image_width)
+        return None
+
+    def _frame_image(self, image):
+        """a frame (u8 or float, [3,h,w] or [1,3,h,w]) as float [3,H,W] in [0,1] at the mapper's image size, by the rule of
+        Cut3rSlam.terminate(add_kf): bilinear, align_corners=False, and a u8 frame stays on the u8 grid (rounded, clamped)"""
+        img = torch.as_tensor(image)
+        img = img[0] if img.dim() == 4 else img
+        u8 = img.dtype == torch.uint8
+        img = img.to(self.device).float()
+        size = self._view_size()
+        if size is not None and tuple(img.shape[-2:]) != size:
+            img = F.interpolate(img[None], size=size, mode="bilinear", align_corners=False)[0]
+            if u8:
+                img = img.round().clamp(0, 255)
+        return (img / 255.0 if (u8 or img.max() > 1.5) else img).contiguous()
+
+    def pose_estimator(self, pose7_c2w, image, tstamp, gt_depth=None, iters=100, pose_backward=None):
+        """gs_backend_per_frame.py:123-177: the pose of ONE frame against the frozen map.  A fresh Camera at `pose7_c2w` ([7] camera->world,
+        t + q_xyzw); `iters` iterations of loss = 0.8 mean|gt - img| + 0.2 (1 - ssim) (+ with gt_depth [h,w] the mean of |1/d - 1/gt_d|
+        over gt_d > 0.001 and d > 0.001), torch.optim.Adam on both increments at opt_params.pose_lr (NOT the 2x / 10x rates of
+        _pose_optimizer), update_pose after every iteration.  Returns the refined pose [7] camera->world (t, q_xyzw) on the host.
+        The frame is brought to the mapper's image size (_frame_image: bilinear, align_corners=False); the reference renders at the kept
+        frame's own (full) size with the full-resolution calibration.
+        self.fused (default): the tape-free loop of gs_step.FusedTrainer.pose_estimator, whose backward pass ends in
+        cut3r_gs_pose_backward (pose_backward="chain": the three-call backward of pose_refine instead; default self.pose_backward);
+        self.fused = False: the loop as the reference writes it, over the differentiable `render` and `ssim`."""
+        if len(self.gaussians) == 0:
+            raise RuntimeError("pose_estimator needs a Gaussian map")
+        img = self._frame_image(image)
+        H, W = img.shape[-2:]
+        if gt_depth is not None:
+            depth = torch.as_tensor(gt_depth).to(self.device).float()
+            if tuple(depth.shape[-2:]) != (H, W):
+                depth = F.interpolate(depth.reshape(1, 1, *depth.shape[-2:]), size=(H, W), mode="bilinear", align_corners=False)[0, 0]
+        else:
+            depth = torch.zeros(H, W, device=self.device)
+        w2c = torch.inverse(pose_vec_to_matrix(torch.as_tensor(pose7_c2w).detach().float()[None].to(self.device))[0])
+        v = Camera(-1, img, depth, w2c, self.fx, self.fy, self.cx, self.cy, tstamp, self.device)
+        if iters > 0 and self.fused:
+            with torch.no_grad():
+                self._fused_trainer().pose_estimator(v, int(iters), use_depth=gt_depth is not None,
+                                                     pose_backward=pose_backward or self.pose_backward)
+        elif iters > 0:
+            lr = self.config["opt_params"]["pose_lr"]
+            with torch.enable_grad():
+                opt = torch.optim.Adam([{"params": [v.cam_rot_delta], "lr": lr}, {"params": [v.cam_trans_delta], "lr": lr}])
+                gt = v.original_image
+                for _ in range(int(iters)):
+                    pkg = render(v, self.gaussians, self.background)
+                    image_r, d = pkg["render"], pkg["depth"]
+                    loss = 0.8 * torch.abs(gt - image_r).mean() + 0.2 * (1.0 - ssim(image_r, gt))
+                    if gt_depth is not None:
+                        gd = v.depth[None]
+                        mask = (gd > 0.001) & (d > 0.001)
+                        loss = loss + torch.abs(1.0 / d[mask] - 1.0 / gd[mask]).mean()
+                    opt.zero_grad(set_to_none=True)
+                    self.gaussians.zero_grad()
+                    loss.backward()
+                    opt.step()
+                    update_pose(v)
+                self.gaussians.zero_grad()
+        with torch.no_grad():
+            return SE3_from_matrix(torch.inverse(get_pose(v))).detach().cpu()
+
+    @torch.no_grad()
+    def eval_rendering(self, images, traj_tstamps, traj, kf_tstamps, gtdepthdir=None, out_dir=None, result_dir=None):
+        """gaussian/utils/eval_utils.py:14-105 eval_rendering: renderings of the WHOLE sequence, also of frames the map was not trained on.
+        images: the frames by index (a dict index -> frame or a sequence; u8 [3,h,w] / [1,3,h,w], brought to the mapper's size by
+        _frame_image); traj_tstamps [n] / traj [n,7]: the full trajectory (camera->world, t + q_xyzw), looked up by tstamp; kf_tstamps: the
+        tstamps of the keyframes.  Frame i is scored if i % 5 == 0, or it is a keyframe, or it is the last frame.  A keyframe is rendered
+        from the mapper's own view of that tstamp (its pose and its exposure model), any other frame from a Camera at the trajectory's
+        pose with identity exposure.  PSNR over gt > 0, SSIM over the whole image; with gtdepthdir (16-bit PNGs / 6553.5, sorted names,
+        eval_dense.read_depth_png, nearest resize) the depth L1 of the KEYFRAMES: invalid GT zeroes the rendered depth, pixels with
+        rendered depth > 0 are averaged.  Returns dict(mean_psnr, mean_ssim, mean_l1, per_frame [(index, psnr, ssim)]) and writes the
+        three means to <dir>/psnr/after_opt/final_result.json, dir = result_dir or out_dir (neither: nothing is written); with out_dir
+        also renders/image_after_opt/%06d.jpg and the 16-bit renders/depth_after_opt/%06d.png.  LPIPS is not built (its AlexNet
+        weights are not available): the reference's mean_lpips key is absent."""
+        import json
+        import os
+
+        import numpy as np
+        items = sorted(images.items()) if hasattr(images, "items") else list(enumerate(images))
+        row = {int(round(float(t))): k for k, t in enumerate(torch.as_tensor(traj_tstamps).reshape(-1).tolist())}
+        traj = torch.as_tensor(traj).float()
+        kfs = {int(round(float(t))) for t in torch.as_tensor(kf_tstamps).reshape(-1).tolist()}
+        own = {int(round(float(v.tstamp))): v for v in self.viewpoints.values() if v.tstamp is not None}
+        gtdepths = sorted(os.listdir(gtdepthdir)) if gtdepthdir is not None else None
+        if out_dir is not None:
+            from PIL import Image
+            img_dir, dep_dir = os.path.join(out_dir, "renders", "image_after_opt"), os.path.join(out_dir, "renders", "depth_after_opt")
+            os.makedirs(img_dir, exist_ok=True)
+            os.makedirs(dep_dir, exist_ok=True)
+        per_frame, l1 = [], []
+        for n, (idx, frame) in enumerate(items):
+            idx = int(idx)
+            if idx % 5 != 0 and idx not in kfs and n != len(items) - 1:
+                continue
+            if idx in kfs:
+                if idx not in own:
+                    raise ValueError(f"eval_rendering: keyframe tstamp {idx} has no view in the mapper")
+                v = own[idx]
+                A, b = v.exposure_a.detach(), v.exposure_b.detach()
+            else:
+                if idx not in row:
+                    raise ValueError(f"eval_rendering: frame {idx} has no pose in the trajectory")
+                w2c = torch.inverse(pose_vec_to_matrix(traj[row[idx]][None].to(self.device))[0])
+                img = self._frame_image(frame)
+                v = Camera(idx, img, torch.zeros(img.shape[-2:], device=self.device), w2c, self.fx, self.fy, self.cx, self.cy, idx, self.device)
+                A, b = torch.eye(3, device=self.device), torch.zeros(3, device=self.device)
+            gt = v.original_image
+            pkg = render(v, self.gaussians, self.background)
+            img = torch.clamp((pkg["render"].permute(1, 2, 0) @ A + b).permute(2, 0, 1), 0.0, 1.0).contiguous()
+            depth = pkg["depth"][0].cpu().numpy().copy()
+            if gtdepthdir is not None:
+                from .eval_dense import DEPTH_SCALE, read_depth_png
+                gd = read_depth_png(os.path.join(gtdepthdir, gtdepths[idx]), DEPTH_SCALE)
+                h, w = depth.shape
+                yi = np.minimum(np.floor(np.arange(h) * (gd.shape[0] / h)).astype(np.int64), gd.shape[0] - 1)      # cv2.INTER_NEAREST
+                xi = np.minimum(np.floor(np.arange(w) * (gd.shape[1] / w)).astype(np.int64), gd.shape[1] - 1)
+                gd = gd[yi][:, xi]
+                depth[gd <= 0] = 0
+                if idx in kfs:
+                    ok = depth > 0
+                    l1.append(float(np.abs(gd[ok] - depth[ok]).mean()) if ok.any() else float("nan"))
+            if out_dir is not None:
+                Image.fromarray((img.permute(1, 2, 0).cpu().numpy() * 255).astype(np.uint8)).save(os.path.join(img_dir, f"{idx:06d}.jpg"))
+                Image.fromarray(np.clip(depth * 6553.5, 0, 65535).astype(np.uint16)).save(os.path.join(dep_dir, f"{idx:06d}.png"))
+            mask = gt > 0
+            mse = ((img[mask] - gt[mask]) ** 2).mean() if mask.any() else torch.zeros((), device=self.device)
+            per_frame.append((idx, float(20 * torch.log10(1.0 / torch.sqrt(mse.clamp_min(1e-12)))), float(ssim(img, gt))))
+        m = max(1, len(per_frame))
+        out = {"mean_psnr": sum(r[1] for r in per_frame) / m, "mean_ssim": sum(r[2] for r in per_frame) / m,
+               "mean_l1": float(np.mean(l1)) if l1 else 0}
+        save = result_dir if result_dir is not None else out_dir
+        if save is not None:
+            d = os.path.join(save, "psnr", "after_opt")
+            os.makedirs(d, exist_ok=True)
+            with open(os.path.join(d, "final_result.json"), "w", encoding="utf-8") as f:
+                json.dump(out, f, indent=4)
+        out["per_frame"] = per_frame
+        return out
 
     @torch.no_grad()
     def trajectory(self):

@@ -6,7 +6,8 @@ implementation the tests compare this one with (same losses, same Adam arithmeti
 Per view and iteration:  cut3r_gs_activate -> cut3r_gs_preprocess / _bin / _render_forward -> loss kernels (+ cut3r_gs_map_coef /
 _refine_coef for the scalar algebra between their two passes) -> cut3r_gs_render_backward / _preprocess_backward ->
 cut3r_gs_activate_backward (gradient of theta accumulated over the views, 16 pose sums per view) -> cut3r_gs_pose_step; then ONE
-cut3r_gs_adam over all Gaussian parameters.
+cut3r_gs_adam over all Gaussian parameters.  `pose_estimator` (a pose against the frozen map, :123-177) ends its backward pass in
+cut3r_gs_pose_backward instead: dgeom -> the 16 pose sums in one kernel, no per-Gaussian gradient, no cut3r_gs_adam.
 
 With Training.compensate_exposure (gs_backend_per_frame.py:516, :992) three launches per rendered view join them: cut3r_exposure_forward
 between the rasteriser and the colour losses (pixel loss and SSIM then read the compensated image), cut3r_exposure_backward in place of
@@ -376,6 +377,75 @@ class FusedTrainer:
         self._run(body, iters, views, snapshot)
         for k in range(B):                                # update_pose: T <- exp(delta) T, delta <- 0
             check(lib.cut3r_gs_pose_step(_p(ps[k]), _p(sums[k]), 0.0, None, 0.0, 0.0, 2, _s()), "gs_pose_step (fold)")
+        self._store_poses(views, ps)
+
+    def _pose_backward(self, v, ps_v, g_color, g_depth, partials, sums_v):
+        """rasteriser backward of one view, then dgeom straight to the view's 16 pose sums (cut3r_gs_pose_backward): the backward pass of
+        an iteration that moves a pose against a frozen map.  sums_v is written, partials is scratch [cut3r_gs_pose_partial_rows(P), 16]"""
+        lib, P = self.lib, self._shape[0]
+        H, W = self._shape[1:]
+        cam, im, z = self._cam(v), self.img, self.zero_img
+        check(lib.cut3r_gs_render_backward(_p(self.ranges), _p(self.point_list), _p(self.geom), P, W, H, cam["tanx"], cam["tany"], _ZERO3,
+                                           _p(self.n_contrib), _p(self.aux), _p(im["alpha"]), _p(im["coord"]), _p(im["depth"]), _p(im["normal"]),
+                                           _p(g_color), _p(z), _p(z), _p(g_depth), _p(z), _p(z), _p(z), _p(self.dgeom),
+                                           _s()), "gs_render_backward")
+        check(lib.cut3r_gs_pose_backward(P, _p(self.means), _p(self.scales), _p(self.rots), _p(self.opac), _IDENTITY16, cam["proj"], W, H,
+                                         cam["tanx"], cam["tany"], 0.0, 1.0, _p(self.geom), _p(self.dgeom), _p(self.mp.gaussians.theta), _p(ps_v),
+                                         _p(partials), _p(sums_v), _s()), "gs_pose_backward")
+
+    def pose_estimator(self, view, iters, use_depth=False, pose_backward="fused"):
+        """GSMapper.pose_estimator's loop (gs_backend_per_frame.py:143-167): the Gaussians stay fixed, the view's increments take one Adam
+        step (both at opt_params.pose_lr) per iteration and are folded into the pose after every one.  Loss: 0.8 L1 + 0.2 (1 - SSIM), with
+        use_depth plus the mean of |1/d - 1/gt_d| over gt_d > 0.001 and d > 0.001 (the pixel-loss kernels with w_depth = 1; without it
+        view.depth is all zero, the mask empty and its clamped count 1).  pose_backward: "fused" = cut3r_gs_pose_backward (one kernel, no
+        per-Gaussian gradient in memory), "chain" = cut3r_gs_preprocess_backward + cut3r_gs_activate_backward(gtheta = NULL)."""
+        if pose_backward not in ("fused", "chain"):
+            raise ValueError(f"pose_backward must be 'fused' or 'chain', not {pose_backward!r}")
+        mp, lib = self.mp, self.lib
+        P = len(mp.gaussians)
+        views = [view]
+        H, W = self._image_size(views)
+        self._buffers(P, H, W)
+        ps = self._load_poses(views)
+        sums = torch.zeros(16, dtype=torch.float32, device=self.dev)
+        rows = int(lib.cut3r_gs_pose_partial_rows(P))
+        partials = torch.empty(rows, 16, dtype=torch.float32, device=self.dev) if pose_backward == "fused" else None
+        lr = float(mp.config["opt_params"]["pose_lr"])
+        w_depth = 1.0 if use_depth else 0.0
+        self.ssim_scale.fill_(-0.2 / (3 * H * W))
+        gt, z = view.original_image, self.zero_img
+        saved = {}
+
+        def snapshot(restore=False):
+            if restore:
+                ps.copy_(saved["ps"])
+            else:
+                saved["ps"] = ps.clone()
+        snapshot()
+
+        def body(it, exact):
+            cam, im = self._cam(view), self.img
+            K = cam["K"]
+            count = self._render(view, ps[0], exact)
+            check(lib.cut3r_pixel_loss_forward(_p(im["color"]), _p(gt), _p(im["depth"]), _p(view.depth), _p(z), H, W, K[0], K[1], K[2], K[3],
+                                               _p(self.sums), _s()), "pixel_loss_forward")
+            check(lib.cut3r_gs_map_coef(_p(self.sums), 0.8, w_depth, 0.0, 1.0, H, W, _p(self.coef), None, _s()), "gs_map_coef")
+            check(lib.cut3r_pixel_loss_backward(_p(im["color"]), _p(gt), _p(im["depth"]), _p(view.depth), _p(z), H, W, K[0], K[1], K[2], K[3],
+                                                _p(self.coef), _p(self.g_img), _p(self.g_depth), _s()), "pixel_loss_backward")
+            check(lib.cut3r_ssim_forward(_p(im["color"]), _p(gt), 3, H, W, _p(self.smap), _p(self.sd1), _p(self.sd2), _p(self.sd3), _s()),
+                  "ssim_forward")
+            check(lib.cut3r_ssim_backward(_p(im["color"]), _p(gt), _p(self.sd1), _p(self.sd2), _p(self.sd3), 3, H, W, _p(self.ssim_scale),
+                                          _p(self.g_ssim), _s()), "ssim_backward")
+            self.g_img.add_(self.g_ssim)
+            if partials is not None:
+                self._pose_backward(view, ps[0], self.g_img, self.g_depth, partials, sums)
+            else:
+                sums.zero_()
+                self._backward(view, ps[0], self.g_img, self.g_depth, 0.0, None, sums)
+            check(lib.cut3r_gs_pose_step(_p(ps[0]), _p(sums), 0.0, None, lr, lr, 1, _s()), "gs_pose_step")
+            return [count]
+
+        self._run(body, iters, views, snapshot)
         self._store_poses(views, ps)
 
     def global_BA(self, iteration_total, densify=True, densify_every=None, opacity_reset=True, seed=0, exposure=False):

@@ -52,6 +52,7 @@ class Cut3rSlam:
         self.tracked_only = False
         # hi2.py:47-48: the Gaussian mapper (cut3r_slam_amd.gs_mapper.GSMapper); None = tracking only (BASELINE configs 1-4)
         self.mapper = None
+        self.traj_full = None                  # terminate(fill=True): (tstamps [n], poses [n,7] c2w) of every frame from the first keyframe on
         self.gs_iter_num = self.config.get("Mapping", {}).get("itr_num", 100)
         # hi2.py:84 reads `self.keyframes.depth[updated_idx][mask] = depth[mask]` with a LIST index: an advanced-index copy, so the
         # reference never changes keyframes.depth and later windows chain on the tracker's own depths.  Default = that effective
@@ -216,7 +217,7 @@ class Cut3rSlam:
         flush()
 
     @torch.no_grad()
-    def terminate(self, add_kf=False, gap=30, finalize_iters=None, gaussian_retrain=False, retrain_iters=10000):
+    def terminate(self, add_kf=False, gap=30, finalize_iters=None, gaussian_retrain=False, retrain_iters=10000, fill=False, fill_iters=100):
         """hi2.py:152-229.  With the Gaussian mapper attached (`self.mapper`) the extra views go to `mapper.add_new_view`, the mapper
         finalises (`GSMapper.finalize`: a global BA of `finalize_iters` iterations, default the configured position_lr_max_steps as the
         reference's `max_steps`; 0 skips it) and its poses are written back (hi2.py:214-216); `gaussian_retrain` rebuilds the map from all
@@ -225,10 +226,17 @@ class Cut3rSlam:
         to the tracking resolution (bilinear, align_corners=False, hi2.py:198) and relocalised against the earlier keyframe by a
         2-view inference (TrackFrontend.predict, track_frontend.py:102-162).  The reference hands these views to
         `mapper.add_new_view`; tracking-only, they are returned: list of dicts (tstamp, pose [7] c2w, depth [H,W],
-        pointmap [h,w,3], conf [h,w], submap).  Returns (keyframes.pose as numpy [buffer,7], new views)."""
+        pointmap [h,w,3], conf [h,w], submap).  Returns (keyframes.pose as numpy [buffer,7], new views).
+        fill (hi2.py:218-221, needs the mapper and the kept frames): after the mapper has finalised, every frame from the first keyframe
+        on gets a pose against the frozen map (trajectory_filler.PoseTrajectoryFiller, `fill_iters` iterations per frame); the result stays
+        in `self.traj_full` = (tstamps [n], poses [n,7] c2w) -- the return value does not change."""
         kf = self.keyframes
         last = kf.counter.value
         views = []
+        if fill and not self.images:
+            raise RuntimeError("terminate(fill=True) needs the frames: set slam.keep_images = True before run()")
+        if fill and not (self.mapper is not None and getattr(self.mapper, "initialized", False)):
+            raise RuntimeError("terminate(fill=True) needs an initialised Gaussian mapper (slam.mapper)")
         if gaussian_retrain and self.mapper is not None and last > 1:        # hi2.py:155-170: a fresh map from every keyframe's pointmap
             n = last - 1
             pms = kf.submap_ds[:(n + 4) // 5, :-1].flatten(0, 1)[:n]
@@ -260,6 +268,9 @@ class Cut3rSlam:
             n = min(max(last - 1, 0), poses.shape[0])
             if n:
                 kf.set_poses_at(range(n), poses[:n].cpu().numpy())
+            if fill:
+                from .trajectory_filler import PoseTrajectoryFiller
+                self.traj_full = PoseTrajectoryFiller(self).run(self.images, iters=fill_iters)
         return kf.pose.numpy().copy(), views
 
     def trajectory(self):

@@ -123,8 +123,10 @@ def frame_timestamps(imagedir, start=0) -> np.ndarray:
     return np.array([float(re.findall(r"[+]?(?:\d*\.\d+|\d+)", x)[-1]) for x in natsorted(os.listdir(imagedir))[start:]])[..., np.newaxis]
 
 
-def save_trajectory(slam, imagedir, output, start=0, traj_full=None):
-    """demo_s.py:97-113: intrinsics.npy, traj_kf.txt ("%.4f" stamp + 7 x "%.7f" c2w pose), optional traj_full.txt"""
+def save_trajectory(slam, imagedir, output, start=0, traj_full=None, traj_full_index=None):
+    """demo_s.py:97-113: intrinsics.npy, traj_kf.txt ("%.4f" stamp + 7 x "%.7f" c2w pose), optional traj_full.txt (rows stamped with the
+    first len(traj_full) frames as the reference does, or -- traj_full_index, the frame index of every row, as
+    PoseTrajectoryFiller.run returns it -- with the frames the rows belong to, which differs when the first keyframe is not frame 0)"""
     t = slam.keyframes.counter.value - 1
     tstamps = slam.keyframes.tstamp[:t]
     poses_kf = slam.keyframes.pose[:t]
@@ -134,5 +136,6 @@ def save_trajectory(slam, imagedir, output, start=0, traj_full=None):
     ttraj_kf = np.concatenate([tstamps_kf, poses_kf.cpu().numpy()], axis=1)
     np.savetxt(os.path.join(output, "traj_kf.txt"), ttraj_kf, fmt="%.4f %.7f %.7f %.7f %.7f %.7f %.7f %.7f")
     if traj_full is not None:
-        np.savetxt(os.path.join(output, "traj_full.txt"), np.concatenate([tstamps_full[:len(traj_full)], traj_full], axis=1))
+        rows = tstamps_full[:len(traj_full)] if traj_full_index is None else tstamps_full[np.asarray(traj_full_index).astype(int)]
+        np.savetxt(os.path.join(output, "traj_full.txt"), np.concatenate([rows, traj_full], axis=1))
     return ttraj_kf

@@ -7,7 +7,9 @@
 Writes <output>/traj_kf.txt and <output>/intrinsics.npy exactly as the reference does (evo-compatible TUM rows); with --mesh also
 <output>/tsdf_mesh_w{W:.1f}.ply per --mesh-weight, the reference's post-run mesh (TSDF fusion on the GPU, cut3r_slam_amd/tsdf.py); with
 --eval-dense --gtdepthdir G --gt-traj T also <output>/3D_eval_results.txt, the dense point-cloud metrics of the keyframe depths against
-the GT depth maps (scripts/eval7_scenes_dense.py, cut3r_slam_amd/eval_dense.py).  The viewers are out of scope:
+the GT depth maps (scripts/eval7_scenes_dense.py, cut3r_slam_amd/eval_dense.py); with --fill (implies --gs) also <output>/traj_full.txt,
+a pose for every frame from the first keyframe on (hislam2/util/trajectory_filler.py), and with --eval-render
+<output>/psnr/after_opt/final_result.json and <output>/renders/ (gaussian/utils/eval_utils.py:14-105).  The viewers are out of scope:
 --droidvis/--gsvis/--posedir/--weights are accepted and ignored, and so is --gtdepthdir without --eval-dense.  Without a checkpoint,
 `--synthetic-weights` runs the production-shape network with seeded random weights (throughput / plumbing runs only).
 """
@@ -72,6 +74,12 @@ def main(argv=None):
                    "position_lr_max_steps, as the reference; 0 skips it)")
     p.add_argument("--gs", action="store_true", help="attach the Gaussian-splatting mapper (hislam2/hi2.py:47-48 always does; needs the "
                    "Mapping / Training / opt_params sections of the config, config/scannet_config.yaml:44-79)")
+    p.add_argument("--fill", action="store_true", help="after the run, register every non-keyframe against the finished Gaussian map "
+                   "(hislam2/util/trajectory_filler.py) -> <output>/traj_full.txt; implies --gs and keeps the frames on the device")
+    p.add_argument("--fill-iters", type=int, default=100, help="pose iterations per filled frame (the reference: 100)")
+    p.add_argument("--eval-render", action="store_true", help="PSNR / SSIM (/ depth L1 of the keyframes with --gtdepthdir) of renderings of "
+                   "every 5th frame, the keyframes and the last frame (gaussian/utils/eval_utils.py:14-105; needs --fill for the poses of "
+                   "the non-keyframes) -> <output>/psnr/after_opt/final_result.json and <output>/renders/")
     p.add_argument("--mesh", action="store_true", help="TSDF-fuse the keyframes and write <output>/tsdf_mesh_w{W:.1f}.ply per weight threshold "
                    "(scripts/run_replica.py:40-52 + tsdf_integrate.py)")
     p.add_argument("--voxel-size", type=float, default=0.03, help="TSDF voxel size in scene units (tsdf_integrate.py default)")
@@ -97,6 +105,11 @@ def main(argv=None):
     p.add_argument("--dense-source", choices=("auto", "tracker", "mapper"), default="auto",
                    help="depth maps of --eval-dense; auto: the Gaussian map's keyframe renders with --gs, else the tracked keyframes")
     args = p.parse_args(argv)
+    if args.eval_render and not args.fill:
+        p.error("--eval-render needs --fill (the poses of the frames between the keyframes)")
+    if args.fill_iters <= 0:
+        p.error("--fill-iters must be > 0")
+    args.gs = args.gs or args.fill
     if args.eval_dense and not (args.gtdepthdir and args.gt_traj):
         p.error("--eval-dense needs --gtdepthdir and --gt-traj")
     if args.gt_depth_scale <= 0 or args.dense_depth_trunc <= 0:
@@ -144,6 +157,7 @@ def main(argv=None):
 
     def make_slam(image_ds, intr_ds):
         s_ = Cut3rSlam(model, cfg, (image_ds.shape[2], image_ds.shape[3]), buffer=buffer, device=args.device)
+        s_.keep_images = args.fill
         if args.gs:
             from cut3r_slam_amd.gs_mapper import GSMapper
             if "Training" not in cfg or "opt_params" not in cfg:
@@ -180,7 +194,19 @@ def main(argv=None):
     torch.cuda.synchronize()
     traj = stream.save_trajectory(slam, args.imagedir, args.output, start=args.start)
     if slam.mapper is not None and slam.mapper.viewpoints:
-        slam.terminate(add_kf=False, finalize_iters=args.gs_final_iters)  # demo_s.py:171 (the trajectory above is the tracker's, as demo_s.py:168-169)
+        fill = args.fill and getattr(slam.mapper, "initialized", False)
+        # demo_s.py:171 (the keyframe trajectory above is the tracker's, as demo_s.py:168-169)
+        slam.terminate(add_kf=False, finalize_iters=args.gs_final_iters, fill=fill, fill_iters=args.fill_iters)
+        if fill:
+            ts_full, poses_full = slam.traj_full
+            stream.save_trajectory(slam, args.imagedir, args.output, start=args.start, traj_full=poses_full, traj_full_index=ts_full)
+            print(f"filled trajectory: {len(poses_full)} frames -> {args.output}/traj_full.txt")
+            if args.eval_render:
+                n_kf = slam.keyframes.counter.value - 1
+                er = slam.mapper.eval_rendering(slam.images, ts_full, poses_full, slam.keyframes.tstamp[:n_kf],
+                                                gtdepthdir=args.gtdepthdir, out_dir=args.output)
+                print(f"render eval over {len(er['per_frame'])} frames: PSNR {er['mean_psnr']:.2f} dB, SSIM {er['mean_ssim']:.4f}, depth L1 "
+                      f"{er['mean_l1']:.4f} -> {args.output}/psnr/after_opt/final_result.json")
         ev = slam.mapper.eval_rendering_kf()                              # demo_s.py:175-190 evaluates the renderings of the keyframes
         slam.mapper.save(os.path.join(args.output, "gaussians.safetensors"))
         print(f"GS mapper: {len(slam.mapper.gaussians)} Gaussians, {len(slam.mapper.viewpoints)} keyframes, PSNR {ev['mean_psnr']:.2f} dB, "

@@ -437,7 +437,25 @@ int cut3r_gs_preprocess_backward(int P, const float* means, const float* scales,
  *   exposure_partial_rows: the number of those rows (-1 for a size the launchers refuse: 1 is a valid count).
  *   gs_exposure_step:  the 12 gradients = the sum of the `rows` partial rows in a fixed order, then one torch.optim.Adam step of A and b
  *                      (betas 0.9 / 0.999, eps 1e-8, step size lr / bc1, the step count kept in the state).
- * H * W must fit an int. */
+ * H * W must fit an int.
+ * Pose-only backward against a frozen map (gs_backend_per_frame.py:123-177 pose_estimator, whose `loss.backward()` reaches only
+ * cam_trans_delta / cam_rot_delta; run for every non-keyframe by util/trajectory_filler.py:60-85):
+ *   gs_pose_backward:  dgeom [P,32] (cut3r_gs_render_backward) -> pose_sums [16] = M (9) | s (3) | r (4), the sums
+ *                      cut3r_gs_activate_backward(gtheta = NULL) accumulates after cut3r_gs_preprocess_backward -- in ONE kernel that writes
+ *                      no per-Gaussian gradient, plus a fixed-order finish.  means / scales / rots / opacities: cut3r_gs_activate's outputs
+ *                      for theta and pose_state; camera arguments as cut3r_gs_preprocess_backward.  NO spherical-harmonics arguments:
+ *                      colour must be view-independent (sh_degree 0 with one coefficient, or precomputed colours), where it has no
+ *                      gradient to the mean -- so no campos either.  Gaussians culled by the forward pass (geom radius <= 0) contribute
+ *                      exactly 0.  partials [cut3r_gs_pose_partial_rows(P), 16]: scratch, one row per workgroup, every row written (no
+ *                      zeroing needed); pose_sums is WRITTEN (not accumulated) as the sum of the rows in a fixed order.  No atomics: the
+ *                      same inputs give the same bits.  Each per-Gaussian term is formed in fp64 and rounded once, so every sum is within
+ *                      n_visible * 2^-24 * sum |term| of the exact sum of the per-Gaussian gradients' contraction.
+ *   gs_pose_partial_rows: the number of those rows (-1 for P <= 0). */
+int cut3r_gs_pose_backward(int P, const float* means, const float* scales, const float* rots, const float* opacities,
+                           const float* viewmatrix_host, const float* projmatrix_host, int W, int H, float tanfovx, float tanfovy,
+                           float kernel_size, float scale_modifier, const float* geom, const float* dgeom, const float* theta,
+                           const float* pose_state, float* partials, float* pose_sums, void* stream);
+long long cut3r_gs_pose_partial_rows(int P);
 int cut3r_gs_activate(int P, const float* theta, const float* pose_state, float* means, float* scales, float* rots, float* opac, float* shs,
                       void* stream);
 int cut3r_gs_activate_backward(int P, const float* theta, const float* pose_state, const float* d_means, const float* d_scales,
