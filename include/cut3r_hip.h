@@ -257,9 +257,14 @@ int cut3r_lie_adj(int group, const float* x, const float* a, float* out, int n, 
  * (hislam2/track_backend.py:256-299; lr 5e-4, `iteration` steps) and the pointmap rewrite (:301-310).
  * first/last: device pointers to slot 0 / slot 5 of the [B][6][N][3] submap store (sub_stride = floats between
  * consecutive submaps); mask: uint8 [B-1,N] (conf of `last` > 0) or NULL; cur/cur_lc: [N,3] current pointmap in the
- * global frame / in the matched submap's frame.  xi,adam_m,adam_v: [B,6] (row 0 unused, zero-initialised by the caller),
- * T: [B,12] row-major 3x4 (identity-initialised); workspace: cut3r_lc_workspace_floats(B,N) floats; loss_out: NULL or
- * float[iters].  Two launches per iteration, deterministic (no float atomics). */
+ * global frame / in the matched submap's frame.  xi,adam_m,adam_v: [B,6], T: [B,12] row-major 3x4: the caller's state,
+ * read and updated in place.  A fresh optimisation passes xi = adam_m = adam_v = 0 and T = identity; a resumed state is
+ * accepted as long as T = matrix(exp(xi)) row by row (T is what the residuals are evaluated with, xi what the step is
+ * taken from).  Row 0 is the fixed identity: T row 0 is read (pass the identity), row 0 of xi, adam_m, adam_v and T is
+ * never written.  The step count of Adam's bias correction restarts at 1 in every call, whatever the state.
+ * workspace: cut3r_lc_workspace_floats(B,N) floats, written before it is read (rows of 28 floats per pair and block of
+ * 2048 points, 25 used: after the call it holds the last iteration's partial sums); loss_out: NULL or float[iters].
+ * Two launches per iteration, deterministic (no float atomics). */
 int cut3r_lc_workspace_floats(int B, int N);
 int cut3r_lc_optimize(const float* first, const float* last, long long sub_stride, const unsigned char* mask, const float* cur,
                       const float* cur_lc, int B, int N, long long n_masked, int iters, float lr, float* xi, float* adam_m,
@@ -268,8 +273,9 @@ int cut3r_lc_optimize(const float* first, const float* last, long long sub_strid
  * chain term + the matched-submap term + the current-vs-lc term, Adam over `_align_lie` AND `matched_lie`).  The objective
  * is a LIST of L1 terms  w * sum_n | T[ia] a_n - T[ic] c_n |_1  over [N,3] point arrays; T[0] is the fixed identity, every
  * other row of T [P,12] is exp of a row of xi [P,6] and is optimised.  terms_dev: DEVICE array of n_terms cut3r_lc_term.
- * workspace: cut3r_lc_workspace_floats(n_terms, N) floats.  xi/adam_m/adam_v zero- and T identity-initialised by the
- * caller.  Two launches per iteration, deterministic. */
+ * workspace: cut3r_lc_workspace_floats(n_terms, N) floats.  xi/adam_m/adam_v/T [P,..]: the caller's state, under the
+ * same rules as cut3r_lc_optimize (zero / identity for a fresh run, else T = matrix(exp(xi)); row 0 read, never
+ * written; bias correction restarts at step 1).  Two launches per iteration, deterministic. */
 typedef struct cut3r_lc_term {
     const float* a;              /* [N,3] points moved by T[ia] */
     const float* c;              /* [N,3] points moved by T[ic] */
