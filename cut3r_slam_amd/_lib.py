@@ -184,13 +184,24 @@ SIGNATURES = {
     "cut3r_voxel_downsample_workspace_bytes": [c_int],
     "cut3r_voxel_downsample_count": [c_void_p, c_int, C.c_double, c_void_p, c_void_p, c_void_p, c_ll, c_void_p, c_void_p],
     "cut3r_voxel_downsample_emit": [c_void_p, c_void_p, c_int, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_ll, c_ll, c_void_p],
+    "cut3r_mesh_faces_check": [c_void_p, c_int, c_int, c_void_p, c_void_p],
+    "cut3r_mesh_cluster_workspace_bytes": [c_int, c_int],
+    "cut3r_mesh_cluster_count": [c_void_p, c_int, c_int, C.c_double, c_void_p, c_void_p, c_void_p, c_ll, c_void_p, c_void_p],
+    "cut3r_mesh_cluster_faces": [c_void_p, c_int, c_int, c_ll, c_int, c_void_p, c_ll, c_void_p, c_void_p, c_void_p],
+    "cut3r_mesh_cluster_emit": [c_void_p, c_void_p, c_int, c_int, c_ll, c_void_p, c_ll] + [c_void_p] * 5 + [c_ll] * 4 + [c_void_p, c_void_p],
+    "cut3r_mesh_label_init": [c_void_p, c_void_p, c_int, c_void_p],
+    "cut3r_mesh_label_round": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "cut3r_mesh_components_workspace_bytes": [c_int, c_int],
+    "cut3r_mesh_components_count": [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_ll, c_void_p, c_void_p],
+    "cut3r_mesh_components_emit": [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_ll] + [c_void_p] * 6 + [c_ll] * 6 + [c_void_p],
 }
 RESTYPES = {"cut3r_ba_workspace_floats": c_ll, "cut3r_gs_workspace_bytes": c_ll, "cut3r_schur_mono_prior_workspace_floats": c_ll,
             "cut3r_knn3_grid_workspace_bytes": c_ll, "cut3r_tsdf_mesh_workspace_bytes": c_ll, "cut3r_tsdf_sparse_assign_workspace_bytes": c_ll,
             "cut3r_tsdf_sparse_mesh_workspace_bytes": c_ll, "cut3r_mesh_cdf_workspace_bytes": c_ll,
             "cut3r_nn_workspace_bytes": c_ll, "cut3r_icp_moments_workspace_bytes": c_ll, "cut3r_mesh_raster_workspace_bytes": c_ll,
             "cut3r_depth_l1_workspace_bytes": c_ll, "cut3r_depth_cloud_workspace_bytes": c_ll, "cut3r_cloud_bounds_workspace_bytes": c_ll,
-            "cut3r_voxel_downsample_workspace_bytes": c_ll, "cut3r_exposure_partial_rows": c_ll, "cut3r_gs_pose_partial_rows": c_ll}
+            "cut3r_voxel_downsample_workspace_bytes": c_ll, "cut3r_exposure_partial_rows": c_ll, "cut3r_gs_pose_partial_rows": c_ll,
+            "cut3r_mesh_cluster_workspace_bytes": c_ll, "cut3r_mesh_components_workspace_bytes": c_ll}
 
 _lib = None
 

@@ -1223,3 +1223,178 @@ def voxel_downsample(points, voxel, colors=None):
     check(lib.cut3r_voxel_downsample_emit(_p(points), _p(colors), N, _p(ws), nbytes, _p(out), _p(out_col), _p(cnt), M, M, _stream()),
           "cut3r_voxel_downsample_emit")
     return out, out_col, cnt
+
+
+# ------------------------------------------------------------------------------------------------ mesh clean-up after the extraction
+class _StageClock:
+    """HIP events between the stages of one call (tools/bench_mesh_clean.py); off unless a `timing` dict is passed.  mark(name) closes
+    the stage `name` on the stream; inside(n) hands n events to a C entry point that records them between its own stages."""
+
+    def __init__(self, timing):
+        self.timing, self.marks = timing, []
+
+    def mark(self, name):
+        if self.timing is not None:
+            e = torch.cuda.Event(enable_timing=True)
+            e.record()
+            self.marks.append((name, e))
+
+    def inside(self, *names):
+        if self.timing is None:
+            return C.c_void_p(0)
+        for n in names:
+            self.mark(n)                                     # recorded once here so that the handle exists; the callee records it again
+        return (C.c_void_p * len(names))(*[C.c_void_p(e.cuda_event) for _, e in self.marks[-len(names):]])
+
+    def close(self):
+        if self.timing is None:
+            return
+        torch.cuda.synchronize()
+        for (_, a), (name, b) in zip(self.marks[:-1], self.marks[1:]):
+            if name != "host":                               # "host": the stretch that ends after a read-back, not a stage
+                self.timing[name] = self.timing.get(name, 0.0) + a.elapsed_time(b)
+
+
+def _mesh(verts, colors, faces):
+    _cuda(verts, colors, faces)
+    _req(verts.dim() == 2 and verts.shape[1] == 3 and verts.dtype == F32 and verts.is_contiguous(), "vertices: contiguous fp32 [V,3]")
+    _req(faces.dim() == 2 and faces.shape[1] == 3 and faces.dtype == torch.int32 and faces.is_contiguous(), "faces: contiguous int32 [F,3]")
+    V, F = verts.shape[0], faces.shape[0]
+    _req(0 < V < 2 ** 31 and 0 < F < 2 ** 31, "mesh: 1 .. 2^31 - 1 vertices and faces")
+    if colors is not None:
+        _req(colors.shape == (V, 3) and colors.dtype == torch.uint8 and colors.is_contiguous(), "colors: contiguous uint8 [V,3]")
+    return V, F
+
+
+def mesh_faces_check(faces, V):
+    """ValueError when an index of faces int32 [F,3] lies outside [0, V): a flag kernel, run before anything gathers through the faces"""
+    bad = torch.empty(1, dtype=torch.int32, device=faces.device)
+    check(_lib.load().cut3r_mesh_faces_check(_p(faces), faces.shape[0], V, _p(bad), _stream()), "cut3r_mesh_faces_check")
+    _req(int(bad.item()) == 0, f"faces: an index outside [0, {V})")
+
+
+def _capacity(capacity, need_v, need_f):
+    cap_v, cap_f = (need_v, need_f) if capacity is None else (int(capacity[0]), int(capacity[1]))
+    _req(cap_v >= need_v and cap_f >= need_f, f"capacity ({cap_v}, {cap_f}) below the counted totals ({need_v}, {need_f})")
+    return cap_v, cap_f
+
+
+def mesh_cluster(verts, colors, faces, cell, passes=0, capacity=None, timing=None):
+    """vertex clustering of a mesh on the GPU (include/cut3r_hip.h, the mesh clean-up block, states the definition) -> dict: vertices fp32
+    [V',3], colors u8 [V',3] or None, faces int32 [F',3], vertex_map int32 [V], face_map int32 [F'] and the counts clusters, degenerate,
+    duplicate, unreferenced.  passes: 0 chooses the sort passes of the de-duplication, 1 / 2 force them (the result is the same).
+    capacity=(rows of vertices, rows of faces) the outputs are allocated with (default: the counted totals).  ValueError before any sort
+    or gather: sizes, a face index outside [0, V), non-finite vertices, cell <= 0 or not finite, 2^21 cells or more on an axis,
+    a capacity below the counted totals."""
+    V, F = _mesh(verts, colors, faces)
+    cell = float(cell)
+    _req(cell > 0 and cell < float("inf"), "cell must be > 0 and finite")
+    _req(passes in (0, 1, 2), "passes: 0, 1 or 2")
+    clock = _StageClock(timing)
+    clock.mark("host")
+    mesh_faces_check(faces, V)
+    clock.mark("face check")
+    lo, hi = cloud_bounds(verts)
+    top = torch.floor((hi.double() - (lo.double() - cell * 0.5)) / cell)
+    _req(bool((top <= VOXEL_MAX_INDEX).all()), f"mesh_cluster: the extent spans more than 2^21 cells of {cell:g}")
+    dev = verts.device
+    lib = _lib.load()
+    nbytes = lib.cut3r_mesh_cluster_workspace_bytes(V, F)
+    _req(nbytes > 0, "mesh_cluster workspace")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    totals = torch.empty(4, dtype=torch.int64, device=dev)
+    clock.mark("host")
+    check(lib.cut3r_mesh_cluster_count(_p(verts), V, F, cell, C.c_void_p(lo.data_ptr()), C.c_void_p(hi.data_ptr()), _p(ws), nbytes, _p(totals),
+                                       _stream()), "cut3r_mesh_cluster_count")
+    clock.mark("keys + sort")
+    M = int(totals[0].item())
+    if passes == 1:
+        _req(3 * max(1, (M - 1).bit_length()) <= 64, f"passes=1: three ids below {M} do not fit one 64-bit key")
+    clock.mark("host")
+    ev = clock.inside("remap", "de-duplication")
+    check(lib.cut3r_mesh_cluster_faces(_p(faces), V, F, M, passes, _p(ws), nbytes, _p(totals), ev, _stream()), "cut3r_mesh_cluster_faces")
+    clock.mark("compaction")
+    Fo, Vo, deg, dup = (int(x) for x in totals.cpu())
+    cap_v, cap_f = _capacity(capacity, Vo, Fo)
+    out_v = torch.empty(cap_v, 3, dtype=F32, device=dev)
+    out_c = torch.empty(cap_v, 3, dtype=torch.uint8, device=dev) if colors is not None else None
+    out_f = torch.empty(cap_f, 3, dtype=torch.int32, device=dev)
+    vmap = torch.empty(V, dtype=torch.int32, device=dev)
+    fmap = torch.empty(cap_f, dtype=torch.int32, device=dev)
+    clock.mark("host")
+    ev = clock.inside("means")
+    check(lib.cut3r_mesh_cluster_emit(_p(verts), _p(colors), V, F, M, _p(ws), nbytes, _p(out_v), _p(out_c), _p(out_f), _p(vmap), _p(fmap), Vo, Fo,
+                                      cap_v, cap_f, ev, _stream()), "cut3r_mesh_cluster_emit")
+    clock.mark("compaction")
+    clock.close()
+    return {"vertices": out_v[:Vo], "colors": None if out_c is None else out_c[:Vo], "faces": out_f[:Fo], "vertex_map": vmap, "face_map": fmap[:Fo],
+            "clusters": M, "degenerate": deg, "duplicate": dup, "unreferenced": M - Vo}
+
+
+def mesh_labels(faces, V, timing=None):
+    """(labels int32 [V], rounds): label(v) = the smallest vertex index of v's connected component (two vertices are connected when a face
+    holds both).  Min-label hooking and pointer jumping, one launch each per round; the loop runs here, reading a device word back after
+    every round, and stops when a round changes nothing.  RuntimeError past V rounds (every other round removes a label, so V suffice)."""
+    _cuda(faces)
+    _req(faces.dim() == 2 and faces.shape[1] == 3 and faces.dtype == torch.int32 and faces.is_contiguous(), "faces: contiguous int32 [F,3]")
+    V, F = int(V), faces.shape[0]
+    _req(0 < V < 2 ** 31 and 0 < F < 2 ** 31, "mesh: 1 .. 2^31 - 1 vertices and faces")
+    dev = faces.device
+    lib = _lib.load()
+    labels = torch.empty(V, dtype=torch.int32, device=dev)
+    scratch = torch.empty(V, dtype=torch.int32, device=dev)
+    changed = torch.empty(1, dtype=torch.int32, device=dev)
+    clock = _StageClock(timing)
+    clock.mark("host")
+    check(lib.cut3r_mesh_label_init(_p(labels), _p(scratch), V, _stream()), "cut3r_mesh_label_init")
+    rounds = 0
+    while True:
+        if rounds >= V:
+            raise RuntimeError(f"mesh_labels: no fixed point after {rounds} rounds over {V} vertices")
+        check(lib.cut3r_mesh_label_round(_p(faces), V, F, _p(labels), _p(scratch), _p(changed), _stream()), "cut3r_mesh_label_round")
+        rounds += 1
+        if int(changed.item()) == 0:
+            break
+    clock.mark("labelling")
+    clock.close()
+    return labels, rounds
+
+
+def mesh_components(verts, colors, faces, min_faces=None, keep_largest=None, capacity=None, timing=None):
+    """small-component removal of a mesh on the GPU (include/cut3r_hip.h states the definition) -> dict: vertices, colors, faces,
+    vertex_map int32 [V], face_map int32 [F'], labels int32 [V], components int32 [K,2] = (label, size) of the kept components by (size
+    descending, label ascending), n_components, rounds.  Exactly one of min_faces >= 1 (components of at least that many faces stay) and
+    keep_largest >= 1.  ValueError as mesh_cluster, and for the options."""
+    V, F = _mesh(verts, colors, faces)
+    _req((min_faces is None) != (keep_largest is None), "exactly one of min_faces and keep_largest")
+    opt = int(min_faces if min_faces is not None else keep_largest)
+    _req(1 <= opt < 2 ** 31, "min_faces / keep_largest must be >= 1")
+    mesh_faces_check(faces, V)
+    cloud_bounds(verts)                                      # refuses non-finite vertices
+    dev = verts.device
+    lib = _lib.load()
+    nbytes = lib.cut3r_mesh_components_workspace_bytes(V, F)
+    _req(nbytes > 0, "mesh_components workspace")
+    labels, rounds = mesh_labels(faces, V, timing)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    totals = torch.empty(4, dtype=torch.int64, device=dev)
+    clock = _StageClock(timing)
+    clock.mark("host")
+    check(lib.cut3r_mesh_components_count(_p(faces), V, F, _p(labels), opt if min_faces is not None else 0, opt if keep_largest is not None else 0,
+                                          _p(ws), nbytes, _p(totals), _stream()), "cut3r_mesh_components_count")
+    n_comp, K, Fo, Vo = (int(x) for x in totals.cpu())
+    cap_v, cap_f = _capacity(capacity, Vo, Fo)
+    out_v = torch.empty(cap_v, 3, dtype=F32, device=dev)
+    out_c = torch.empty(cap_v, 3, dtype=torch.uint8, device=dev) if colors is not None else None
+    out_f = torch.empty(cap_f, 3, dtype=torch.int32, device=dev)
+    vmap = torch.empty(V, dtype=torch.int32, device=dev)
+    fmap = torch.empty(cap_f, dtype=torch.int32, device=dev)
+    comps = torch.empty(K, 2, dtype=torch.int32, device=dev)
+    check(lib.cut3r_mesh_components_emit(_p(verts), _p(colors), V, _p(faces), F, _p(ws), nbytes, _p(out_v), _p(out_c), _p(out_f), _p(vmap), _p(fmap),
+                                         _p(comps), Vo, Fo, K, cap_v, cap_f, K, _stream()), "cut3r_mesh_components_emit")
+    clock.mark("filter")
+    clock.close()
+    if timing is not None:
+        timing["rounds"] = rounds
+    return {"vertices": out_v[:Vo], "colors": None if out_c is None else out_c[:Vo], "faces": out_f[:Fo], "vertex_map": vmap, "face_map": fmap[:Fo],
+            "labels": labels, "components": comps, "n_components": n_comp, "rounds": rounds}

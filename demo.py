@@ -5,7 +5,9 @@
                    --output outputs/room0 [--kf_every 10] [--ckpt_path checkpoints/cut3r_512_dpt_4_64.pth]
 
 Writes <output>/traj_kf.txt and <output>/intrinsics.npy exactly as the reference does (evo-compatible TUM rows); with --mesh also
-<output>/tsdf_mesh_w{W:.1f}.ply per --mesh-weight, the reference's post-run mesh (TSDF fusion on the GPU, cut3r_slam_amd/tsdf.py); with
+<output>/tsdf_mesh_w{W:.1f}.ply per --mesh-weight, the reference's post-run mesh (TSDF fusion on the GPU, cut3r_slam_amd/tsdf.py), and with
+--mesh-simplify CELL and / or --mesh-min-faces N next to each of them tsdf_mesh_w{W:.1f}_clean.ply, that mesh after vertex clustering and
+small-component removal (cut3r_slam_amd/mesh_clean.py; scored into eval_recon_w{W:.1f}_clean.txt with --gt-mesh); with
 --eval-dense --gtdepthdir G --gt-traj T also <output>/3D_eval_results.txt, the dense point-cloud metrics of the keyframe depths against
 the GT depth maps (scripts/eval7_scenes_dense.py, cut3r_slam_amd/eval_dense.py); with --fill (implies --gs) also <output>/traj_full.txt,
 a pose for every frame from the first keyframe on (hislam2/util/trajectory_filler.py), and with --eval-render
@@ -89,6 +91,10 @@ def main(argv=None):
                    help="auto: the Gaussian map's keyframe renders with --gs, else the tracked keyframes")
     p.add_argument("--mesh-sparse", action="store_true", help="with --mesh: fuse into the sparse brick volume (bricks of 8^3 voxels near "
                    "surfaces only: the same mesh, memory by surface area, no 2^31-voxel limit)")
+    p.add_argument("--mesh-simplify", type=float, default=None, metavar="CELL", help="with --mesh: also write tsdf_mesh_w{W:.1f}_clean.ply, "
+                   "the mesh after vertex clustering at this cell size (cut3r_slam_amd/mesh_clean.py)")
+    p.add_argument("--mesh-min-faces", type=int, default=None, metavar="N", help="with --mesh: also write tsdf_mesh_w{W:.1f}_clean.ply, the "
+                   "mesh without the connected components of fewer than N faces (after --mesh-simplify when both are given)")
     p.add_argument("--gt-mesh", type=str, default=None, help="score every mesh written against this GT mesh (scripts/eval_recon.py "
                    "--eval_3d) -> <output>/eval_recon_w{W:.1f}.txt; needs --mesh")
     p.add_argument("--gt-traj", type=str, default=None, help="TUM ground-truth trajectory: the Sim(3) of traj_kf.txt onto it is applied to "
@@ -118,6 +124,12 @@ def main(argv=None):
         p.error("--gt-mesh needs --mesh")
     if args.mesh_sparse and not args.mesh:
         p.error("--mesh-sparse needs --mesh")
+    if (args.mesh_simplify is not None or args.mesh_min_faces is not None) and not args.mesh:
+        p.error("--mesh-simplify and --mesh-min-faces need --mesh")
+    if args.mesh_simplify is not None and not (0 < args.mesh_simplify < float("inf")):
+        p.error("--mesh-simplify must be > 0 and finite")
+    if args.mesh_min_faces is not None and args.mesh_min_faces < 1:
+        p.error("--mesh-min-faces must be >= 1")
     if args.eval_2d and not args.gt_mesh:
         p.error("--eval-2d needs --gt-mesh")
     if args.gt_unseen and not args.eval_2d:
@@ -223,6 +235,20 @@ def main(argv=None):
                   f"({vol.nbytes / 1e9:.2f} GB), allocated and integrated in {1e3 * t_int:.1f} ms")
         else:
             print(f"TSDF: {X}x{Y}x{Z} voxels of {vol.voxel_size:g} ({vol.nbytes / 1e9:.2f} GB), integrated in {1e3 * t_int:.1f} ms")
+        def score(mesh, w, tag):
+            from cut3r_slam_amd import eval_recon as ER
+            if args.gt_traj:
+                mesh = ER.apply_transform(mesh, ER.sim3_from_trajectories(os.path.join(args.output, "traj_kf.txt"), args.gt_traj))
+            res = ER.calc_3d_metric(mesh, args.gt_mesh)
+            if args.eval_2d:
+                import numpy as np
+                res.update(ER.calc_2d_metric(mesh, args.gt_mesh, n_imgs=args.n_imgs,
+                                             unseen=np.load(args.gt_unseen) if args.gt_unseen else None))
+            with open(os.path.join(args.output, f"eval_recon_w{w:.1f}{tag}.txt"), "w") as fh:
+                fh.write(f"{res}")
+            print(f"  vs {args.gt_mesh}: accuracy {res['accuracy']:.3f} cm, completion {res['completion']:.3f} cm, "
+                  f"completion ratio {res['completion_ratio']:.2f} %" + (f", depth L1 {res['depth l1']:.3f} cm" if args.eval_2d else ""))
+
         for w in args.mesh_weight:
             t_ext = time.time()
             mesh = vol.extract_mesh(w)
@@ -231,18 +257,17 @@ def main(argv=None):
             write_ply(path, mesh)
             print(f"mesh w >= {w:g}: {len(mesh.vertices)} vertices, {len(mesh.faces)} faces, extracted in {1e3 * t_ext:.1f} ms -> {path}")
             if args.gt_mesh and len(mesh.faces):
-                from cut3r_slam_amd import eval_recon as ER
-                if args.gt_traj:
-                    mesh = ER.apply_transform(mesh, ER.sim3_from_trajectories(os.path.join(args.output, "traj_kf.txt"), args.gt_traj))
-                res = ER.calc_3d_metric(mesh, args.gt_mesh)
-                if args.eval_2d:
-                    import numpy as np
-                    res.update(ER.calc_2d_metric(mesh, args.gt_mesh, n_imgs=args.n_imgs,
-                                                 unseen=np.load(args.gt_unseen) if args.gt_unseen else None))
-                with open(os.path.join(args.output, f"eval_recon_w{w:.1f}.txt"), "w") as fh:
-                    fh.write(f"{res}")
-                print(f"  vs {args.gt_mesh}: accuracy {res['accuracy']:.3f} cm, completion {res['completion']:.3f} cm, "
-                      f"completion ratio {res['completion_ratio']:.2f} %" + (f", depth L1 {res['depth l1']:.3f} cm" if args.eval_2d else ""))
+                score(mesh, w, "")
+            if args.mesh_simplify is not None or args.mesh_min_faces is not None:
+                from cut3r_slam_amd import mesh_clean
+                t_cl = time.time()
+                cleaned = mesh_clean.clean(mesh, cell=args.mesh_simplify, min_faces=args.mesh_min_faces)[0] if len(mesh.faces) else mesh
+                t_cl = time.time() - t_cl
+                path = os.path.join(args.output, f"tsdf_mesh_w{w:.1f}_clean.ply")
+                write_ply(path, cleaned)
+                print(f"  cleaned: {len(cleaned.vertices)} vertices, {len(cleaned.faces)} faces in {1e3 * t_cl:.1f} ms -> {path}")
+                if args.gt_mesh and len(cleaned.faces):
+                    score(cleaned, w, "_clean")
     if args.eval_dense:
         from cut3r_slam_amd import eval_dense as ED
         est = ED.from_slam(slam, args.dense_source, stream.frame_timestamps(args.imagedir, args.start))

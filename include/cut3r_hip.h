@@ -685,6 +685,56 @@ int cut3r_voxel_downsample_count(const float* points, int N, double voxel, const
 int cut3r_voxel_downsample_emit(const float* points, const unsigned char* colors, int N, const void* workspace, long long workspace_bytes,
                                 float* out_points, unsigned char* out_colors, int* out_counts, long long M, long long capacity, void* stream);
 
+/* ---- Mesh clean-up after the extraction (csrc/mesh_clean.hip) ---------------------------------------------------------------------------
+ * A mesh is verts [V,3] fp32, colors [V,3] u8 (or NULL) and faces [F,3] int32 on the device, 1 <= V, F <= 2^31 - 1.  Every output is one
+ * definite set of bits: stable sorts, count -> scan -> emit compactions in input order, and integer atomics only.
+ * faces_check runs first: *bad (device int) = 1 when a face index lies outside [0, V), else 0.  The kernels below skip such a face
+ * instead of reading out of bounds, but the callers refuse the mesh. */
+int cut3r_mesh_faces_check(const int* faces, int F, int V, int* bad, void* stream);
+/* Vertex clustering (Open3D simplify_vertex_clustering with averaged positions, in a fixed order).  The clusters are the voxels of
+ * cut3r_voxel_downsample over ALL vertices (same frame, key, stable sort and fp64 means: the same device code, lo and hi HOST fp32 [3] from
+ * cut3r_cloud_bounds), numbered in ascending key order; c(v) is the cluster of vertex v.  A face becomes (c(a), c(b), c(c)); it is dropped
+ * when two ids are equal (degenerate), else rotated cyclically so that the smallest id leads (orientation kept); among faces with the same
+ * rotated triple the smallest input face index stays (duplicates: a stable radix sort of the triples with the face index, one 64-bit
+ * pass when 3 ceil(log2 M) <= 64, else two; passes = 0 chooses, 1 or 2 force, 1 is refused when the key does not fit); the survivors come
+ * out in ascending input face index; clusters that no survivor references are dropped and the rest renumbered in order.
+ * count sorts the vertices and writes *total = M (device).  faces, given that M, writes totals [4] (device) = F', V', degenerate,
+ * duplicate.  emit, given M, V' and F', writes out_verts [V',3], out_colors [V',3] (colors and out_colors both given or both NULL),
+ * out_faces [F',3], vertex_map [V] (new index of c(v), or -1) and face_map [F'] (input index of each survivor); V' = F' = 0 is valid and
+ * writes vertex_map only.  One workspace (cut3r_mesh_cluster_workspace_bytes(V, F)) carries the state from count through faces to emit.
+ * events: NULL, or HOST array of hipEvent_t recorded between the stages (faces: [0] after the remap, [1] after the de-duplication; emit:
+ * [0] after the means); a NULL entry is skipped.  Refused: sizes < 1, cell <= 0 or not finite, non-finite or reversed bounds, an index
+ * >= 2^21 on some axis, M outside 1..V, V' > M, F' > F, a capacity (rows the output buffers hold) below V' or F'. */
+long long cut3r_mesh_cluster_workspace_bytes(int V, int F);                   /* -1 on bad sizes */
+int cut3r_mesh_cluster_count(const float* verts, int V, int F, double cell, const float* lo, const float* hi, void* workspace,
+                             long long workspace_bytes, long long* total, void* stream);
+int cut3r_mesh_cluster_faces(const int* faces, int V, int F, long long M, int passes, void* workspace, long long workspace_bytes,
+                             long long* totals, void* const* events, void* stream);
+int cut3r_mesh_cluster_emit(const float* verts, const unsigned char* colors, int V, int F, long long M, void* workspace,
+                            long long workspace_bytes, float* out_verts, unsigned char* out_colors, int* out_faces, int* vertex_map,
+                            int* face_map, long long Vout, long long Fout, long long cap_v, long long cap_f, void* const* events, void* stream);
+/* Connected components (Open3D cluster_connected_triangles): two vertices are connected when a face holds both, and label(v) is the smallest
+ * vertex index of v's component.  label_init sets labels [V] = scratch [V] = 0..V-1.  label_round is one round: a hook launch (per face,
+ * integer atomicMin of the face's smallest label into the three vertices and into the three labels they carried, read from labels, written
+ * to scratch) and a pointer-jumping launch (every vertex to the end of its chain; both arrays equal afterwards); *changed (device int) = 1
+ * when a face saw two labels.  The HOST loops until *changed stays 0, at most V rounds: no kernel waits for another workgroup. */
+int cut3r_mesh_label_init(int* labels, int* scratch, int V, void* stream);
+int cut3r_mesh_label_round(const int* faces, int V, int F, int* labels, int* scratch, int* changed, void* stream);
+/* Small-component removal (Open3D remove_triangles_by_mask on the cluster sizes).  A face belongs to the component of its first vertex, a
+ * component's size is its number of faces (integer atomic adds).  Exactly one of min_faces, keep_largest is > 0 (the other 0): components
+ * of size >= min_faces stay, or the first keep_largest in the order (size descending, label ascending).  Faces stay in input order;
+ * vertices that no kept face references are dropped, the rest keep their order.  count writes totals [4] (device) = components, kept
+ * components K, F', V'; emit writes out_verts, out_colors, out_faces, vertex_map [V], face_map [F'] as above and comps [K,2] int32 =
+ * (label, size) of the kept components in that order.  Workspace: cut3r_mesh_components_workspace_bytes(V, F), untouched between the two.
+ * Refused: sizes < 1, both or neither option, a negative option, counts out of range, a capacity below V', F' or K. */
+long long cut3r_mesh_components_workspace_bytes(int V, int F);                /* -1 on bad sizes */
+int cut3r_mesh_components_count(const int* faces, int V, int F, const int* labels, int min_faces, int keep_largest, void* workspace,
+                                long long workspace_bytes, long long* totals, void* stream);
+int cut3r_mesh_components_emit(const float* verts, const unsigned char* colors, int V, const int* faces, int F, void* workspace,
+                               long long workspace_bytes, float* out_verts, unsigned char* out_colors, int* out_faces, int* vertex_map,
+                               int* face_map, int* comps, long long Vout, long long Fout, long long K, long long cap_v, long long cap_f,
+                               long long cap_k, void* stream);
+
 /* Measurement aid of bench.py's roofline (no reference counterpart; not on the product path): a bare MFMA loop (v_mfma_f32_16x16x32_f16,
  * 16 independent accumulator chains per wave, 8 waves per workgroup, `grid` workgroups, `iters` x 16 MFMAs per wave, operands = 16-byte
  * chunks of data[nhalf] fp16, nhalf a power of two >= 32768) with s_memtime / s_memrealtime stamps around the loop.  stamps [grid,2] u64 =
