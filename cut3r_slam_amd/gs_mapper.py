@@ -420,6 +420,15 @@ def depth_to_normal(viewpoint, depth):
     return F.pad(n, (1, 1, 1, 1))
 
 
+def gt_normal(view):
+    """the normals of the view's own depth map [3,H,W]: cached on the view (they change only with its depth), rebuilt when view.depth is
+    a new tensor"""
+    c = getattr(view, "_gt_normal", None)
+    if c is None or c[0] is not view.depth:
+        c = view._gt_normal = (view.depth, depth_to_normal(view, view.depth[None]).detach().contiguous())
+    return c[1]
+
+
 def ssim(a, b):
     """gaussian/utils/loss_utils.py:129-170 ssim on the fused kernels: a = the rendering (receives gradients), b = the keyframe image"""
     return fused_ssim(a, b)
@@ -647,13 +656,10 @@ class GSMapper:
                 image, depth = pkg["render"], pkg["depth"]
                 if exposure:                                              # :513: colours through the view's affine exposure model
                     image = (image.permute(1, 2, 0) @ v.exposure_a + v.exposure_b).permute(2, 0, 1).contiguous()
-                gt_image, gt_depth = v.original_image, v.depth[None]
-                gcache = getattr(v, "_gt_normal", None)
-                if gcache is None or gcache[0] is not v.depth:               # the keyframe's own depth normals change only with its depth
-                    gcache = v._gt_normal = (v.depth, depth_to_normal(v, gt_depth).detach().contiguous())
+                gt_image = v.original_image
                 # :516-531 -- 0.8 L1 + 0.2 (1 - SSIM) colour, lambda_depth inverse-depth L1, lambda_normal depth-normal agreement: the three
                 # per-pixel terms in one fused kernel each way, SSIM in its own
-                pix = pixel_losses(image, depth, gt_image, v.depth, gcache[1], (v.fx, v.fy, v.cx, v.cy), 0.8, self.lambda_depth, self.lambda_normal)
+                pix = pixel_losses(image, depth, gt_image, v.depth, gt_normal(v), (v.fx, v.fy, v.cx, v.cy), 0.8, self.lambda_depth, self.lambda_normal)
                 rgb_dl_nl = pix + 0.2 * (1.0 - ssim(image, gt_image))
                 vis = pkg["visibility_filter"]
                 sc = self.gaussians.get_scaling
@@ -709,14 +715,11 @@ class GSMapper:
             image, depth = pkg["render"], pkg["depth"]
             if exposure:
                 image = (image.permute(1, 2, 0) @ v.exposure_a + v.exposure_b).permute(2, 0, 1).contiguous()
-            gt_image, gt_depth = v.original_image, v.depth[None]
-            gcache = getattr(v, "_gt_normal", None)
-            if gcache is None or gcache[0] is not v.depth:
-                gcache = v._gt_normal = (v.depth, depth_to_normal(v, gt_depth).detach().contiguous())
+            gt_image = v.original_image
             nl = (1 - (pkg["normal"] * depth_to_normal(v, depth)).sum(0)).mean()          # rendered normal vs normal of the rendered depth
             # :1003-1006: with densify_every  rgb + lambda_depth/10 depth + lambda_normal (nl + gt normal);  else  rgb + lambda_normal/2 (nl + gt normal)
             w_d, w_n = (self.lambda_depth / 10, self.lambda_normal) if densify_every is not None else (0.0, self.lambda_normal / 2)
-            loss = (pixel_losses(image, depth, gt_image, v.depth, gcache[1], (v.fx, v.fy, v.cx, v.cy), 0.8, w_d, w_n)
+            loss = (pixel_losses(image, depth, gt_image, v.depth, gt_normal(v), (v.fx, v.fy, v.cx, v.cy), 0.8, w_d, w_n)
                     + 0.2 * (1.0 - ssim(image, gt_image)) + w_n * nl)
             self.gaussians.zero_grad()
             opt.zero_grad(set_to_none=True)
@@ -755,18 +758,22 @@ class GSMapper:
         """gs_backend_per_frame.py:865-944 (Hi2.terminate(gaussian_retrain=True)): a fresh map from every keyframe's stride-2 pointmap
         (rgbs u8 [n,3,H,W], pointmaps [n,h,w,3] world), then `iteration_total` single-view iterations with fixed poses -- colour, inverse
         depth and the depth-normal term -- densifying every Training.gaussian_update_every iterations after the first 1000"""
-        import random
         self.reset()
         self.initialized = True
         pm = torch.as_tensor(pointmaps, dtype=torch.float32, device=self.device)
         h1, w1 = pm.shape[1:3]
         rgb = F.interpolate(torch.as_tensor(rgbs).to(self.device).float() / 255.0, size=(h1, w1), mode="bilinear", align_corners=False)
         self.gaussians.extend_from_pcd_seq(submap_idx=0, rgb=rgb[..., ::2, ::2].permute(0, 2, 3, 1), pointmap=pm[:, ::2, ::2])
-        views = list(self.viewpoints.values())
-        if not views or len(self.gaussians) == 0:
+        if not self.viewpoints or len(self.gaussians) == 0:
             return None
+        return self._reinit_loop(iteration_total, seed)
+
+    def _reinit_loop(self, iteration_total, seed):
+        """the training loop of gaussian_reinit on the map as it stands: on the tape-free trainer (self.fused), or in tensor operations"""
+        import random
         if self.fused and iteration_total > 0:
             return self._fused_trainer().reinit_loop(iteration_total, seed)
+        views = list(self.viewpoints.values())
         rng = random.Random(seed)
         update_every = self.config["Training"].get("gaussian_update_every", 200)
         last = None
@@ -774,12 +781,9 @@ class GSMapper:
             v = views[rng.randint(0, len(views) - 1)]
             pkg = render(v, self.gaussians, self.background)
             image, depth = pkg["render"], pkg["depth"]
-            gcache = getattr(v, "_gt_normal", None)
-            if gcache is None or gcache[0] is not v.depth:
-                gcache = v._gt_normal = (v.depth, depth_to_normal(v, v.depth[None]).detach().contiguous())
             # (the reference averages the normal term over all pixels here, not over the depth mask: where either depth is missing the
             #  term is the constant 1 -- same gradient as the masked mean up to the normaliser; kept masked, as in optimization())
-            loss = (pixel_losses(image, depth, v.original_image, v.depth, gcache[1], (v.fx, v.fy, v.cx, v.cy), 0.8, self.lambda_depth,
+            loss = (pixel_losses(image, depth, v.original_image, v.depth, gt_normal(v), (v.fx, v.fy, v.cx, v.cy), 0.8, self.lambda_depth,
                                  self.lambda_normal) + 0.2 * (1.0 - ssim(image, v.original_image)))
             self.gaussians.zero_grad()
             loss.backward()

@@ -1,13 +1,14 @@
 """The Gaussian mapper's optimisation loops without an autograd tape: `GSMapper.optimization` and `GSMapper.pose_refine`
-(/root/reference/hislam2/gs_backend_per_frame.py:451-587, :202-326) as direct calls into the C ABI -- about 25 launches per rendered view
+(hislam2/gs_backend_per_frame.py:451-587, :202-326) as direct calls into the C ABI -- about 25 launches per rendered view
 instead of the ~100 launches + autograd bookkeeping of the tensor-op formulation in gs_mapper.py, which stays as the second
 implementation the tests compare this one with (same losses, same Adam arithmetic, same pose update).
 
-Per view and iteration:  cut3r_gs_activate -> cut3r_gs_preprocess / _bin / _render_forward -> loss kernels (+ cut3r_gs_map_coef /
-_refine_coef for the scalar algebra between their two passes) -> cut3r_gs_render_backward / _preprocess_backward ->
-cut3r_gs_activate_backward (gradient of theta accumulated over the views, 16 pose sums per view) -> cut3r_gs_pose_step; then ONE
-cut3r_gs_adam over all Gaussian parameters.  `pose_estimator` (a pose against the frozen map, :123-177) ends its backward pass in
-cut3r_gs_pose_backward instead: dgeom -> the 16 pose sums in one kernel, no per-Gaussian gradient, no cut3r_gs_adam.
+Per view and iteration:  cut3r_gs_activate -> cut3r_gs_preprocess / _bin / _render_forward (`_render`) -> loss kernels (+ the _map_coef /
+_refine_coef launch for the scalar algebra between their two passes; `_colour_losses` is the mapping loops' block) -> the rasteriser's
+_render_backward / _preprocess_backward -> cut3r_gs_activate_backward (`_backward`: gradient of theta accumulated over the views, 16 pose
+sums per view) -> cut3r_gs_pose_step; then ONE Adam launch over all Gaussian parameters (`_adam`).  `pose_estimator` (a pose against the
+frozen map, :123-177) ends its backward pass in cut3r_gs_pose_backward instead: dgeom -> the 16 pose sums in one kernel, no per-Gaussian
+gradient, no Adam launch.
 
 With Training.compensate_exposure (gs_backend_per_frame.py:516, :992) three launches per rendered view join them: cut3r_exposure_forward
 between the rasteriser and the colour losses (pixel loss and SSIM then read the compensated image), cut3r_exposure_backward in place of
@@ -30,17 +31,11 @@ import torch
 from . import _lib
 from . import gaussian_rasterizer as GR
 from ._lib import check
+from .gaussian_rasterizer import _p, _s
+from .gs_mapper import gt_normal, position_lr
 
 PS = 32            # floats of pose state per view (include/cut3r_hip.h)
 ES = 40            # floats of exposure state per view: A [9] row-major | b [3] | Adam m [12] | v [12] | steps | 3 x zero
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _s():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _arr(vals):
@@ -174,16 +169,23 @@ class FusedTrainer:
                                           _p(self.n_contrib), _p(self.aux), _s()), "gs_render_forward")
         return n_read
 
+    def _render_backward(self, v, g_color, g_depth, g_normal=None):
+        """rasteriser backward of one view (its forward buffers are still the current ones): the gradients of the colour, depth and
+        (optionally) normal images -> self.dgeom"""
+        P, (H, W) = self._shape[0], self._shape[1:]
+        cam, im, z = self._cam(v), self.img, self.zero_img
+        check(self.lib.cut3r_gs_render_backward(_p(self.ranges), _p(self.point_list), _p(self.geom), P, W, H, cam["tanx"], cam["tany"], _ZERO3,
+                                                _p(self.n_contrib), _p(self.aux), _p(im["alpha"]), _p(im["coord"]), _p(im["depth"]), _p(im["normal"]),
+                                                _p(g_color), _p(z), _p(z), _p(g_depth), _p(z), _p(z), _p(g_normal if g_normal is not None else z),
+                                                _p(self.dgeom), _s()), "gs_render_backward")
+
     def _backward(self, v, ps_v, g_color, g_depth, iso_coef, gtheta, sums_v, g_normal=None):
-        """rasteriser backward + activation chain of one view (its forward buffers are still the current ones)"""
+        """rasteriser backward + activation chain of one view"""
         lib, P = self.lib, self._shape[0]
         H, W = self._shape[1:]
-        cam, im, z = self._cam(v), self.img, self.zero_img
+        cam = self._cam(v)
         self.flat.zero_()
-        check(lib.cut3r_gs_render_backward(_p(self.ranges), _p(self.point_list), _p(self.geom), P, W, H, cam["tanx"], cam["tany"], _ZERO3,
-                                           _p(self.n_contrib), _p(self.aux), _p(im["alpha"]), _p(im["coord"]), _p(im["depth"]), _p(im["normal"]),
-                                           _p(g_color), _p(z), _p(z), _p(g_depth), _p(z), _p(z), _p(g_normal if g_normal is not None else z), _p(self.dgeom),
-                                           _s()), "gs_render_backward")
+        self._render_backward(v, g_color, g_depth, g_normal)
         check(lib.cut3r_gs_preprocess_backward(P, _p(self.means), _p(self.scales), _p(self.rots), _p(self.opac), _p(self.shs), 0, 1, _IDENTITY16,
                                                cam["proj"], _ZERO3, W, H, cam["tanx"], cam["tany"], 0.0, 1.0, _p(self.geom), _p(self.dgeom),
                                                _p(self.d_means), _p(self.d_scales), _p(self.d_rots), _p(self.d_opac), _p(self.d_shs), None,
@@ -191,6 +193,84 @@ class FusedTrainer:
         check(lib.cut3r_gs_activate_backward(P, _p(self.mp.gaussians.theta), _p(ps_v), _p(self.d_means), _p(self.d_scales), _p(self.d_rots),
                                              _p(self.d_opac), _p(self.d_shs), _p(self.radii), float(iso_coef), _p(self.nvis), _p(gtheta), _p(sums_v),
                                              _s()), "gs_activate_backward")
+
+    def _pose_backward(self, v, ps_v, g_color, g_depth, partials, sums_v):
+        """rasteriser backward of one view, then dgeom straight to the view's 16 pose sums (cut3r_gs_pose_backward): the backward pass of
+        an iteration that moves a pose against a frozen map.  sums_v is written, partials is scratch [cut3r_gs_pose_partial_rows(P), 16]"""
+        P, (H, W) = self._shape[0], self._shape[1:]
+        cam = self._cam(v)
+        self._render_backward(v, g_color, g_depth)
+        check(self.lib.cut3r_gs_pose_backward(P, _p(self.means), _p(self.scales), _p(self.rots), _p(self.opac), _IDENTITY16, cam["proj"], W, H,
+                                              cam["tanx"], cam["tany"], 0.0, 1.0, _p(self.geom), _p(self.dgeom), _p(self.mp.gaussians.theta),
+                                              _p(ps_v), _p(partials), _p(sums_v), _s()), "gs_pose_backward")
+
+    def _compensate(self, es_v):
+        """the rendered colour image through one view's exposure model -> self.img_x (what the colour losses then read)"""
+        H, W = self._shape[1:]
+        check(self.lib.cut3r_exposure_forward(_p(self.img["color"]), _p(es_v), H, W, _p(self.img_x), _s()), "exposure_forward")
+        return self.img_x
+
+    def _colour_losses(self, v, col, gt_n, w_depth, w_normal, g, acc, es_v=None, partials_v=None):
+        """the colour block of one view, on the colour image `col` (the rendering, or its exposure-compensated copy) and the rendered depth:
+        g x (0.8 L1 colour + w_depth inverse-depth L1 + w_normal agreement of the depth's normals with gt_n [3,H,W]) through the pixel-loss
+        kernels and the coefficient launch between them (acc: where it adds that value, or None), 0.2 (1 - SSIM) at the weight the caller put
+        into self.ssim_scale.  Leaves d loss / d rendered colour in self.g_img and d loss / d rendered depth in self.g_depth."""
+        lib = self.lib
+        H, W = self._shape[1:]
+        K = self._cam(v)["K"]
+        gt, depth = v.original_image, self.img["depth"]
+        check(lib.cut3r_pixel_loss_forward(_p(col), _p(gt), _p(depth), _p(v.depth), _p(gt_n), H, W, K[0], K[1], K[2], K[3], _p(self.sums), _s()),
+              "pixel_loss_forward")
+        check(lib.cut3r_gs_map_coef(_p(self.sums), 0.8, float(w_depth), float(w_normal), g, H, W, _p(self.coef), _p(acc), _s()), "gs_map_coef")
+        check(lib.cut3r_pixel_loss_backward(_p(col), _p(gt), _p(depth), _p(v.depth), _p(gt_n), H, W, K[0], K[1], K[2], K[3], _p(self.coef),
+                                            _p(self.g_img), _p(self.g_depth), _s()), "pixel_loss_backward")
+        check(lib.cut3r_ssim_forward(_p(col), _p(gt), 3, H, W, _p(self.smap), _p(self.sd1), _p(self.sd2), _p(self.sd3), _s()), "ssim_forward")
+        check(lib.cut3r_ssim_backward(_p(col), _p(gt), _p(self.sd1), _p(self.sd2), _p(self.sd3), 3, H, W, _p(self.ssim_scale), _p(self.g_ssim),
+                                      _s()), "ssim_backward")
+        self._colour_gradient(es_v, partials_v)
+
+    def _colour_gradient(self, es_v, partials_v):
+        """g_img <- d loss / d rendered colour.  Without exposure: g_img + g_ssim.  With it: A (g_img + g_ssim), and the partial sums of the
+        12 exposure gradients into partials_v (None: the exposure stays fixed)"""
+        if es_v is None:
+            self.g_img.add_(self.g_ssim)
+            return
+        H, W = self._shape[1:]
+        check(self.lib.cut3r_exposure_backward(_p(self.img["color"]), _p(self.g_img), _p(self.g_ssim), _p(es_v), H, W, _p(self.g_img),
+                                               _p(partials_v), _s()), "exposure_backward")
+
+    def _adam(self, gm, reset=False):
+        """ONE Adam step of all Gaussian parameters on self.gtheta; the step count advances on the host only (the device scalar of the
+        tensor-op path goes stale).  reset: the step that follows an opacity reset leaves the opacity column where the reset put it, its
+        moments zero -- the rule GaussianMap.step_like_reference states for the tensor-op path"""
+        keep = gm.theta.detach()[:, 6:7].clone() if reset else None
+        gm.steps += 1
+        gm._steps_dev_stale = True
+        b1, b2 = 0.9, 0.999
+        check(self.lib.cut3r_gs_adam(self._shape[0] * 14, _p(gm.theta), _p(gm.m), _p(gm.v), _p(self.gtheta), _p(gm.lr), b1, b2, 1 - b1 ** gm.steps,
+                                     1 - b2 ** gm.steps, 1e-15, _s()), "gs_adam")
+        if reset:
+            with torch.no_grad():
+                gm.theta[:, 6:7] = keep
+                gm.m[:, 6:7] = 0
+                gm.v[:, 6:7] = 0
+
+    def _single_view(self, v, ps_v, w_depth, w_normal, final, sums_v=None, es_v=None, partials=None, before_backward=None):
+        """the part of an iteration global_BA and reinit_loop share: ONE view rendered with an exact instance count (the set of Gaussians
+        changes under densification), the colour block at weight 1 against the view's own depth normals (into self.loss_acc when
+        `final`), and the backward pass into self.gtheta / sums_v.  before_backward() runs between the two and may return the
+        gradient of the rendered normal image."""
+        gt_n = gt_normal(v)
+        self.gtheta.zero_()
+        if sums_v is not None:
+            sums_v.zero_()
+        if final:
+            self.loss_acc.zero_()
+        self._render(v, ps_v, True)
+        col = self._compensate(es_v) if es_v is not None else self.img["color"]
+        self._colour_losses(v, col, gt_n, w_depth, w_normal, 1.0, self.loss_acc if final else None, es_v, partials)
+        g_normal = before_backward() if before_backward is not None else None
+        self._backward(v, ps_v, self.g_img, self.g_depth, 0.0, self.gtheta, sums_v, g_normal=g_normal)
 
     # ------------------------------------------------------------------ pose state <-> cameras
     def _load_poses(self, views):
@@ -215,24 +295,18 @@ class FusedTrainer:
             v.exposure_a.data.copy_(es[k, 0:9].view(3, 3))
             v.exposure_b.data.copy_(es[k, 9:12])
 
-    def _compensate(self, es_v):
-        """the rendered colour image through one view's exposure model -> self.img_x (what the colour losses then read)"""
-        H, W = self._shape[1:]
-        check(self.lib.cut3r_exposure_forward(_p(self.img["color"]), _p(es_v), H, W, _p(self.img_x), _s()), "exposure_forward")
-        return self.img_x
+    @staticmethod
+    def _pose_snapshot(ps):
+        """the snapshot of a loop that moves nothing but the pose state: taken now, put back by snapshot(restore=True)"""
+        saved = ps.clone()
 
-    def _colour_gradient(self, es_v, partials_v):
-        """g_img <- d loss / d rendered colour.  Without exposure: g_img + g_ssim.  With it: A (g_img + g_ssim), and the partial sums of the
-        12 exposure gradients into partials_v (None: the exposure stays fixed)"""
-        if es_v is None:
-            self.g_img.add_(self.g_ssim)
-            return
-        H, W = self._shape[1:]
-        check(self.lib.cut3r_exposure_backward(_p(self.img["color"]), _p(self.g_img), _p(self.g_ssim), _p(es_v), H, W, _p(self.g_img),
-                                               _p(partials_v), _s()), "exposure_backward")
+        def snapshot(restore=False):
+            if restore:
+                ps.copy_(saved)
+        return snapshot
 
-    # ------------------------------------------------------------------ the two loops
-    def _run(self, body, iters, views, snapshot):
+    # ------------------------------------------------------------------ the loops
+    def _run(self, body, iters, snapshot):
         """iteration 0 with exact instance counts, the others in capacity mode; one overflow read at the end, redo from the snapshot if set"""
         flag = GR.overflow_flag(self.dev)
         flag.zero_()
@@ -277,11 +351,7 @@ class FusedTrainer:
                 saved.update(theta=gm.theta.detach().clone(), m=gm.m.clone(), v=gm.v.clone(), ps=ps.clone(), steps=gm.steps,
                              es=es.clone() if es is not None else None)
         snapshot()
-        for v in views:                                   # the keyframe's own depth normals (constant while its depth stays)
-            gc = getattr(v, "_gt_normal", None)
-            if gc is None or gc[0] is not v.depth:
-                from .gs_mapper import depth_to_normal
-                v._gt_normal = (v.depth, depth_to_normal(v, v.depth[None]).detach().contiguous())
+        gt_n = [gt_normal(v) for v in views]              # the keyframes' own depth normals (constant while their depth stays)
         last = [None]
 
         def body(it, exact):
@@ -294,31 +364,17 @@ class FusedTrainer:
             counts = []
             extra = 0.0
             for k, v in enumerate(views):
-                cam, im = self._cam(v), self.img
                 counts.append(self._render(v, ps[k], exact))
-                col = self._compensate(es[k]) if es is not None else im["color"]
-                K = cam["K"]
-                check(lib.cut3r_pixel_loss_forward(_p(col), _p(v.original_image), _p(im["depth"]), _p(v.depth), _p(v._gt_normal[1]), H, W,
-                                                   K[0], K[1], K[2], K[3], _p(self.sums), _s()), "pixel_loss_forward")
-                check(lib.cut3r_gs_map_coef(_p(self.sums), 0.8, float(mp.lambda_depth), float(mp.lambda_normal), g, H, W, _p(self.coef),
-                                            _p(self.loss_acc) if final else None, _s()), "gs_map_coef")
-                check(lib.cut3r_pixel_loss_backward(_p(col), _p(v.original_image), _p(im["depth"]), _p(v.depth), _p(v._gt_normal[1]), H, W,
-                                                    K[0], K[1], K[2], K[3], _p(self.coef), _p(self.g_img), _p(self.g_depth), _s()), "pixel_loss_backward")
-                check(lib.cut3r_ssim_forward(_p(col), _p(v.original_image), 3, H, W, _p(self.smap), _p(self.sd1), _p(self.sd2), _p(self.sd3),
-                                             _s()), "ssim_forward")
-                check(lib.cut3r_ssim_backward(_p(col), _p(v.original_image), _p(self.sd1), _p(self.sd2), _p(self.sd3), 3, H, W,
-                                              _p(self.ssim_scale), _p(self.g_ssim), _s()), "ssim_backward")
-                self._colour_gradient(es[k] if es is not None else None, partials[k] if partials is not None else None)
+                col = self._compensate(es[k]) if es is not None else self.img["color"]
+                self._colour_losses(v, col, gt_n[k], mp.lambda_depth, mp.lambda_normal, g, self.loss_acc if final else None,
+                                    es[k] if es is not None else None, partials[k] if partials is not None else None)
                 if final:                                 # the reported loss: the two terms that have no sums kernel, in tensor operations
                     vis = self.radii > 0
                     sc = self.scales
                     iso = (torch.abs(sc - sc.mean(dim=1, keepdim=True)) * vis[:, None]).sum() / (3 * vis.sum()).clamp_min(1)
                     extra = extra + g * (0.2 * (1.0 - self.smap.mean()) + mp.lambda_iso * iso)
                 self._backward(v, ps[k], self.g_img, self.g_depth, g * mp.lambda_iso, self.gtheta, sums[k] if sums is not None else None)
-            gm.steps += 1
-            b1, b2 = 0.9, 0.999
-            check(lib.cut3r_gs_adam(P * 14, _p(gm.theta), _p(gm.m), _p(gm.v), _p(self.gtheta), _p(gm.lr), b1, b2, 1 - b1 ** gm.steps,
-                                    1 - b2 ** gm.steps, 1e-15, _s()), "gs_adam")
+            self._adam(gm)
             if sums is not None:
                 for k in range(N):
                     check(lib.cut3r_gs_pose_step(_p(ps[k]), _p(sums[k]), 0.0, None, lr * 2, lr * 10, 1, _s()), "gs_pose_step")
@@ -329,8 +385,7 @@ class FusedTrainer:
                 last[0] = self.loss_acc[0] + extra
             return counts
 
-        self._run(body, iters, views, snapshot)
-        gm._steps_dev_stale = True
+        self._run(body, iters, snapshot)
         if optimize_pose:
             self._store_poses(views, ps)
             if es is not None:
@@ -349,14 +404,6 @@ class FusedTrainer:
         sums = torch.zeros(B, 16, dtype=torch.float32, device=self.dev)
         ratios = torch.zeros(B, 1, dtype=torch.float32, device=self.dev)
         lr = mp.config["opt_params"]["pose_lr"]
-        saved = {}
-
-        def snapshot(restore=False):
-            if restore:
-                ps.copy_(saved["ps"])
-            else:
-                saved["ps"] = ps.clone()
-        snapshot()
 
         def body(it, exact):
             sums.zero_()
@@ -374,24 +421,10 @@ class FusedTrainer:
                 check(lib.cut3r_gs_pose_step(_p(ps[k]), _p(sums[k]), 0.05 / B, _p(ratios[k]), lr * 2, lr * 10, 0, _s()), "gs_pose_step")
             return counts
 
-        self._run(body, iters, views, snapshot)
+        self._run(body, iters, self._pose_snapshot(ps))
         for k in range(B):                                # update_pose: T <- exp(delta) T, delta <- 0
             check(lib.cut3r_gs_pose_step(_p(ps[k]), _p(sums[k]), 0.0, None, 0.0, 0.0, 2, _s()), "gs_pose_step (fold)")
         self._store_poses(views, ps)
-
-    def _pose_backward(self, v, ps_v, g_color, g_depth, partials, sums_v):
-        """rasteriser backward of one view, then dgeom straight to the view's 16 pose sums (cut3r_gs_pose_backward): the backward pass of
-        an iteration that moves a pose against a frozen map.  sums_v is written, partials is scratch [cut3r_gs_pose_partial_rows(P), 16]"""
-        lib, P = self.lib, self._shape[0]
-        H, W = self._shape[1:]
-        cam, im, z = self._cam(v), self.img, self.zero_img
-        check(lib.cut3r_gs_render_backward(_p(self.ranges), _p(self.point_list), _p(self.geom), P, W, H, cam["tanx"], cam["tany"], _ZERO3,
-                                           _p(self.n_contrib), _p(self.aux), _p(im["alpha"]), _p(im["coord"]), _p(im["depth"]), _p(im["normal"]),
-                                           _p(g_color), _p(z), _p(z), _p(g_depth), _p(z), _p(z), _p(z), _p(self.dgeom),
-                                           _s()), "gs_render_backward")
-        check(lib.cut3r_gs_pose_backward(P, _p(self.means), _p(self.scales), _p(self.rots), _p(self.opac), _IDENTITY16, cam["proj"], W, H,
-                                         cam["tanx"], cam["tany"], 0.0, 1.0, _p(self.geom), _p(self.dgeom), _p(self.mp.gaussians.theta), _p(ps_v),
-                                         _p(partials), _p(sums_v), _s()), "gs_pose_backward")
 
     def pose_estimator(self, view, iters, use_depth=False, pose_backward="fused"):
         """GSMapper.pose_estimator's loop (gs_backend_per_frame.py:143-167): the Gaussians stay fixed, the view's increments take one Adam
@@ -413,30 +446,10 @@ class FusedTrainer:
         lr = float(mp.config["opt_params"]["pose_lr"])
         w_depth = 1.0 if use_depth else 0.0
         self.ssim_scale.fill_(-0.2 / (3 * H * W))
-        gt, z = view.original_image, self.zero_img
-        saved = {}
-
-        def snapshot(restore=False):
-            if restore:
-                ps.copy_(saved["ps"])
-            else:
-                saved["ps"] = ps.clone()
-        snapshot()
 
         def body(it, exact):
-            cam, im = self._cam(view), self.img
-            K = cam["K"]
             count = self._render(view, ps[0], exact)
-            check(lib.cut3r_pixel_loss_forward(_p(im["color"]), _p(gt), _p(im["depth"]), _p(view.depth), _p(z), H, W, K[0], K[1], K[2], K[3],
-                                               _p(self.sums), _s()), "pixel_loss_forward")
-            check(lib.cut3r_gs_map_coef(_p(self.sums), 0.8, w_depth, 0.0, 1.0, H, W, _p(self.coef), None, _s()), "gs_map_coef")
-            check(lib.cut3r_pixel_loss_backward(_p(im["color"]), _p(gt), _p(im["depth"]), _p(view.depth), _p(z), H, W, K[0], K[1], K[2], K[3],
-                                                _p(self.coef), _p(self.g_img), _p(self.g_depth), _s()), "pixel_loss_backward")
-            check(lib.cut3r_ssim_forward(_p(im["color"]), _p(gt), 3, H, W, _p(self.smap), _p(self.sd1), _p(self.sd2), _p(self.sd3), _s()),
-                  "ssim_forward")
-            check(lib.cut3r_ssim_backward(_p(im["color"]), _p(gt), _p(self.sd1), _p(self.sd2), _p(self.sd3), 3, H, W, _p(self.ssim_scale),
-                                          _p(self.g_ssim), _s()), "ssim_backward")
-            self.g_img.add_(self.g_ssim)
+            self._colour_losses(view, self.img["color"], self.zero_img, w_depth, 0.0, 1.0, None)
             if partials is not None:
                 self._pose_backward(view, ps[0], self.g_img, self.g_depth, partials, sums)
             else:
@@ -445,7 +458,7 @@ class FusedTrainer:
             check(lib.cut3r_gs_pose_step(_p(ps[0]), _p(sums), 0.0, None, lr, lr, 1, _s()), "gs_pose_step")
             return [count]
 
-        self._run(body, iters, views, snapshot)
+        self._run(body, iters, self._pose_snapshot(ps))
         self._store_poses(views, ps)
 
     def global_BA(self, iteration_total, densify=True, densify_every=None, opacity_reset=True, seed=0, exposure=False):
@@ -455,9 +468,7 @@ class FusedTrainer:
         The instance count is read every iteration (the set of Gaussians changes under densification).  exposure: the colour losses read
         the rendering through the drawn view's exposure model, which steps with its pose (moments kept over the iterations of the call)."""
         import random
-        from .gs_mapper import depth_to_normal, position_lr
         mp, lib = self.mp, self.lib
-        gm = mp.gaussians
         views = list(mp.viewpoints.values())
         H, W = self._image_size(views)
         ps = self._load_poses(views)
@@ -467,7 +478,7 @@ class FusedTrainer:
         update_every, reset_every = tr.get("gaussian_update_every", 200), tr.get("gaussian_reset", 3001)
         lr = op["pose_lr"]
         w_d, w_n = (mp.lambda_depth / 10, mp.lambda_normal) if densify_every is not None else (0.0, mp.lambda_normal / 2)
-        self._buffers(len(gm), H, W)
+        self._buffers(len(mp.gaussians), H, W)
         self.ssim_scale.fill_(-0.2 / (3 * H * W))
         es = self.exposure_state = load_exposures(views, self.dev) if exposure else None
         elr = op.get("exposure_lr", 0.0005)
@@ -475,6 +486,20 @@ class FusedTrainer:
         partials = torch.empty(rows, 12, dtype=torch.float32, device=self.dev) if exposure else None
         g_nrm = torch.empty(3, H, W, dtype=torch.float32, device=self.dev)
         last = None
+
+        def rendered_normal_term():
+            """agreement of the rendered normal of view v with the normal of its rendered depth: the value into the reported loss, the
+            gradient into g_nrm and (added) self.g_depth"""
+            nonlocal last
+            im, K = self.img, self._cam(v)["K"]
+            if final:
+                check(lib.cut3r_normal_agree_forward(_p(im["normal"]), _p(im["depth"]), H, W, K[0], K[1], K[2], K[3], _p(self.nvis), _s()),
+                      "normal_agree_forward")
+                last = self.loss_acc[0] + 0.2 * (1.0 - self.smap.mean()) + w_n * self.nvis[0] / (H * W)
+            check(lib.cut3r_normal_agree_backward(_p(im["normal"]), _p(im["depth"]), H, W, K[0], K[1], K[2], K[3], float(w_n) / (H * W), _p(g_nrm),
+                                                  _p(self.g_depth), _s()), "normal_agree_backward")
+            return g_nrm
+
         for iteration in range(iteration_total):
             mp.iteration_count += 1
             gm = mp.gaussians
@@ -482,41 +507,14 @@ class FusedTrainer:
             self._buffers(P, H, W)
             k = rng.randint(0, len(views) - 1)
             v = views[k]
-            gc = getattr(v, "_gt_normal", None)
-            if gc is None or gc[0] is not v.depth:
-                v._gt_normal = (v.depth, depth_to_normal(v, v.depth[None]).detach().contiguous())
             final = iteration == iteration_total - 1
-            cam, im = self._cam(v), self.img
-            K = cam["K"]
-            self.gtheta.zero_()
-            sums[k].zero_()
-            if final:
-                self.loss_acc.zero_()
-            self._render(v, ps[k], True)
-            col = self._compensate(es[k]) if es is not None else im["color"]
-            check(lib.cut3r_pixel_loss_forward(_p(col), _p(v.original_image), _p(im["depth"]), _p(v.depth), _p(v._gt_normal[1]), H, W, K[0], K[1],
-                                               K[2], K[3], _p(self.sums), _s()), "pixel_loss_forward")
-            check(lib.cut3r_gs_map_coef(_p(self.sums), 0.8, float(w_d), float(w_n), 1.0, H, W, _p(self.coef), _p(self.loss_acc) if final else None, _s()),
-                  "gs_map_coef")
-            check(lib.cut3r_pixel_loss_backward(_p(col), _p(v.original_image), _p(im["depth"]), _p(v.depth), _p(v._gt_normal[1]), H, W, K[0], K[1],
-                                                K[2], K[3], _p(self.coef), _p(self.g_img), _p(self.g_depth), _s()), "pixel_loss_backward")
-            check(lib.cut3r_ssim_forward(_p(col), _p(v.original_image), 3, H, W, _p(self.smap), _p(self.sd1), _p(self.sd2), _p(self.sd3), _s()),
-                  "ssim_forward")
-            check(lib.cut3r_ssim_backward(_p(col), _p(v.original_image), _p(self.sd1), _p(self.sd2), _p(self.sd3), 3, H, W, _p(self.ssim_scale),
-                                          _p(self.g_ssim), _s()), "ssim_backward")
-            self._colour_gradient(es[k] if es is not None else None, partials)
-            if final:
-                check(lib.cut3r_normal_agree_forward(_p(im["normal"]), _p(im["depth"]), H, W, K[0], K[1], K[2], K[3], _p(self.nvis), _s()), "normal_agree_forward")
-                last = self.loss_acc[0] + 0.2 * (1.0 - self.smap.mean()) + w_n * self.nvis[0] / (H * W)
-            check(lib.cut3r_normal_agree_backward(_p(im["normal"]), _p(im["depth"]), H, W, K[0], K[1], K[2], K[3], float(w_n) / (H * W), _p(g_nrm),
-                                                  _p(self.g_depth), _s()), "normal_agree_backward")
-            self._backward(v, ps[k], self.g_img, self.g_depth, 0.0, self.gtheta, sums[k], g_normal=g_nrm)
+            self._single_view(v, ps[k], w_d, w_n, final, sums[k], es[k] if es is not None else None, partials, rendered_normal_term)
             if iteration < 10000 and densify:
                 check(lib.cut3r_gs_densify_stats(P, _p(self.radii), _p(self.d_means2D), _p(gm.max_radii2D), _p(gm.grad_accum), _p(gm.grad_accum_abs), _p(gm.denom), _s()),
                       "gs_densify_stats")
             # the reference's order (gs_backend_per_frame.py:1025-1041): densify_and_prune / reset_opacity come BEFORE optimizer.step() and
             # re-create the parameters, whose .grad is then None: Adam skips every group after a densification (no update, no moment
-            # update, no step increment) and the opacity group after a reset (GaussianMap.step_like_reference)
+            # update, no step increment) and the opacity group after a reset (_adam)
             do_densify = do_reset = False
             if iteration < 10000 and densify:
                 do_densify = (iteration == iteration_total // 2) if densify_every is not None else ((mp.iteration_count + 1) % update_every == 0)
@@ -526,17 +524,7 @@ class FusedTrainer:
                 if do_reset:
                     gm.reset_opacity()
             if not do_densify:
-                keep = gm.theta.detach()[:, 6:7].clone() if do_reset else None
-                gm.steps += 1
-                gm._steps_dev_stale = True
-                b1, b2 = 0.9, 0.999
-                check(lib.cut3r_gs_adam(P * 14, _p(gm.theta), _p(gm.m), _p(gm.v), _p(self.gtheta), _p(gm.lr), b1, b2, 1 - b1 ** gm.steps, 1 - b2 ** gm.steps,
-                                        1e-15, _s()), "gs_adam")
-                if do_reset:
-                    with torch.no_grad():
-                        gm.theta[:, 6:7] = keep
-                        gm.m[:, 6:7] = 0
-                        gm.v[:, 6:7] = 0
+                self._adam(gm, reset=do_reset)
             if densify and "position_lr_final" in op:
                 gm.lr[0, 0:3] = position_lr(op, iteration)
             check(lib.cut3r_gs_pose_step(_p(ps[k]), _p(sums[k]), 0.0, None, lr * 2, lr * 10, 1, _s()), "gs_pose_step")
@@ -552,7 +540,6 @@ class FusedTrainer:
         colour, inverse depth and the depth-normal term -- densification statistics and clone / split / prune every
         Training.gaussian_update_every iterations after the first 1000"""
         import random
-        from .gs_mapper import depth_to_normal
         mp, lib = self.mp, self.lib
         views = list(mp.viewpoints.values())
         H, W = self._image_size(views)
@@ -563,36 +550,19 @@ class FusedTrainer:
         self._buffers(len(mp.gaussians), H, W)
         self.ssim_scale.fill_(-0.2 / (3 * H * W))
         last = None
+
+        def report():
+            nonlocal last
+            if final:
+                last = self.loss_acc[0] + 0.2 * (1.0 - self.smap.mean())
+
         for iteration in range(iteration_total):
             gm = mp.gaussians
             P = len(gm)
             self._buffers(P, H, W)
             k = rng.randint(0, len(views) - 1)
-            v = views[k]
-            gc = getattr(v, "_gt_normal", None)
-            if gc is None or gc[0] is not v.depth:
-                v._gt_normal = (v.depth, depth_to_normal(v, v.depth[None]).detach().contiguous())
             final = iteration == iteration_total - 1
-            cam, im = self._cam(v), self.img
-            K = cam["K"]
-            self.gtheta.zero_()
-            if final:
-                self.loss_acc.zero_()
-            self._render(v, ps[k], True)
-            check(lib.cut3r_pixel_loss_forward(_p(im["color"]), _p(v.original_image), _p(im["depth"]), _p(v.depth), _p(v._gt_normal[1]), H, W, K[0], K[1],
-                                               K[2], K[3], _p(self.sums), _s()), "pixel_loss_forward")
-            check(lib.cut3r_gs_map_coef(_p(self.sums), 0.8, float(mp.lambda_depth), float(mp.lambda_normal), 1.0, H, W, _p(self.coef),
-                                        _p(self.loss_acc) if final else None, _s()), "gs_map_coef")
-            check(lib.cut3r_pixel_loss_backward(_p(im["color"]), _p(v.original_image), _p(im["depth"]), _p(v.depth), _p(v._gt_normal[1]), H, W, K[0], K[1],
-                                                K[2], K[3], _p(self.coef), _p(self.g_img), _p(self.g_depth), _s()), "pixel_loss_backward")
-            check(lib.cut3r_ssim_forward(_p(im["color"]), _p(v.original_image), 3, H, W, _p(self.smap), _p(self.sd1), _p(self.sd2), _p(self.sd3), _s()),
-                  "ssim_forward")
-            check(lib.cut3r_ssim_backward(_p(im["color"]), _p(v.original_image), _p(self.sd1), _p(self.sd2), _p(self.sd3), 3, H, W, _p(self.ssim_scale),
-                                          _p(self.g_ssim), _s()), "ssim_backward")
-            self.g_img.add_(self.g_ssim)
-            if final:
-                last = self.loss_acc[0] + 0.2 * (1.0 - self.smap.mean())
-            self._backward(v, ps[k], self.g_img, self.g_depth, 0.0, self.gtheta, None)
+            self._single_view(views[k], ps[k], mp.lambda_depth, mp.lambda_normal, final, before_backward=report)
             if iteration > 1000:
                 check(lib.cut3r_gs_densify_stats(P, _p(self.radii), _p(self.d_means2D), _p(gm.max_radii2D), _p(gm.grad_accum), _p(gm.grad_accum_abs), _p(gm.denom), _s()),
                       "gs_densify_stats")
@@ -600,9 +570,5 @@ class FusedTrainer:
                 # (gs_backend_per_frame.py:920-935: densification first, then an optimizer.step() that finds no gradients)
                 gm.densify_and_prune(op["densify_grad_threshold"], mp.gaussian_th, mp.gaussian_extent, mp.size_threshold)
             else:
-                gm.steps += 1
-                gm._steps_dev_stale = True
-                b1, b2 = 0.9, 0.999
-                check(lib.cut3r_gs_adam(P * 14, _p(gm.theta), _p(gm.m), _p(gm.v), _p(self.gtheta), _p(gm.lr), b1, b2, 1 - b1 ** gm.steps, 1 - b2 ** gm.steps,
-                                        1e-15, _s()), "gs_adam")
+                self._adam(gm)
         return float(last) if last is not None else None

@@ -1,6 +1,7 @@
 """GS mapper (cut3r_slam_amd/gs_mapper.py, mirrors hislam2/gs_backend_per_frame.py:87-121,202-326,451-587) on a synthetic scene: a
 textured, gently curved wall modelled by ground-truth Gaussians, observed (image + depth) through the HIP rasteriser.  The reference's
 backend cannot run here (CUDA rasteriser, open3d): functional tests, PARITY UNPINNED."""
+import functools
 import math
 import os
 import sys
@@ -484,12 +485,10 @@ def test_an_overflowed_capacity_is_never_kept():
     assert int(c.gaussians.step_count) == int(a.gaussians.step_count) == c.gaussians.steps
 
 
-def test_one_mapping_iteration_matches_the_fp64_restatement_of_the_loss():
-    """the WHOLE mapping iteration -- pose composition exp([tau, phi]) T, activations, rasteriser, colour L1 + SSIM, inverse-depth L1,
-    depth-normal agreement, isotropy -- against oracle/gs_loss_oracle.py (fp64 torch autograd over the fp64 rasteriser restatement): the
-    loss value and the gradient of every Gaussian parameter, for the tape-free trainer AND the tensor-op formulation; the first Adam step
-    of the pose increments moves against the oracle's pose gradient.  Parity unpinned vs the reference (its CUDA rasteriser cannot run
-    here): this pins the mapper's iteration to an independent reading of gs_backend_per_frame.py:451-587."""
+@functools.lru_cache(maxsize=None)
+def _host_scene():
+    """a map and one observed camera built on the host (no atomics before the first launch): 160 Gaussians seen in 32 x 48 pixels ->
+    (Hs, Ws, f, K, theta0 [P,14], w2c [4,4], gt_image [3,Hs,Ws], gt_depth [Hs,Ws]), all on the CPU; shared, not to be written to"""
     from oracle import gs_loss_oracle as LO
     Hs, Ws, f = 32, 48, 40.0
     K = (f, f, Ws / 2, Hs / 2)
@@ -508,6 +507,18 @@ def test_one_mapping_iteration_matches_the_fp64_restatement_of_the_loss():
         gt_image = obs["color"].clamp(0, 1).float()
         gt_depth = (obs["depth"][0] * (1 + 0.02 * torch.randn(Hs, Ws, generator=g).double())).float()
         gt_depth[5:9, 10:20] = 0.0
+    return Hs, Ws, f, K, theta0, w2c, gt_image, gt_depth
+
+
+def test_one_mapping_iteration_matches_the_fp64_restatement_of_the_loss():
+    """the WHOLE mapping iteration -- pose composition exp([tau, phi]) T, activations, rasteriser, colour L1 + SSIM, inverse-depth L1,
+    depth-normal agreement, isotropy -- against oracle/gs_loss_oracle.py (fp64 torch autograd over the fp64 rasteriser restatement): the
+    loss value and the gradient of every Gaussian parameter, for the tape-free trainer AND the tensor-op formulation; the first Adam step
+    of the pose increments moves against the oracle's pose gradient.  Parity unpinned vs the reference (its CUDA rasteriser cannot run
+    here): this pins the mapper's iteration to an independent reading of gs_backend_per_frame.py:451-587."""
+    from oracle import gs_loss_oracle as LO
+    Hs, Ws, f, K, theta0, w2c, gt_image, gt_depth = _host_scene()
+    P = theta0.shape[0]
     cfg = dict(CONFIG, Training=dict(CONFIG["Training"], lambda_depth=2.0, lambda_normal=0.3, lambda_iso=4.0))
     res = {}
     for fused in (True, False):
@@ -547,3 +558,90 @@ def test_one_mapping_iteration_matches_the_fp64_restatement_of_the_loss():
         assert bool((torch.sign(got[big]) == -torch.sign(gref[big])).all()), (got, gref)
         assert float((got[big].abs() - step).abs().max()) < 0.05 * step, (got, step)
     torch.testing.assert_close(res[True][2], res[False][2], atol=1e-6, rtol=0)
+
+
+def test_tape_free_reinit_loop_matches_the_tensor_op_formulation():
+    """GSMapper._reinit_loop (the training loop of gaussian_reinit, on a prepared map) on the tape-free trainer against the autograd
+    formulation: one iteration -> the same gradient of every parameter (m = 0.1 g) and the same loss; reinit fixes the poses, so both
+    sides leave them where they were"""
+    a, b = _pair()
+    a.fused, b.fused = False, True
+    pa0, pb0 = a.trajectory().detach().clone(), b.trajectory().detach().clone()
+    la, lb = a._reinit_loop(1, seed=3), b._reinit_loop(1, seed=3)
+    ga, gb = a.gaussians.m / 0.1, b.gaussians.m / 0.1
+    for name, (c0, c1) in {"xyz": (0, 3), "colour": (3, 6), "opacity": (6, 7), "log scale": (7, 10)}.items():
+        sc, err = float(ga[:, c0:c1].abs().max()), float((ga[:, c0:c1] - gb[:, c0:c1]).abs().max())
+        print(f"[gs fused reinit] d loss / d {name}: scale {sc:.3e}, max |autograd - fused| {err:.3e}")
+        assert sc > 0 and err <= 2e-4 * sc + 1e-9, (name, sc, err)
+    print(f"[gs fused reinit] loss: autograd {la!r}, fused {lb!r}")
+    assert abs(la - lb) <= 1e-5 * abs(la) + 1e-6, (la, lb)
+    assert torch.equal(a.trajectory().detach(), pa0) and torch.equal(b.trajectory().detach(), pb0)
+    for m in (a, b):
+        for v in m.viewpoints.values():
+            assert not bool(v.cam_trans_delta.any()) and not bool(v.cam_rot_delta.any())
+
+
+class _Recorder:
+    """stands in for FusedTrainer.lib: every entry point looked up is wrapped to note its name (without the cut3r_ prefix), then forwards"""
+
+    def __init__(self, lib):
+        self._lib, self.names = lib, []
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+
+        def call(*args):
+            self.names.append(name[len("cut3r_"):])
+            return fn(*args)
+        return call
+
+
+def _two_camera_mapper():
+    """the host-built scene of _host_scene under two cameras, the second a few centimetres off the first, on a tape-free mapper whose
+    trainer's library is a _Recorder -> (mapper, trainer, views)"""
+    Hs, Ws, f, K, theta0, w2c, gt_image, gt_depth = _host_scene()
+    m = GM.GSMapper(CONFIG, f, f, Ws / 2, Hs / 2, downsample_ratio=2, device=DEV)
+    m.gaussians._append({"xyz": theta0[:, 0:3], "f_dc": theta0[:, 3:6], "opacity": theta0[:, 6:7], "scaling": theta0[:, 7:10], "rotation": theta0[:, 10:14]},
+                        torch.zeros(theta0.shape[0]))
+    off = SE3.exp(torch.tensor([[0.03, -0.02, 0.01, 0.0, 0.0, 0.0]], device=DEV)).matrix()[0].cpu()
+    for k, T in enumerate((w2c, off @ w2c)):
+        m.viewpoints[k] = GM.Camera(k, gt_image, gt_depth, T.to(DEV), f, f, Ws / 2, Hs / 2, device=DEV)
+    tr = m._fused_trainer()
+    tr.lib = _Recorder(tr.lib)
+    return m, tr, list(m.viewpoints.values())
+
+
+def test_the_tape_free_loops_launch_what_they_always_launched():
+    """the C-ABI entry points every FusedTrainer loop calls, in order, on two host-built cameras (no atomics in the set-up): pinned
+    to the trace recorded before the loops were put on shared helpers (one colour block, one Adam step, one rasteriser backward), so a
+    change to a helper that adds, drops or reorders a launch in ANY loop shows here"""
+    render = ["gs_activate", "gs_preprocess", "gs_bin", "gs_render_forward"]
+    colour = ["pixel_loss_forward", "gs_map_coef", "pixel_loss_backward", "ssim_forward", "ssim_backward"]
+    backward = ["gs_render_backward", "gs_preprocess_backward", "gs_activate_backward"]
+    view = render + colour + backward
+    view_x = render + ["exposure_forward"] + colour + ["exposure_backward"] + backward
+    view_refine = render + ["refine_loss_forward", "gs_refine_coef", "refine_loss_backward"] + backward
+
+    def trace(call):
+        m, tr, views = _two_camera_mapper()
+        call(m, tr, views)
+        torch.cuda.synchronize()
+        return tr.lib.names
+
+    # optimization: per iteration both views, then ONE Adam step and a pose step per view; iteration 1 runs in capacity mode (same launches)
+    iteration = view + view + ["gs_adam", "gs_pose_step", "gs_pose_step"]
+    assert trace(lambda m, tr, views: tr.optimization(views, 2, True)) == ["exposure_partial_rows"] + iteration + iteration
+    iteration_x = view_x + view_x + ["gs_adam", "gs_pose_step", "gs_pose_step", "gs_exposure_step", "gs_exposure_step"]
+    assert trace(lambda m, tr, views: tr.optimization(views, 2, True, exposure=True)) == ["exposure_partial_rows"] + iteration_x + iteration_x
+    # pose_refine: a pose step per view after the views, and the fold of the increments after the loop
+    assert trace(lambda m, tr, views: tr.pose_refine(views, 1)) == view_refine + view_refine + ["gs_pose_step"] * 2 + ["gs_pose_step"] * 2
+    # pose_estimator: dgeom straight to the pose sums, or the three-call chain
+    assert trace(lambda m, tr, views: tr.pose_estimator(views[0], 1)) == (
+        ["gs_pose_partial_rows"] + render + colour + ["gs_render_backward", "gs_pose_backward"] + ["gs_pose_step"])
+    assert trace(lambda m, tr, views: tr.pose_estimator(views[0], 1, pose_backward="chain")) == ["gs_pose_partial_rows"] + view + ["gs_pose_step"]
+    # global_BA: one drawn view, the rendered-normal term (its value in the last iteration only) before the backward pass
+    assert trace(lambda m, tr, views: tr.global_BA(1, densify=True, densify_every=None, opacity_reset=False, seed=3)) == (
+        ["exposure_partial_rows"] + render + colour + ["normal_agree_forward", "normal_agree_backward"] + backward
+        + ["gs_densify_stats", "gs_adam", "gs_pose_step"])
+    # reinit_loop: one drawn view, fixed poses
+    assert trace(lambda m, tr, views: tr.reinit_loop(1, seed=3)) == view + ["gs_adam"]
