@@ -825,12 +825,12 @@ extern "C" int cut3r_corr_index_backward(const float* coords, const float* grad_
 
 extern "C" long long cut3r_ba_workspace_floats(int P, int ht, int wd, int N, int M, int fixedp) {
     const long long HW = (long long)ht * wd, Pf = P - fixedp, nblk = (HW + BA_BLOCK - 1) / BA_BLOCK, n = Pf * 6;
-    //      Hpart                      E                 C, w, dz     H            v    S      vS  L
-    return (long long)N * nblk * BA_HROW + Pf * M * 6 * HW + 3 * M * HW + Pf * Pf * 36 + Pf * 6 + n * n + n + n * n + 64;
+    //      Hpart                      E                 C, w, dz     H            v    S      vS  hdiag  L
+    return (long long)N * nblk * BA_HROW + Pf * M * 6 * HW + 3 * M * HW + Pf * Pf * 36 + Pf * 6 + n * n + n + n + n * n + 64;
 }
 
-// workspace layout shared by the staged entry points
-struct BaWs { float *Hpart, *E, *Cm, *wm, *H, *v, *S, *vS, *L; int nblk, n; };
+// workspace layout shared by the staged entry points (cut3r_ba_step keeps diag(H) in `hd` and damps into `L`: n * n floats)
+struct BaWs { float *Hpart, *E, *Cm, *wm, *H, *v, *S, *vS, *hd, *L; int nblk, n; };
 static BaWs ba_ws(float* workspace, int P, int ht, int wd, int N, int M, int fixedp) {
     const long long HW = (long long)ht * wd;
     const int Pf = P - fixedp;
@@ -845,7 +845,8 @@ static BaWs ba_ws(float* workspace, int P, int ht, int wd, int N, int M, int fix
     w.v = w.H + (size_t)Pf * Pf * 36;
     w.S = w.v + (size_t)Pf * 6;
     w.vS = w.S + (size_t)w.n * w.n;
-    w.L = w.vS + w.n;
+    w.hd = w.vS + w.n;
+    w.L = w.hd + w.n;
     return w;
 }
 
@@ -901,9 +902,9 @@ extern "C" int cut3r_ba_step(const float* Gij, const float* disps, const float* 
     if (!workspace || !eta) return CUT3R_ERR_ARG;
     const BaWs w = ba_ws(workspace, P, ht, wd, N, M, fixedp);
     int rc = cut3r_ba_assemble(Gij, disps, intr, target, weight, eta, ii, jj, src_ptr, src_edges, kx, present, P, ht, wd, N, M, fixedp, 0,
-                               workspace, w.S, w.vS, w.L, stream);                  // (hdiag in the first n floats of the L region)
+                               workspace, w.S, w.vS, w.hd, stream);
     if (rc != CUT3R_OK) return rc;
-    rc = cut3r_ba_solve(w.S, w.vS, w.L, w.n, ep, lm, w.L + w.n, dx, flag, stream);
+    rc = cut3r_ba_solve(w.S, w.vS, w.hd, w.n, ep, lm, w.L, dx, flag, stream);
     if (rc != CUT3R_OK) return rc;
     return cut3r_ba_backsub(workspace, dx, present, P, ht, wd, N, M, fixedp, dz, stream);
 }

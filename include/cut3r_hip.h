@@ -301,7 +301,9 @@ int cut3r_corr_index_backward(const float* coords, const float* grad_out, float*
  * Gij [N,7] = G_j*G_i^-1 (SE3 data), disps [P,ht*wd], intr [P,4], target/weight [N,ht*wd,2], eta [M,ht*wd];
  * ii,jj int32 [N]; CSR of edges by source frame (src_ptr [M+1], src_edges [N], kx [M] = sorted unique(ii));
  * present uint8 [P-fixedp, M] marks the non-zero E blocks.  Outputs dx [P-fixedp,6], dz [M,ht*wd], flag[0] = 1 if
- * the Cholesky failed (dx = 0, as geom/chol.py:13-18).  Requires 6*(P-fixedp) <= 192. */
+ * the Cholesky failed (dx = 0, as geom/chol.py:13-18).  Requires 6*(P-fixedp) <= 192 (otherwise: CUT3R_ERR_ARG, nothing written).
+ * workspace: cut3r_ba_workspace_floats(P, ht, wd, N, M, fixedp) floats, for cut3r_ba_step and for the staged entry points alike;
+ * no entry point reads or writes outside them. */
 long long cut3r_ba_workspace_floats(int P, int ht, int wd, int N, int M, int fixedp);
 int cut3r_ba_step(const float* Gij, const float* disps, const float* intr, const float* target, const float* weight, const float* eta,
                   const int* ii, const int* jj, const int* src_ptr, const int* src_edges, const int* kx, const unsigned char* present,

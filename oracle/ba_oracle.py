@@ -30,9 +30,10 @@ def project(Gij_M, disp, intr_i, intr_j, ht, wd):
     return coords, valid
 
 
-def ba_dense(target, weight, eta, poses7, disps, intr, ii, jj, fixedp, ep=0.1, lm=1e-4, eps=1e-6):
+def ba_dense(target, weight, eta, poses7, disps, intr, ii, jj, fixedp, ep=0.1, lm=1e-4, eps=1e-6, return_system=False):
     """Numerical-Jacobian Gauss-Newton step on the same normal equations, solved WITHOUT the Schur reduction.
-    Left perturbation of world->camera poses: G <- exp(a) G (retr, ba.py:29).  Returns dx [P-fixedp,6], dz [M,HW]."""
+    Left perturbation of world->camera poses: G <- exp(a) G (retr, ba.py:29).  Returns dx [P-fixedp,6], dz [M,HW], kx; with
+    return_system also the assembled, damped (H, g) that were solved (unknowns: 6 (P-fixedp) pose entries, then M*HW disparities)."""
     P, ht, wd = disps.shape
     HW = ht * wd
     N = len(ii)
@@ -87,6 +88,8 @@ def ba_dense(target, weight, eta, poses7, disps, intr, ii, jj, fixedp, ep=0.1, l
     zi = torch.arange(Pf * 6, nx)
     H[zi, zi] += eta.reshape(-1).to(DT) + 1e-7
     sol = torch.linalg.solve(H, g)
+    if return_system:
+        return sol[:Pf * 6].reshape(Pf, 6), sol[Pf * 6:].reshape(M, HW), kx, H, g
     return sol[:Pf * 6].reshape(Pf, 6), sol[Pf * 6:].reshape(M, HW), kx
 
 

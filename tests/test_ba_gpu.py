@@ -12,6 +12,7 @@ from cut3r_slam_amd.ba import BA  # noqa: E402
 from cut3r_slam_amd.lietorch import SE3  # noqa: E402
 from oracle import ba_oracle as BO  # noqa: E402
 from oracle import lie_oracle as LO  # noqa: E402
+from tests.ba_scenes import mono_prior_inputs, mono_prior_ref, scene as _scene  # noqa: E402
 
 DEV = "cuda:0"
 
@@ -30,35 +31,6 @@ def test_corr_index_forward_backward_vs_grid_sample():
     lhs = float((out.double() * G.double()).sum())
     rhs = float((vol.to(DEV).double() * gv.double()).sum())
     assert abs(lhs - rhs) < 1e-4 * max(1.0, abs(lhs))
-
-
-def _scene(P, ht, wd, seed):
-    g = np.random.default_rng(seed)
-    fx = fy = 0.8 * wd
-    intr = np.tile(np.array([fx, fy, wd / 2 - 0.5, ht / 2 - 0.5]), (P, 1))
-    # world->camera poses near identity, moving sideways; inverse depths ~ 0.4
-    tang = np.zeros((P, 6))
-    tang[:, 0] = np.linspace(0, 0.6, P) + g.normal(0, 0.02, P)
-    tang[:, 1:3] = g.normal(0, 0.03, (P, 2))
-    tang[:, 3:] = g.normal(0, 0.03, (P, 3))
-    poses = np.stack([LO.matrix_to_data(1, LO.exp_matrix(1, a)) for a in tang])
-    disps = g.uniform(0.3, 0.6, (P, ht, wd))
-    ii, jj = [], []
-    for i in range(P):
-        for j in range(P):
-            if i != j and abs(i - j) <= 2:
-                ii.append(i); jj.append(j)
-    ii, jj = np.array(ii), np.array(jj)
-    N = len(ii)
-    # targets: the true projections under perturbed geometry (so the residual is small but non-zero)
-    G = BO.se3_matrix(poses)
-    tgt = np.zeros((N, ht, wd, 2))
-    for e in range(N):
-        c, _ = BO.project(G[jj[e]] @ torch.linalg.inv(G[ii[e]]), torch.from_numpy(disps[ii[e]] * 1.05), intr[ii[e]], intr[jj[e]], ht, wd)
-        tgt[e] = c.reshape(ht, wd, 2).numpy() + g.normal(0, 0.3, (ht, wd, 2))
-    wgt = g.uniform(0.2, 1.0, (N, ht, wd, 2))
-    eta = g.uniform(1e-3, 1e-2, (len(np.unique(ii)), ht, wd))
-    return poses, disps, intr, ii, jj, tgt, wgt, eta
 
 
 @pytest.mark.parametrize("P,ht,wd,fixedp", [(4, 6, 8, 1), (6, 12, 16, 2)])
@@ -159,34 +131,8 @@ def test_schur_solve_mono_prior_matches_fp64_restatement_including_the_covarianc
     covariance) against the same formulas in fp64 torch on the CPU, with GENERAL (not block-diagonal) Hs / Es; a non-SPD system gives
     the reference's swallowed failure: dso = 0, dz = w / C (CholeskySolver, chol.py:9-18).  Parity unpinned (dead code in the reference)."""
     from cut3r_slam_amd.ba import schur_solve_mono_prior
-    g = torch.Generator().manual_seed(4)
-    M, D, HW = 3, 6, 40
-    Es = torch.randn(1, M, M, D, HW, generator=g, dtype=torch.float64) * 0.3
-    A = torch.randn(M * D, M * D, generator=g, dtype=torch.float64)
-    Hfull = A @ A.T + 4.0 * torch.eye(M * D, dtype=torch.float64)
-    Hs = Hfull.reshape(M, D, M, D).permute(0, 2, 1, 3)[None].contiguous()
-    vs = torch.randn(1, M, D, generator=g, dtype=torch.float64)
-    C = torch.rand(1, M, HW, generator=g, dtype=torch.float64) * 2 + 6.0
-    w = torch.randn(1, M, HW, generator=g, dtype=torch.float64)
-
-    def ref(C, w, Hs, Es, vs, ep=0.1, lm=1e-4):
-        Q = (1.0 / C).view(1, M * HW, 1)
-        wv = w.reshape(1, M * HW, 1)
-        H = Hs.permute(0, 1, 3, 2, 4).reshape(1, M * D, M * D)
-        E = Es.permute(0, 1, 3, 2, 4).reshape(1, M * D, M * HW)
-        v = vs.reshape(1, M * D, 1)
-        H = H + (ep + lm * H) * torch.eye(M * D, dtype=torch.float64)
-        Et = E.transpose(1, 2)
-        S = H - E @ (Q * Et)
-        v = v - E @ (Q * wv)
-        L = torch.linalg.cholesky(S)
-        dso = torch.cholesky_solve(v, L)
-        dz = Q * (wv - Et @ dso)
-        Fm = torch.linalg.solve_triangular(L, E * Q[..., 0][:, None], upper=False)
-        cov = (Fm ** 2).sum(1) + Q[..., 0]
-        return dso.reshape(1, M, D), dz.reshape(1, M, HW), cov.reshape(M, HW)
-
-    dso_r, dz_r, cov_r = ref(C, w, Hs, Es, vs)
+    C, w, Hs, Es, vs = mono_prior_inputs(3, 6, 40, 4)
+    dso_r, dz_r, cov_r = mono_prior_ref(C, w, Hs, Es, vs)
     f = lambda t: t.float().to(DEV)
     dso, dz, cov = schur_solve_mono_prior(f(C), f(w), f(Hs), f(Es), f(vs), dzcov=True)
     torch.cuda.synchronize()
