@@ -99,7 +99,12 @@ SIGNATURES = {
                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "cut3r_lc_optimize_terms": [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p],
+    "cut3r_lc_optimize_sim3": [c_void_p, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_int, c_int, c_ll, c_int, c_float,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "cut3r_lc_optimize_terms_sim3": [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p],
     "cut3r_transform_submaps": [c_void_p, c_void_p, c_int, c_ll, c_void_p],
+    "cut3r_scale_planes": [c_void_p, c_void_p, c_int, c_ll, c_void_p],
     "cut3r_corr_index_forward": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "cut3r_corr_index_backward": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "cut3r_ba_workspace_floats": [c_int, c_int, c_int, c_int, c_int, c_int],

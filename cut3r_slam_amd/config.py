@@ -7,6 +7,13 @@ The schema mirrors the parameter names/shapes of the reference module tree
  /root/reference/src/croco/models/dpt_block.py:281-480) so that a reference checkpoint's
 ``ckpt["model"]`` loads into this runtime unchanged.  tests/golden/make_fixtures.py asserts this
 schema equals ``ARCroco3DStereo(cfg).state_dict()`` key-for-key, shape-for-shape.
+
+The run-time (YAML / dict) configuration is separate; its loop-closure keys live under ``Tracking.frontend``:
+  iteration   Adam iterations of a loop closure's submap optimisation; 0 switches loop closure off.
+  loop_group  "se3" (default, the reference's rigid correction per submap) or "sim3": one similarity per submap, so that a loop
+              whose two ends disagree in scale can be closed.  In "sim3" mode poses stay rigid, the depth maps of the rewritten
+              keyframes are multiplied by their submap's scale, and the mapper receives 8-wide Sim3 ``pose_updates``
+              (track_backend.py, gs_mapper.GSMapper.gaussain_update).  No counterpart in the reference.
 """
 from __future__ import annotations
 

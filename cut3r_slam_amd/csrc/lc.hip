@@ -10,6 +10,10 @@
 //              matrix(exp(xi)) with forward-mode duals (lie_math.h), Adam step, lane 0 writes the new 3x4 matrix.
 // Loss (identical to the reference):  mean_{masked (b,n), xyz} |T_b last_b - T_{b+1} first_{b+1}|
 //                                    + mean_{n, xyz} |T_{B-1} cur - cur_lc|,  T_0 = I fixed.
+// The group of the corrections is a template parameter of the two Adam kernels: SE3 (the reference's; xi [.,6]) or Sim3 (xi [.,7] =
+// [tau, phi, sigma], T = [e^sigma R | W tau]; no counterpart in the reference: the tracker chains windows by a depth scale, and a loop
+// whose ends disagree in scale leaves a residual no rigid correction removes).  lc_accum / lc_terms_accum produce the gradient with respect
+// to a general 3x4 T and are shared; scale_planes rescales the depth maps of the keyframes a Sim3 correction moves.
 #include "common.h"
 #include "lie_math.h"
 #include "../../include/cut3r_hip.h"
@@ -113,9 +117,12 @@ DEVINL void lc_loss_row(const float* __restrict__ partial, int rows, float* __re
 // one wave per optimised submap b = 1..B-1  (b = 0 is the fixed identity; its wave reports the loss when asked to).
 // Lanes 0..11 each sum one gradient element over the partial rows in block order (the same order a single thread would
 // use), the 12 sums are broadcast and every lane carries the (tiny) dual-number pull-back; lane 0 writes.
+// GRP: the group of the corrections (lie_math.h: 1 = SE3, xi [B,6]; 2 = Sim3, xi [B,7] = [tau, phi, sigma], T = [e^sigma R | W tau]).
+template <int GRP>
 __global__ __launch_bounds__(64) void lc_adam_kernel(const float* __restrict__ partial, int nblk, int B, float* __restrict__ xi,
                                                      float* __restrict__ m, float* __restrict__ v, float* __restrict__ T,
                                                      float* __restrict__ loss_out, int step, AdamHyper h) {
+    constexpr int K = tdim(GRP);
     const int b = blockIdx.x;
     if (b == 0) {
         if (loss_out) lc_loss_row(partial, B * nblk, loss_out, step);
@@ -143,34 +150,34 @@ __global__ __launch_bounds__(64) void lc_adam_kernel(const float* __restrict__ p
 #pragma unroll
         for (int k = 0; k < 12; k++) G[k] = __shfl(g, k);
     }
-    typedef Dual<6> D;
-    D a[6], X[7], M[16];
+    typedef Dual<K> D;
+    D a[K], X[ddim(GRP)], M[16];
 #pragma unroll
-    for (int k = 0; k < 6; k++) { a[k] = D(xi[(size_t)b * 6 + k]); a[k].d[k] = 1.f; }
-    f_exp<1, D>(a, X);
-    f_matrix<1, D>(X, M);
+    for (int k = 0; k < K; k++) { a[k] = D(xi[(size_t)b * K + k]); a[k].d[k] = 1.f; }
+    f_exp<GRP, D>(a, X);
+    f_matrix<GRP, D>(X, M);
     const float bc1 = 1.f - powf(h.b1, (float)(step + 1)), bc2 = 1.f - powf(h.b2, (float)(step + 1));
-    float nx[6], nm[6], nv[6];
+    float nx[K], nm[K], nv[K];
 #pragma unroll
-    for (int j = 0; j < 6; j++) {
+    for (int j = 0; j < K; j++) {
         float g = 0.f;
 #pragma unroll
         for (int r = 0; r < 3; r++)
 #pragma unroll
             for (int c = 0; c < 4; c++) g += G[r * 4 + c] * M[r * 4 + c].d[j];
-        const float mj = h.b1 * m[(size_t)b * 6 + j] + (1.f - h.b1) * g;
-        const float vj = h.b2 * v[(size_t)b * 6 + j] + (1.f - h.b2) * g * g;
+        const float mj = h.b1 * m[(size_t)b * K + j] + (1.f - h.b1) * g;
+        const float vj = h.b2 * v[(size_t)b * K + j] + (1.f - h.b2) * g * g;
         nm[j] = mj;
         nv[j] = vj;
         // torch.optim.Adam: step_size = lr / bc1 ; denom = sqrt(v)/sqrt(bc2) + eps
-        nx[j] = xi[(size_t)b * 6 + j] - (h.lr / bc1) * mj / (sqrtf(vj) / sqrtf(bc2) + h.eps);
+        nx[j] = xi[(size_t)b * K + j] - (h.lr / bc1) * mj / (sqrtf(vj) / sqrtf(bc2) + h.eps);
     }
-    float Xf[7], Mf[16];
-    f_exp<1, float>(nx, Xf);
-    f_matrix<1, float>(Xf, Mf);
+    float Xf[ddim(GRP)], Mf[16];
+    f_exp<GRP, float>(nx, Xf);
+    f_matrix<GRP, float>(Xf, Mf);
     if (threadIdx.x == 0) {
 #pragma unroll
-        for (int j = 0; j < 6; j++) { m[(size_t)b * 6 + j] = nm[j]; v[(size_t)b * 6 + j] = nv[j]; xi[(size_t)b * 6 + j] = nx[j]; }
+        for (int j = 0; j < K; j++) { m[(size_t)b * K + j] = nm[j]; v[(size_t)b * K + j] = nv[j]; xi[(size_t)b * K + j] = nx[j]; }
 #pragma unroll
         for (int k = 0; k < 12; k++) T[(size_t)b * 12 + k] = Mf[k];
     }
@@ -229,10 +236,12 @@ __global__ __launch_bounds__(LC_BLOCK) void lc_terms_accum_kernel(const LcTerm* 
 
 // one wave per transform p = 1..P-1 (p = 0 is the fixed identity and reports the loss): lanes 0..11 gather, in term order,
 // the partial rows of the terms that reference p
+template <int GRP>
 __global__ __launch_bounds__(64) void lc_terms_adam_kernel(const LcTerm* __restrict__ terms, int n_terms, const float* __restrict__ partial,
                                                            int nblk, int P, float* __restrict__ xi, float* __restrict__ m,
                                                            float* __restrict__ v, float* __restrict__ T, float* __restrict__ loss_out,
                                                            int step, AdamHyper h) {
+    constexpr int K = tdim(GRP);
     const int b = blockIdx.x;
     if (b == 0) {
         if (loss_out) lc_loss_row(partial, n_terms * nblk, loss_out, step);
@@ -269,33 +278,33 @@ __global__ __launch_bounds__(64) void lc_terms_adam_kernel(const LcTerm* __restr
 #pragma unroll
         for (int k = 0; k < 12; k++) G[k] = __shfl(g, k);
     }
-    typedef Dual<6> D;
-    D a[6], X[7], M[16];
+    typedef Dual<K> D;
+    D a[K], X[ddim(GRP)], M[16];
 #pragma unroll
-    for (int k = 0; k < 6; k++) { a[k] = D(xi[(size_t)b * 6 + k]); a[k].d[k] = 1.f; }
-    f_exp<1, D>(a, X);
-    f_matrix<1, D>(X, M);
+    for (int k = 0; k < K; k++) { a[k] = D(xi[(size_t)b * K + k]); a[k].d[k] = 1.f; }
+    f_exp<GRP, D>(a, X);
+    f_matrix<GRP, D>(X, M);
     const float bc1 = 1.f - powf(h.b1, (float)(step + 1)), bc2 = 1.f - powf(h.b2, (float)(step + 1));
-    float nx[6], nm[6], nv[6];
+    float nx[K], nm[K], nv[K];
 #pragma unroll
-    for (int j = 0; j < 6; j++) {
+    for (int j = 0; j < K; j++) {
         float g = 0.f;
 #pragma unroll
         for (int r = 0; r < 3; r++)
 #pragma unroll
             for (int c = 0; c < 4; c++) g += G[r * 4 + c] * M[r * 4 + c].d[j];
-        const float mj = h.b1 * m[(size_t)b * 6 + j] + (1.f - h.b1) * g;
-        const float vj = h.b2 * v[(size_t)b * 6 + j] + (1.f - h.b2) * g * g;
+        const float mj = h.b1 * m[(size_t)b * K + j] + (1.f - h.b1) * g;
+        const float vj = h.b2 * v[(size_t)b * K + j] + (1.f - h.b2) * g * g;
         nm[j] = mj;
         nv[j] = vj;
-        nx[j] = xi[(size_t)b * 6 + j] - (h.lr / bc1) * mj / (sqrtf(vj) / sqrtf(bc2) + h.eps);
+        nx[j] = xi[(size_t)b * K + j] - (h.lr / bc1) * mj / (sqrtf(vj) / sqrtf(bc2) + h.eps);
     }
-    float Xf[7], Mf[16];
-    f_exp<1, float>(nx, Xf);
-    f_matrix<1, float>(Xf, Mf);
+    float Xf[ddim(GRP)], Mf[16];
+    f_exp<GRP, float>(nx, Xf);
+    f_matrix<GRP, float>(Xf, Mf);
     if (threadIdx.x == 0) {
 #pragma unroll
-        for (int j = 0; j < 6; j++) { m[(size_t)b * 6 + j] = nm[j]; v[(size_t)b * 6 + j] = nv[j]; xi[(size_t)b * 6 + j] = nx[j]; }
+        for (int j = 0; j < K; j++) { m[(size_t)b * K + j] = nm[j]; v[(size_t)b * K + j] = nv[j]; xi[(size_t)b * K + j] = nx[j]; }
 #pragma unroll
         for (int k = 0; k < 12; k++) T[(size_t)b * 12 + k] = Mf[k];
     }
@@ -313,16 +322,18 @@ __global__ __launch_bounds__(256) void transform_submaps_kernel(float* __restric
     }
 }
 
-}  // namespace
-
-extern "C" int cut3r_lc_workspace_floats(int B, int N) {
-    const int nblk = (N + LC_BLOCK * LC_PPT - 1) / (LC_BLOCK * LC_PPT);
-    return B * nblk * LC_ROW;
+// in-place plane i <- scale[i] * plane i (the depth maps of the keyframes a Sim3 correction rescales): one fp32 multiply per element
+__global__ __launch_bounds__(256) void scale_planes_kernel(float* __restrict__ planes, const float* __restrict__ scale, long long per_plane) {
+    const float s = scale[blockIdx.y];
+    float* p = planes + (size_t)blockIdx.y * per_plane;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < (size_t)per_plane; i += (size_t)gridDim.x * blockDim.x) p[i] *= s;
 }
 
-extern "C" int cut3r_lc_optimize(const float* first, const float* last, long long sub_stride, const unsigned char* mask,
-                                 const float* cur, const float* cur_lc, int B, int N, long long n_masked, int iters, float lr,
-                                 float* xi, float* adam_m, float* adam_v, float* T, float* workspace, float* loss_out, void* stream) {
+// the iteration loop of the chain form / the term-list form for either group
+template <int G>
+int lc_optimize_run(const float* first, const float* last, long long sub_stride, const unsigned char* mask, const float* cur,
+                    const float* cur_lc, int B, int N, long long n_masked, int iters, float lr, float* xi, float* adam_m, float* adam_v,
+                    float* T, float* workspace, float* loss_out, void* stream) {
     if (!first || !last || !cur || !cur_lc || !xi || !adam_m || !adam_v || !T || !workspace) return CUT3R_ERR_ARG;
     if (B < 2 || N <= 0 || iters < 0 || n_masked < 0) return CUT3R_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
@@ -333,13 +344,14 @@ extern "C" int cut3r_lc_optimize(const float* first, const float* last, long lon
     for (int it = 0; it < iters; it++) {
         hipLaunchKernelGGL(lc_accum_kernel, dim3(nblk, B), dim3(LC_BLOCK), 0, s, first, last, sub_stride, mask, cur, cur_lc, T, B, N,
                            w_fl, w_cur, workspace, nblk);
-        hipLaunchKernelGGL(lc_adam_kernel, dim3(B), dim3(64), 0, s, workspace, nblk, B, xi, adam_m, adam_v, T, loss_out, it, h);
+        hipLaunchKernelGGL(lc_adam_kernel<G>, dim3(B), dim3(64), 0, s, workspace, nblk, B, xi, adam_m, adam_v, T, loss_out, it, h);
     }
     return cut3r_check_launch();
 }
 
-extern "C" int cut3r_lc_optimize_terms(const void* terms_dev, int n_terms, int P, int N, int iters, float lr, float* xi, float* adam_m,
-                                       float* adam_v, float* T, float* workspace, float* loss_out, void* stream) {
+template <int G>
+int lc_optimize_terms_run(const void* terms_dev, int n_terms, int P, int N, int iters, float lr, float* xi, float* adam_m, float* adam_v,
+                          float* T, float* workspace, float* loss_out, void* stream) {
     static_assert(sizeof(LcTerm) == sizeof(cut3r_lc_term), "cut3r_lc_term layout");
     if (!terms_dev || !xi || !adam_m || !adam_v || !T || !workspace) return CUT3R_ERR_ARG;
     if (n_terms < 1 || P < 2 || N <= 0 || iters < 0) return CUT3R_ERR_ARG;
@@ -349,10 +361,41 @@ extern "C" int cut3r_lc_optimize_terms(const void* terms_dev, int n_terms, int P
     const LcTerm* terms = (const LcTerm*)terms_dev;
     for (int it = 0; it < iters; it++) {
         hipLaunchKernelGGL(lc_terms_accum_kernel, dim3(nblk, n_terms), dim3(LC_BLOCK), 0, s, terms, T, N, workspace, nblk);
-        hipLaunchKernelGGL(lc_terms_adam_kernel, dim3(P), dim3(64), 0, s, terms, n_terms, workspace, nblk, P, xi, adam_m, adam_v, T,
+        hipLaunchKernelGGL(lc_terms_adam_kernel<G>, dim3(P), dim3(64), 0, s, terms, n_terms, workspace, nblk, P, xi, adam_m, adam_v, T,
                            loss_out, it, h);
     }
     return cut3r_check_launch();
+}
+
+}  // namespace
+
+extern "C" int cut3r_lc_workspace_floats(int B, int N) {
+    const int nblk = (N + LC_BLOCK * LC_PPT - 1) / (LC_BLOCK * LC_PPT);
+    return B * nblk * LC_ROW;
+}
+
+extern "C" int cut3r_lc_optimize(const float* first, const float* last, long long sub_stride, const unsigned char* mask,
+                                 const float* cur, const float* cur_lc, int B, int N, long long n_masked, int iters, float lr,
+                                 float* xi, float* adam_m, float* adam_v, float* T, float* workspace, float* loss_out, void* stream) {
+    return lc_optimize_run<1>(first, last, sub_stride, mask, cur, cur_lc, B, N, n_masked, iters, lr, xi, adam_m, adam_v, T, workspace,
+                              loss_out, stream);
+}
+
+extern "C" int cut3r_lc_optimize_sim3(const float* first, const float* last, long long sub_stride, const unsigned char* mask,
+                                      const float* cur, const float* cur_lc, int B, int N, long long n_masked, int iters, float lr,
+                                      float* xi, float* adam_m, float* adam_v, float* T, float* workspace, float* loss_out, void* stream) {
+    return lc_optimize_run<2>(first, last, sub_stride, mask, cur, cur_lc, B, N, n_masked, iters, lr, xi, adam_m, adam_v, T, workspace,
+                              loss_out, stream);
+}
+
+extern "C" int cut3r_lc_optimize_terms(const void* terms_dev, int n_terms, int P, int N, int iters, float lr, float* xi, float* adam_m,
+                                       float* adam_v, float* T, float* workspace, float* loss_out, void* stream) {
+    return lc_optimize_terms_run<1>(terms_dev, n_terms, P, N, iters, lr, xi, adam_m, adam_v, T, workspace, loss_out, stream);
+}
+
+extern "C" int cut3r_lc_optimize_terms_sim3(const void* terms_dev, int n_terms, int P, int N, int iters, float lr, float* xi, float* adam_m,
+                                            float* adam_v, float* T, float* workspace, float* loss_out, void* stream) {
+    return lc_optimize_terms_run<2>(terms_dev, n_terms, P, N, iters, lr, xi, adam_m, adam_v, T, workspace, loss_out, stream);
 }
 
 extern "C" int cut3r_transform_submaps(float* pts, const float* T, int B, long long points_per_submap, void* stream) {
@@ -360,5 +403,13 @@ extern "C" int cut3r_transform_submaps(float* pts, const float* T, int B, long l
     int gx = (int)((points_per_submap + 255) / 256);
     if (gx > 1024) gx = 1024;
     hipLaunchKernelGGL(transform_submaps_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, pts, T, points_per_submap);
+    return cut3r_check_launch();
+}
+
+extern "C" int cut3r_scale_planes(float* planes, const float* scale, int n, long long per_plane, void* stream) {
+    if (!planes || !scale || n <= 0 || n > 65535 || per_plane <= 0) return CUT3R_ERR_ARG;
+    int gx = (int)((per_plane + 255) / 256);
+    if (gx > 1024) gx = 1024;
+    hipLaunchKernelGGL(scale_planes_kernel, dim3(gx, n), dim3(256), 0, (hipStream_t)stream, planes, scale, per_plane);
     return cut3r_check_launch();
 }

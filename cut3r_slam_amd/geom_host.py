@@ -55,6 +55,24 @@ def matrices_to_pose_vecs(T: np.ndarray) -> np.ndarray:
     return np.concatenate([np.asarray(T[:, :3, 3], np.float32), q.astype(np.float32)], axis=1)
 
 
+def similarity_scale(S: np.ndarray) -> np.ndarray:
+    """S [...,3,4] (or [...,4,4]) = [sR | t] -> s = det(sR)^(1/3), fp64"""
+    return np.cbrt(np.linalg.det(np.asarray(S, np.float64)[..., :3, :3]))
+
+
+def similarity_on_poses(S: np.ndarray, c2w: np.ndarray):
+    """A similarity [sR | t] per camera (S [n,3,4] or [n,4,4], or one for all) applied to camera-to-world matrices c2w [n,4,4] with the
+    result kept RIGID: rotation R R0, centre s R c0 + t (the camera moves with the rescaled scene, its axes stay orthonormal; the factor s
+    goes to the depth maps).  fp64 inside; returns (c2w' [n,4,4] fp32, s [n] fp64).  For s = 1 this is S @ c2w."""
+    c2w = np.asarray(c2w, np.float64).reshape(-1, 4, 4)
+    S = np.broadcast_to(np.asarray(S, np.float64)[..., :3, :], (len(c2w), 3, 4))
+    s = similarity_scale(S)
+    out = np.tile(np.eye(4), (len(c2w), 1, 1))
+    out[:, :3, :3] = (S[:, :, :3] / s[:, None, None]) @ c2w[:, :3, :3]
+    out[:, :3, 3] = np.einsum("nij,nj->ni", S[:, :, :3], c2w[:, :3, 3]) + S[:, :, 3]
+    return out.astype(np.float32), s
+
+
 def inv4(T: np.ndarray) -> np.ndarray:
     return np.linalg.inv(np.asarray(T, np.float32)).astype(np.float32)
 

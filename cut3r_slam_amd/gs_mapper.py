@@ -876,23 +876,35 @@ class GSMapper:
         Orientation: the reference multiplies `SO3(update[:, 3:]) * SO3(get_rotation)`, i.e. it reads the Gaussians' (r, x, y, z)
         quaternions as lietorch's (x, y, z, w).  That is exact only for isotropic Gaussians; the default here composes the rotations in
         one convention (a rigid correction of the whole scene then leaves every rendering unchanged, which the test checks);
-        reference_quat_order=True reproduces the reference's arithmetic."""
+        reference_quat_order=True reproduces the reference's arithmetic.
+        `pose_updates` [m,8] (t, q_xyzw, s: Sim3 data, the tracker's loop_group = "sim3"; no counterpart in the reference): positions
+        become s R x + t, orientations compose as above, the log-scales grow by log s, and the stored depth of every updated viewpoint
+        is multiplied by the scale of its submap under the tracker's rule (camera j of the packet takes row min(j // 5, m - 1)); the
+        corrected poses it hands over are rigid.  A similarity of the whole scene then leaves every colour rendering unchanged and
+        multiplies the rendered depth by s."""
         with torch.no_grad():
             w2cs = torch.inverse(pose_vec_to_matrix(torch.as_tensor(packet["camera_pose"]).float().to(self.device)))
+            upd = torch.as_tensor(packet["pose_updates"]).float().to(self.device)
+            if upd.dim() != 2 or upd.shape[1] not in (7, 8):
+                raise ValueError(f"pose_updates: [m,7] (SE3) or [m,8] (Sim3), got {tuple(upd.shape)}")
+            sim3 = upd.shape[1] == 8
             update_idx = []
             for i, k in enumerate(packet["camera_idx"]):
                 if k in self.viewpoints and i < w2cs.shape[0]:
                     update_idx.append(k)
                     self.viewpoints[k].update_RT(w2cs[i, :3, :3], w2cs[i, :3, 3])
+                    if sim3:
+                        self.viewpoints[k].depth = self.viewpoints[k].depth * upd[min(i // 5, upd.shape[0] - 1), 7]
             sub = torch.as_tensor(list(packet["submap_idx"]), device=self.device, dtype=torch.int32)
-            upd = torch.as_tensor(packet["pose_updates"]).float().to(self.device)
+            scale, upd = (upd[:, 7], upd[:, :7].contiguous()) if sim3 else (None, upd)
             hit = self.gaussians.kf_id[:, None] == sub[None, :]
             gi = hit.any(dim=1).nonzero()[:, 0]
             if gi.numel():
                 row = hit[gi].float().argmax(dim=1)
                 T = SE3(upd[row]).matrix()
                 gm = self.gaussians
-                xyz = (T[:, :3, :3] @ gm.p["xyz"].detach()[gi][:, :, None])[:, :, 0] + T[:, :3, 3]
+                xyz = (T[:, :3, :3] @ gm.p["xyz"].detach()[gi][:, :, None])[:, :, 0]
+                xyz = (scale[row][:, None] * xyz if sim3 else xyz) + T[:, :3, 3]
                 rot = gm.get_rotation.detach()[gi]
                 q_u = upd[row][:, 3:]                                        # (x, y, z, w)
                 if reference_quat_order:
@@ -901,6 +913,8 @@ class GSMapper:
                     new_rot = _quat_mult(torch.cat([q_u[:, 3:], q_u[:, :3]], -1), rot)
                 gm.theta.data[gi, 0:3] = xyz
                 gm.theta.data[gi, 10:14] = new_rot
+                if sim3:
+                    gm.theta.data[gi, 7:10] += torch.log(scale[row])[:, None]
                 gm.reset_moments(gi)
                 gm.reset_densification_stats()
         for k in update_idx:

@@ -641,10 +641,20 @@ def resize_linear_u8(img_hwc, H1, W1, chw_out=True, out=None):
 
 
 # ------------------------------------------------------------------------------------------------ loop closure
-def lc_optimize(submaps, mask, cur, cur_lc, iters, lr=5e-4, return_loss=False):
+LC_GROUPS = {"se3": (6, ""), "sim3": (7, "_sim3")}          # group -> (tangent dimension, suffix of the C entry points)
+
+
+def _lc_group(group):
+    _req(group in LC_GROUPS, f"group: one of {sorted(LC_GROUPS)}, not {group!r}")
+    return LC_GROUPS[group]
+
+
+def lc_optimize(submaps, mask, cur, cur_lc, iters, lr=5e-4, return_loss=False, group="se3"):
     """Fused Adam over per-submap se(3) corrections (track_backend.py:256-299).  submaps: [B,6,h,w,3] fp32 contiguous
     (slot 0 = first, slot 5 = last pointmap of each submap); mask: bool/uint8 [B-1,h*w] or None; cur, cur_lc: [h*w,3].
-    Returns (xi [B,6], T [B,3,4]) (+ per-iteration loss)."""
+    Returns (xi [B,6], T [B,3,4]) (+ per-iteration loss).  group="sim3": the same objective over similarities, xi [B,7] =
+    [tau, phi, sigma], T = [e^sigma R | W tau]."""
+    K, sfx = _lc_group(group)
     _cuda(submaps, mask, cur, cur_lc)
     _req(submaps.dtype == F32 and submaps.dim() == 5 and submaps.is_contiguous() and submaps.shape[1] == 6 and submaps.shape[4] == 3, "submaps [B,6,h,w,3]")
     B = submaps.shape[0]
@@ -660,23 +670,25 @@ def lc_optimize(submaps, mask, cur, cur_lc, iters, lr=5e-4, return_loss=False):
     else:
         n_masked = (B - 1) * N
     lib = _lib.load()
-    xi = torch.zeros(B, 6, device=dev)
+    xi = torch.zeros(B, K, device=dev)
     m, v = torch.zeros_like(xi), torch.zeros_like(xi)
     T = torch.eye(4, device=dev)[:3].reshape(1, 12).repeat(B, 1).contiguous()
     ws = torch.empty(lib.cut3r_lc_workspace_floats(B, N), device=dev)
     loss = torch.zeros(max(iters, 1), device=dev) if return_loss else None
     first = submaps
     last_ptr = C.c_void_p(submaps.data_ptr() + 5 * N * 3 * 4)
-    check(lib.cut3r_lc_optimize(_p(first), last_ptr, 6 * N * 3, _p(mask), _p(cur), _p(cur_lc), B, N, n_masked, int(iters), float(lr),
-                                _p(xi), _p(m), _p(v), _p(T), _p(ws), _p(loss), _stream()), "cut3r_lc_optimize")
+    fn = "cut3r_lc_optimize" + sfx
+    check(getattr(lib, fn)(_p(first), last_ptr, 6 * N * 3, _p(mask), _p(cur), _p(cur_lc), B, N, n_masked, int(iters), float(lr),
+                           _p(xi), _p(m), _p(v), _p(T), _p(ws), _p(loss), _stream()), fn)
     T = T.view(B, 3, 4)
     return (xi, T, loss) if return_loss else (xi, T)
 
 
-def lc_optimize_terms(terms, P, N, iters, lr=5e-4, return_loss=False):
+def lc_optimize_terms(terms, P, N, iters, lr=5e-4, return_loss=False, group="se3"):
     """Fused Adam over P-1 se(3) vectors for a list of L1 terms (track_backend.py:400-461).  terms: list of
     (a [N,3] fp32 cuda, ia, c [N,3] fp32 cuda, ic, weight, mask uint8 [N] | None) with transform indices in [0, P), 0 = the
-    fixed identity.  Returns (xi [P,6], T [P,3,4]) (+ per-iteration loss)."""
+    fixed identity.  Returns (xi [P,6], T [P,3,4]) (+ per-iteration loss).  group="sim3": xi [P,7], as in lc_optimize."""
+    K, sfx = _lc_group(group)
     _req(len(terms) >= 1 and P >= 2, "at least one term and one free transform")
     keep = []
     arr = (_lib.LcTerm * len(terms))()
@@ -694,13 +706,14 @@ def lc_optimize_terms(terms, P, N, iters, lr=5e-4, return_loss=False):
     raw = bytes(arr)
     terms_dev = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev)
     lib = _lib.load()
-    xi = torch.zeros(P, 6, device=dev)
+    xi = torch.zeros(P, K, device=dev)
     m, v = torch.zeros_like(xi), torch.zeros_like(xi)
     T = torch.eye(4, device=dev)[:3].reshape(1, 12).repeat(P, 1).contiguous()
     ws = torch.empty(lib.cut3r_lc_workspace_floats(len(terms), N), device=dev)
     loss = torch.zeros(max(iters, 1), device=dev) if return_loss else None
-    check(lib.cut3r_lc_optimize_terms(_p(terms_dev), len(terms), int(P), int(N), int(iters), float(lr), _p(xi), _p(m), _p(v), _p(T), _p(ws),
-                                      _p(loss), _stream()), "cut3r_lc_optimize_terms")
+    fn = "cut3r_lc_optimize_terms" + sfx
+    check(getattr(lib, fn)(_p(terms_dev), len(terms), int(P), int(N), int(iters), float(lr), _p(xi), _p(m), _p(v), _p(T), _p(ws),
+                           _p(loss), _stream()), fn)
     T = T.view(P, 3, 4)
     return (xi, T, loss) if return_loss else (xi, T)
 
@@ -714,6 +727,18 @@ def transform_submaps(submaps, T):
     lib = _lib.load()
     check(lib.cut3r_transform_submaps(_p(submaps), _p(T), B, per, _stream()), "cut3r_transform_submaps")
     return submaps
+
+
+def scale_planes(planes, scale):
+    """in place: plane i of `planes` [n, ...] fp32 <- scale[i] * plane i (one fp32 multiply per element, one launch): the depth maps of
+    the keyframes a sim(3) loop correction rescales."""
+    _cuda(planes, scale)
+    n = planes.shape[0]
+    _req(planes.dtype == F32 and planes.is_contiguous() and planes.dim() >= 1 and 0 < n <= 65535 and planes.numel() > 0, "planes: contiguous fp32 [n<=65535, ...]")
+    _req(scale.dtype == F32 and scale.is_contiguous() and scale.numel() == n, "scale: contiguous fp32 [n]")
+    lib = _lib.load()
+    check(lib.cut3r_scale_planes(_p(planes), _p(scale), n, planes.numel() // n, _stream()), "cut3r_scale_planes")
+    return planes
 
 
 # ------------------------------------------------------------------------------------------------ TSDF fusion / mesh extraction

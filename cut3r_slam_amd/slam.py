@@ -20,7 +20,7 @@ DEFAULT_CONFIG = {
     "Tracking": {
         "motion_filter": {"thresh": 0.9, "skip": 5, "skip_blur": False, "kf_every": -1, "init_thresh": 4.0},
         "frontend": {"keyframe_thresh": 4.0, "frontend_thresh": 16.0, "frontend_window": 25, "frontend_radius": 2,
-                     "frontend_nms": 1, "mono_depth_alpha": 0.01, "iteration": 0},
+                     "frontend_nms": 1, "mono_depth_alpha": 0.01, "iteration": 0, "loop_group": "se3"},
     }
 }
 

@@ -8,6 +8,13 @@
               later loops -> chain + matched-submap + current-vs-lc terms, the same fused optimiser over a term list
                              (ops.lc_optimize_terms), Adam over the submap AND the lc-submap corrections
   rewrite   : every pointmap of every corrected submap in place (ops.transform_submaps) + the 7-float poses
+
+config["loop_group"] = "sim3" (default "se3", the reference's) optimises one SIMILARITY per submap instead: the tracker chains windows
+by a log-depth scale, so the two ends of a loop can disagree in scale, which no rigid correction removes.  The objective is unchanged,
+the group is enlarged (ops.lc_optimize*(group="sim3")).  The rewrite then keeps every pose rigid (rotation R R0, centre s R c + t,
+geom_host.similarity_on_poses) and multiplies the depth maps of the rewritten keyframes by their submap's scale (ops.scale_planes), so
+that pointmap, depth and pose stay consistent and the next window's chained scale inherits the correction; `pose_updates` carries Sim3
+data [m,8].  This mode has no counterpart in the reference.
 """
 from __future__ import annotations
 
@@ -18,7 +25,7 @@ import torch
 
 from . import geom_host as gh
 from . import ops
-from .lietorch import SE3
+from .lietorch import SE3, Sim3
 
 
 class TrackBackend:
@@ -28,6 +35,9 @@ class TrackBackend:
         self.model = slam.model
         self.graph = slam.graph
         self.loop_iters = int(config.get("iteration", 0))
+        self.loop_group = str(config.get("loop_group", "se3"))
+        if self.loop_group not in ops.LC_GROUPS:
+            raise ValueError(f"loop_group: one of {sorted(ops.LC_GROUPS)}, not {self.loop_group!r}")
         self._chain_ws = None
         self.downsample_ratio = slam.downsample_ratio
         self.conf_th = 0.05
@@ -131,6 +141,14 @@ class TrackBackend:
         # scipy's Rotation on the stack) -- and ONE upload of the world->camera rows
         i0, n = sub0 * 5, B * 5 + (1 if include_last else 0)
         c2w = gh.pose_vec_to_matrix(kf.pose[i0:i0 + n].numpy())
+        if self.loop_group == "sim3":
+            # poses stay rigid; the scale of each keyframe's submap goes to its depth map (one launch over the contiguous range)
+            row = np.minimum(np.arange(n) // 5, B - 1)
+            out, s = gh.similarity_on_poses(Th[row], c2w)
+            ops.scale_planes(kf.depth[i0:i0 + n], torch.from_numpy(s.astype(np.float32)).to(kf.depth.device))
+            new = gh.matrices_to_pose_vecs(out)
+            kf.set_poses(i0, new)
+            return new
         out = np.empty_like(c2w)
         for j in range(n):
             Ts = np.eye(4, dtype=np.float32)
@@ -147,9 +165,9 @@ class TrackBackend:
         B = block.shape[0]
         mask = (kf.conf_ds[sub0:sub1, 5] > 0).reshape(B - 1, -1) if B > 1 else None         # conf of each submap's last map
         cur = kf.submap_ds[sub1, idx_current % 5]
-        res = ops.lc_optimize(block.contiguous(), mask, cur, pointmap_current_lc, self.loop_iters, 5e-4, return_loss)
+        res = ops.lc_optimize(block.contiguous(), mask, cur, pointmap_current_lc, self.loop_iters, 5e-4, return_loss, group=self.loop_group)
         xi, T = res[0], res[1]
-        se3 = SE3.exp(xi)
+        se3 = Sim3.exp(xi) if self.loop_group == "sim3" else SE3.exp(xi)
         new_pose = self._rewrite(sub0, sub1, T)
         updates = {"pose_updates": se3.data, "submap_idx": range(sub0, sub1 + 1),
                    "camera_idx": range(sub0 * 5, (sub1 + 1) * 5 + 1), "camera_pose": torch.from_numpy(new_pose)}
@@ -185,9 +203,9 @@ class TrackBackend:
             terms.append((lc_all[k, 0], B + k, block[int(sub_matched_all[k]), 0], int(sub_matched_all[k]), w_c, None))
         for k in range(Bc):
             terms.append((pm_cur[k], int(sub_cur_all[k]), lc_all[k, N6 - 1], B + k, w_c, None))
-        res = ops.lc_optimize_terms(terms, B + Bc, N, self.loop_iters, 5e-4, return_loss)
+        res = ops.lc_optimize_terms(terms, B + Bc, N, self.loop_iters, 5e-4, return_loss, group=self.loop_group)
         xi, T = res[0], res[1]
-        se3 = SE3.exp(xi[:B].contiguous())
+        se3 = Sim3.exp(xi[:B].contiguous()) if self.loop_group == "sim3" else SE3.exp(xi[:B].contiguous())
         new_pose = self._rewrite(0, sub1, T[:B].contiguous())
         ops.transform_submaps(lc_all, T[B:].reshape(Bc, 12).contiguous())              # lc submaps moved by their matched transform (:513-516)
         for i in range(Bc - 1):

@@ -68,6 +68,8 @@ def main(argv=None):
     p.add_argument("--seed", type=int, default=0, help="seed of --synthetic-weights")
     p.add_argument("--small", action="store_true", help="debug: tiny architecture (with --synthetic-weights)")
     p.add_argument("--window-batch", type=int, default=1, help="tracking windows decoded together (1 = reference schedule)")
+    p.add_argument("--loop-sim3", action="store_true", help="loop closure optimises one similarity per submap (scale drift) instead of the "
+                   "reference's rigid correction: Tracking.frontend.loop_group = sim3")
     p.add_argument("--lookahead", type=int, default=1, help="overlap mode (kf_every = -1): hold back LOOKAHEAD x skip frames, encode their tested "
                    "frames as one batch and take the keyframe decisions on the device (1 = the reference's frame-by-frame loop; identical "
                    "results, latency LOOKAHEAD x skip frames; with --window-batch the found keyframes are tracked several windows at a time)")
@@ -155,6 +157,8 @@ def main(argv=None):
     if args.kf_every > 0:
         trk["motion_filter"]["kf_every"] = args.kf_every
     trk["frontend"]["window_batch"] = args.window_batch
+    if args.loop_sim3:
+        trk["frontend"]["loop_group"] = "sim3"
 
     if args.synthetic_weights:
         mcfg = tiny_config("dpt") if args.small else production_config()

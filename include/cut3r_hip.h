@@ -286,8 +286,21 @@ typedef struct cut3r_lc_term {
 } cut3r_lc_term;
 int cut3r_lc_optimize_terms(const void* terms_dev, int n_terms, int P, int N, int iters, float lr, float* xi, float* adam_m,
                             float* adam_v, float* T, float* workspace, float* loss_out, void* stream);
-/* in place p <- T_b p for the points_per_submap points of each of the B submaps (pts: [B, points_per_submap, 3]) */
+/* The same two optimisers over sim(3): one 7-vector [tau(3), phi(3), sigma] per transform, T = [e^sigma R | W tau] (Sophus /
+ * lietorch Sim3.exp), so that a loop whose two ends disagree in SCALE can be closed.  No counterpart in the reference (its
+ * loop closure is rigid); the objective, the accumulate launch, the workspace (cut3r_lc_workspace_floats) and every rule
+ * above are those of the se(3) entry points -- only xi/adam_m/adam_v are [B,7] / [P,7]. */
+int cut3r_lc_optimize_sim3(const float* first, const float* last, long long sub_stride, const unsigned char* mask, const float* cur,
+                           const float* cur_lc, int B, int N, long long n_masked, int iters, float lr, float* xi, float* adam_m,
+                           float* adam_v, float* T, float* workspace, float* loss_out, void* stream);
+int cut3r_lc_optimize_terms_sim3(const void* terms_dev, int n_terms, int P, int N, int iters, float lr, float* xi, float* adam_m,
+                                 float* adam_v, float* T, float* workspace, float* loss_out, void* stream);
+/* in place p <- T_b p for the points_per_submap points of each of the B submaps (pts: [B, points_per_submap, 3]); T_b is any
+ * 3x4 (rigid or a similarity) */
 int cut3r_transform_submaps(float* pts, const float* T, int B, long long points_per_submap, void* stream);
+/* in place planes[i] <- scale[i] * planes[i] for the n planes of per_plane floats each (planes: [n, per_plane], n <= 65535): the
+ * depth maps of the keyframes a sim(3) correction rescales.  One fp32 multiply per element, one launch. */
+int cut3r_scale_planes(float* planes, const float* scale, int n, long long per_plane, void* stream);
 
 /* ---- legacy dense-BA operators (`droid_backends` sources are absent from the reference) --------------
  * corr_index: replaces droid_backends.corr_index_forward/backward (call sites hislam2/modules/corr.py:12,19).
