@@ -199,6 +199,11 @@ SIGNATURES = {
     "cut3r_mesh_components_workspace_bytes": [c_int, c_int],
     "cut3r_mesh_components_count": [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_ll, c_void_p, c_void_p],
     "cut3r_mesh_components_emit": [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_ll] + [c_void_p] * 6 + [c_ll] * 6 + [c_void_p],
+    "cut3r_lpips_input": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
+    "cut3r_lpips_conv_out": [c_int, c_int, c_int, c_int],
+    "cut3r_lpips_conv": [c_void_p] * 4 + [c_int] * 10 + [c_void_p],
+    "cut3r_lpips_pool": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
+    "cut3r_lpips_tail": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
 }
 RESTYPES = {"cut3r_ba_workspace_floats": c_ll, "cut3r_gs_workspace_bytes": c_ll, "cut3r_schur_mono_prior_workspace_floats": c_ll,
             "cut3r_knn3_grid_workspace_bytes": c_ll, "cut3r_tsdf_mesh_workspace_bytes": c_ll, "cut3r_tsdf_sparse_assign_workspace_bytes": c_ll,

@@ -17,9 +17,10 @@ rasteriser.  Mirrors, with the same names, argument meaning
 
 The reference's backend cannot run here (CUDA rasteriser, open3d, munch): PARITY UNPINNED, covered by functional tests on a
 synthetic scene (tests/test_gs_mapper_gpu.py).  The rasteriser and the 3-NN search are the HIP kernels of csrc/gs.hip; the loss
-terms and the Adam updates are plain torch tensor arithmetic on the GPU.  Not built: GUI, Gaussian ply export and LPIPS (PSNR / SSIM of the keyframes and -- eval_rendering -- of the whole sequence,
-a safetensors checkpoint, -- cut3r_slam_amd/tsdf.py, fuse_mapper -- the TSDF mesh of the keyframe renders and -- eval_recon.py -- its
-reconstruction metrics are).
+terms and the Adam updates are plain torch tensor arithmetic on the GPU.  Not built: GUI and Gaussian ply export (PSNR / SSIM of the
+keyframes and -- eval_rendering -- of the whole sequence, LPIPS of both with the user's AlexNet weights -- cut3r_slam_amd/lpips.py,
+csrc/lpips.hip --, a safetensors checkpoint, -- cut3r_slam_amd/tsdf.py, fuse_mapper -- the TSDF mesh of the keyframe renders and
+-- eval_recon.py -- its reconstruction metrics are).
 `gaussain_update` (the map correction after a loop closure, :701-774) composes rotations consistently by default; see its docstring."""
 from __future__ import annotations
 
@@ -949,8 +950,8 @@ class GSMapper:
         return {"pointmaps": pms, "depths": depths, "poses": torch.stack(poses)}, list(current_window)
 
 
-    # ---- checkpoint / evaluation (gs_backend_per_frame.py:1088-1096; gaussian/utils/eval_utils.py:110-150 without LPIPS, whose
-    #      pretrained network is not available offline)
+    # ---- checkpoint / evaluation (gs_backend_per_frame.py:1088-1096; gaussian/utils/eval_utils.py:110-150; LPIPS with an
+    #      lpips.LPIPS object built from the user's weight files)
     def save(self, path):
         """the Gaussian map (parameters, optimiser moments, bookkeeping) as a safetensors file: nothing executable in the file"""
         from safetensors.torch import save_file
@@ -978,11 +979,14 @@ class GSMapper:
         g.grad_accum_abs = t["grad_accum_abs"] if "grad_accum_abs" in t else torch.zeros_like(g.grad_accum)
 
     @torch.no_grad()
-    def eval_rendering_kf(self):
+    def eval_rendering_kf(self, lpips=None):
         """eval_utils.py:110-150 over the mapper's own keyframes: PSNR on the pixels with a ground-truth colour (gt > 0) and SSIM per
         view -> dict(mean_psnr, mean_ssim, per_view).  With Training.compensate_exposure the rendering goes through the view's
-        exposure model before the clamp (eval_utils.py:127)"""
+        exposure model before the clamp (eval_utils.py:127).  lpips: None, or an lpips.LPIPS object (eval_utils.py:115,141,150): each view
+        is also scored on (img, gt), the rows become (k, psnr, ssim, lpips) and mean_lpips follows mean_ssim; a view below 31 pixels
+        either way is a ValueError before the first rendering."""
         exposure = bool(self.config["Training"].get("compensate_exposure", False))
+        self._check_lpips(lpips)
         rows = []
         for k in sorted(self.viewpoints):
             v = self.viewpoints[k]
@@ -994,9 +998,20 @@ class GSMapper:
             gt = v.original_image
             mask = gt > 0
             mse = ((img[mask] - gt[mask]) ** 2).mean() if mask.any() else torch.zeros((), device=self.device)
-            rows.append((k, float(20 * torch.log10(1.0 / torch.sqrt(mse.clamp_min(1e-12)))), float(ssim(img, gt))))
+            rows.append((k, float(20 * torch.log10(1.0 / torch.sqrt(mse.clamp_min(1e-12)))), float(ssim(img, gt)))
+                        + (() if lpips is None else (lpips(img.contiguous(), gt),)))
         n = max(1, len(rows))
-        return {"mean_psnr": sum(r[1] for r in rows) / n, "mean_ssim": sum(r[2] for r in rows) / n, "per_view": rows}
+        out = {"mean_psnr": sum(r[1] for r in rows) / n, "mean_ssim": sum(r[2] for r in rows) / n}
+        if lpips is not None:
+            out["mean_lpips"] = sum(r[3] for r in rows) / n
+        out["per_view"] = rows
+        return out
+
+    def _check_lpips(self, lpips):
+        """with an LPIPS object, the mapper's views must be large enough for it (lpips.check_size raises ValueError)"""
+        if lpips is not None and self._view_size() is not None:
+            from .lpips import check_size
+            check_size(*self._view_size())
 
     # ---- poses of frames the map was not trained on (gs_backend_per_frame.py:123-177) and the rendering evaluation of the whole
     #      sequence (gaussian/utils/eval_utils.py:14-105)
@@ -1069,7 +1084,7 @@ class GSMapper:
             return SE3_from_matrix(torch.inverse(get_pose(v))).detach().cpu()
 
     @torch.no_grad()
-    def eval_rendering(self, images, traj_tstamps, traj, kf_tstamps, gtdepthdir=None, out_dir=None, result_dir=None):
+    def eval_rendering(self, images, traj_tstamps, traj, kf_tstamps, gtdepthdir=None, out_dir=None, result_dir=None, lpips=None):
         """gaussian/utils/eval_utils.py:14-105 eval_rendering: renderings of the WHOLE sequence, also of frames the map was not trained on.
         images: the frames by index (a dict index -> frame or a sequence; u8 [3,h,w] / [1,3,h,w], brought to the mapper's size by
         _frame_image); traj_tstamps [n] / traj [n,7]: the full trajectory (camera->world, t + q_xyzw), looked up by tstamp; kf_tstamps: the
@@ -1079,8 +1094,11 @@ class GSMapper:
         eval_dense.read_depth_png, nearest resize) the depth L1 of the KEYFRAMES: invalid GT zeroes the rendered depth, pixels with
         rendered depth > 0 are averaged.  Returns dict(mean_psnr, mean_ssim, mean_l1, per_frame [(index, psnr, ssim)]) and writes the
         three means to <dir>/psnr/after_opt/final_result.json, dir = result_dir or out_dir (neither: nothing is written); with out_dir
-        also renders/image_after_opt/%06d.jpg and the 16-bit renders/depth_after_opt/%06d.png.  LPIPS is not built (its AlexNet
-        weights are not available): the reference's mean_lpips key is absent."""
+        also renders/image_after_opt/%06d.jpg and the 16-bit renders/depth_after_opt/%06d.png.  lpips: None (the reference's mean_lpips
+        key is then absent), or an lpips.LPIPS object (eval_utils.py:29,83,92): every scored frame is also scored on (img, gt), img the
+        clamped, exposure-compensated rendering that PSNR uses; the rows become (index, psnr, ssim, lpips) and mean_lpips is returned and
+        written between mean_ssim and mean_l1, the reference's key order.  A view below 31 pixels either way is a ValueError before the
+        loop."""
         import json
         import os
 
@@ -1091,6 +1109,7 @@ class GSMapper:
         kfs = {int(round(float(t))) for t in torch.as_tensor(kf_tstamps).reshape(-1).tolist()}
         own = {int(round(float(v.tstamp))): v for v in self.viewpoints.values() if v.tstamp is not None}
         gtdepths = sorted(os.listdir(gtdepthdir)) if gtdepthdir is not None else None
+        self._check_lpips(lpips)
         if out_dir is not None:
             from PIL import Image
             img_dir, dep_dir = os.path.join(out_dir, "renders", "image_after_opt"), os.path.join(out_dir, "renders", "depth_after_opt")
@@ -1133,10 +1152,13 @@ class GSMapper:
                 Image.fromarray(np.clip(depth * 6553.5, 0, 65535).astype(np.uint16)).save(os.path.join(dep_dir, f"{idx:06d}.png"))
             mask = gt > 0
             mse = ((img[mask] - gt[mask]) ** 2).mean() if mask.any() else torch.zeros((), device=self.device)
-            per_frame.append((idx, float(20 * torch.log10(1.0 / torch.sqrt(mse.clamp_min(1e-12)))), float(ssim(img, gt))))
+            per_frame.append((idx, float(20 * torch.log10(1.0 / torch.sqrt(mse.clamp_min(1e-12)))), float(ssim(img, gt)))
+                             + (() if lpips is None else (lpips(img, gt),)))
         m = max(1, len(per_frame))
-        out = {"mean_psnr": sum(r[1] for r in per_frame) / m, "mean_ssim": sum(r[2] for r in per_frame) / m,
-               "mean_l1": float(np.mean(l1)) if l1 else 0}
+        out = {"mean_psnr": sum(r[1] for r in per_frame) / m, "mean_ssim": sum(r[2] for r in per_frame) / m}
+        if lpips is not None:
+            out["mean_lpips"] = sum(r[3] for r in per_frame) / m
+        out["mean_l1"] = float(np.mean(l1)) if l1 else 0
         save = result_dir if result_dir is not None else out_dir
         if save is not None:
             d = os.path.join(save, "psnr", "after_opt")

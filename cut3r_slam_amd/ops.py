@@ -1423,3 +1423,65 @@ def mesh_components(verts, colors, faces, min_faces=None, keep_largest=None, cap
         timing["rounds"] = rounds
     return {"vertices": out_v[:Vo], "colors": None if out_c is None else out_c[:Vo], "faces": out_f[:Fo], "vertex_map": vmap, "face_map": fmap[:Fo],
             "labels": labels, "components": comps, "n_components": n_comp, "rounds": rounds}
+
+
+# ------------------------------------------------------------------------------------------------ LPIPS (csrc/lpips.hip)
+LPIPS_NORMS = {"torchmetrics": 0, "lpips": 1}
+
+
+def _lpips_act(x, name):
+    _cuda(x)
+    _req(x.dim() == 4 and x.dtype == F32 and x.is_contiguous() and x.numel() > 0, f"{name}: contiguous fp32 [n,H,W,C]")
+    return tuple(int(v) for v in x.shape)
+
+
+def lpips_input(a, b):
+    """a, b fp32 [B,3,H,W] in [0,1] -> channels-last fp32 [2B,H,W,3] = ((2 v - 1) - shift) / scale, the B images of a first"""
+    _cuda(a, b)
+    _req(a.dim() == 4 and a.shape[1] == 3 and a.shape == b.shape and a.numel() > 0, "a, b: [B,3,H,W] of one shape")
+    _req(a.dtype == F32 and b.dtype == F32 and a.is_contiguous() and b.is_contiguous(), "a, b: contiguous fp32")
+    B, _, H, W = a.shape
+    out = torch.empty(2 * B, H, W, 3, dtype=F32, device=a.device)
+    check(_lib.load().cut3r_lpips_input(_p(a), _p(b), B, H, W, _p(out), _stream()), "cut3r_lpips_input")
+    return out
+
+
+def lpips_conv(x, w, bias, stride, pad, impl=0):
+    """relu(conv(x) + bias): x [n,H,W,Ci], w [KH,KW,Ci,Co], bias [Co] -> [n,Ho,Wo,Co], every output the k-ascending fmaf chain from its
+    bias (impl 0: on the fp32 MFMA, the tile chosen by the number of rows; 1: the same chain on the VALU; 2 / 3: the MFMA kernel with 128- /
+    64-row tiles; all four give the same bits)"""
+    n, H, W, Ci = _lpips_act(x, "x")
+    _cuda(w, bias)
+    _req(w.dim() == 4 and w.dtype == F32 and w.is_contiguous() and w.shape[2] == Ci, f"w: contiguous fp32 [KH,KW,{Ci},Co]")
+    KH, KW, _, Co = (int(v) for v in w.shape)
+    _req(bias.shape == (Co,) and bias.dtype == F32 and bias.is_contiguous(), f"bias: contiguous fp32 [{Co}]")
+    lib = _lib.load()
+    Ho, Wo = lib.cut3r_lpips_conv_out(H, KH, stride, pad), lib.cut3r_lpips_conv_out(W, KW, stride, pad)
+    _req(Ho > 0 and Wo > 0, f"a {KH}x{KW} convolution of a {H}x{W} map has no output")
+    y = torch.empty(n, Ho, Wo, Co, dtype=F32, device=x.device)
+    check(lib.cut3r_lpips_conv(_p(x), _p(w), _p(bias), _p(y), n, H, W, Ci, Co, KH, KW, int(stride), int(pad), int(impl), _stream()),
+          f"cut3r_lpips_conv n={n} {H}x{W}x{Ci} -> {Co} k={KH}")
+    return y
+
+
+def lpips_pool(x):
+    """3x3 stride-2 max-pool without padding of a channels-last map"""
+    n, H, W, Cc = _lpips_act(x, "x")
+    _req(H >= 3 and W >= 3, f"a 3x3 pool of a {H}x{W} map has no output")
+    y = torch.empty(n, (H - 3) // 2 + 1, (W - 3) // 2 + 1, Cc, dtype=F32, device=x.device)
+    check(_lib.load().cut3r_lpips_pool(_p(x), _p(y), n, H, W, Cc, _stream()), "cut3r_lpips_pool")
+    return y
+
+
+def lpips_tail(feat, lin, score, accumulate, norm="torchmetrics"):
+    """one tap: feat [2B,Hl,Wl,C], lin [C] -> v [B,Hl,Wl]; score [B] fp64 (+)= the fp64 mean of v per pair, in a fixed order"""
+    n, H, W, Cc = _lpips_act(feat, "feat")
+    _cuda(lin, score)
+    _req(norm in LPIPS_NORMS, f"norm must be one of {sorted(LPIPS_NORMS)}")
+    _req(n % 2 == 0 and Cc % 4 == 0, "feat: an even number of images, C a multiple of 4")
+    _req(lin.shape == (Cc,) and lin.dtype == F32 and lin.is_contiguous(), f"lin: contiguous fp32 [{Cc}]")
+    _req(score.shape == (n // 2,) and score.dtype == torch.float64 and score.is_contiguous(), f"score: contiguous fp64 [{n // 2}]")
+    v = torch.empty(n // 2, H, W, dtype=F32, device=feat.device)
+    check(_lib.load().cut3r_lpips_tail(_p(feat), _p(lin), n // 2, H * W, Cc, LPIPS_NORMS[norm], int(bool(accumulate)), _p(v), _p(score),
+                                       _stream()), "cut3r_lpips_tail")
+    return v

@@ -11,7 +11,8 @@ small-component removal (cut3r_slam_amd/mesh_clean.py; scored into eval_recon_w{
 --eval-dense --gtdepthdir G --gt-traj T also <output>/3D_eval_results.txt, the dense point-cloud metrics of the keyframe depths against
 the GT depth maps (scripts/eval7_scenes_dense.py, cut3r_slam_amd/eval_dense.py); with --fill (implies --gs) also <output>/traj_full.txt,
 a pose for every frame from the first keyframe on (hislam2/util/trajectory_filler.py), and with --eval-render
-<output>/psnr/after_opt/final_result.json and <output>/renders/ (gaussian/utils/eval_utils.py:14-105).  The viewers are out of scope:
+<output>/psnr/after_opt/final_result.json and <output>/renders/ (gaussian/utils/eval_utils.py:14-105; with --lpips-weights FILE... also
+mean_lpips, cut3r_slam_amd/lpips.py).  The viewers are out of scope:
 --droidvis/--gsvis/--posedir/--weights are accepted and ignored, and so is --gtdepthdir without --eval-dense.  Without a checkpoint,
 `--synthetic-weights` runs the production-shape network with seeded random weights (throughput / plumbing runs only).
 """
@@ -84,6 +85,9 @@ def main(argv=None):
     p.add_argument("--eval-render", action="store_true", help="PSNR / SSIM (/ depth L1 of the keyframes with --gtdepthdir) of renderings of "
                    "every 5th frame, the keyframes and the last frame (gaussian/utils/eval_utils.py:14-105; needs --fill for the poses of "
                    "the non-keyframes) -> <output>/psnr/after_opt/final_result.json and <output>/renders/")
+    p.add_argument("--lpips-weights", type=str, nargs="+", default=None, metavar="FILE", help="local .safetensors / .pth files with the "
+                   "AlexNet `features` and the LPIPS `lin` layers (cut3r_slam_amd/lpips.py; never fetched): the evaluations of the Gaussian "
+                   "map also report LPIPS (gaussian/utils/eval_utils.py:29,92,115,150), mean_lpips in final_result.json; needs --gs")
     p.add_argument("--mesh", action="store_true", help="TSDF-fuse the keyframes and write <output>/tsdf_mesh_w{W:.1f}.ply per weight threshold "
                    "(scripts/run_replica.py:40-52 + tsdf_integrate.py)")
     p.add_argument("--voxel-size", type=float, default=0.03, help="TSDF voxel size in scene units (tsdf_integrate.py default)")
@@ -118,6 +122,8 @@ def main(argv=None):
     if args.fill_iters <= 0:
         p.error("--fill-iters must be > 0")
     args.gs = args.gs or args.fill
+    if args.lpips_weights and not args.gs:
+        p.error("--lpips-weights needs --gs (LPIPS scores the renderings of the Gaussian map)")
     if args.eval_dense and not (args.gtdepthdir and args.gt_traj):
         p.error("--eval-dense needs --gtdepthdir and --gt-traj")
     if args.gt_depth_scale <= 0 or args.dense_depth_trunc <= 0:
@@ -165,6 +171,11 @@ def main(argv=None):
         model = Cut3rModel(mcfg, synth_state_dict(mcfg, seed=args.seed), args.device, minimal=True)
     else:
         model = Cut3rModel.from_pretrained(args.ckpt_path, device=args.device, minimal=True)
+
+    lpips = None
+    if args.lpips_weights:
+        from cut3r_slam_amd.lpips import LPIPS, load_lpips_weights
+        lpips = LPIPS(load_lpips_weights(*args.lpips_weights), args.device)          # before the run: a bad file fails at once
 
     n_files = len(os.listdir(args.imagedir))
     buffer = min(1000, n_files // 5 + 150) if args.buffer < 0 else args.buffer
@@ -220,13 +231,15 @@ def main(argv=None):
             if args.eval_render:
                 n_kf = slam.keyframes.counter.value - 1
                 er = slam.mapper.eval_rendering(slam.images, ts_full, poses_full, slam.keyframes.tstamp[:n_kf],
-                                                gtdepthdir=args.gtdepthdir, out_dir=args.output)
-                print(f"render eval over {len(er['per_frame'])} frames: PSNR {er['mean_psnr']:.2f} dB, SSIM {er['mean_ssim']:.4f}, depth L1 "
+                                                gtdepthdir=args.gtdepthdir, out_dir=args.output, lpips=lpips)
+                lp = f", LPIPS {er['mean_lpips']:.4f}" if lpips is not None else ""
+                print(f"render eval over {len(er['per_frame'])} frames: PSNR {er['mean_psnr']:.2f} dB, SSIM {er['mean_ssim']:.4f}{lp}, depth L1 "
                       f"{er['mean_l1']:.4f} -> {args.output}/psnr/after_opt/final_result.json")
-        ev = slam.mapper.eval_rendering_kf()                              # demo_s.py:175-190 evaluates the renderings of the keyframes
+        ev = slam.mapper.eval_rendering_kf(lpips=lpips)                   # demo_s.py:175-190 evaluates the renderings of the keyframes
         slam.mapper.save(os.path.join(args.output, "gaussians.safetensors"))
+        lp = f", LPIPS {ev['mean_lpips']:.4f}" if lpips is not None else ""
         print(f"GS mapper: {len(slam.mapper.gaussians)} Gaussians, {len(slam.mapper.viewpoints)} keyframes, PSNR {ev['mean_psnr']:.2f} dB, "
-              f"SSIM {ev['mean_ssim']:.4f} -> {args.output}/gaussians.safetensors")
+              f"SSIM {ev['mean_ssim']:.4f}{lp} -> {args.output}/gaussians.safetensors")
     if args.mesh:
         from cut3r_slam_amd.tsdf import write_ply
         t_int = time.time()

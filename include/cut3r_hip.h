@@ -750,6 +750,33 @@ int cut3r_mesh_components_emit(const float* verts, const unsigned char* colors, 
                                int* face_map, int* comps, long long Vout, long long Fout, long long K, long long cap_v, long long cap_f,
                                long long cap_k, void* stream);
 
+/* ---- LPIPS of the rendering evaluation (csrc/lpips.hip) ---------------------------------------------------------------------------------
+ * gaussian/utils/eval_utils.py:29,83,92 and :115,141,150: LearnedPerceptualImagePatchSimilarity(net_type="alex", normalize=True).  fp32,
+ * compiled without FMA contraction; tests/lpips_oracle.py restates every step and the maps are compared bit for bit.  Activations are
+ * channels-last [n,H,W,C]; the n = 2B images of a call are the B first images followed by the B second images.  Every entry point refuses
+ * (CUT3R_ERR_ARG, before any launch) null pointers, non-positive sizes and a shape whose output would be empty. */
+/* eval_utils.py:29 normalize=True and the network's scaling layer: a, b [B,3,H,W] in [0,1] -> out [2B,H,W,3],
+ * x = ((2 v - 1) - shift_c) / scale_c, shift (-.030, -.088, -.188), scale (.458, .448, .450), every step rounded, the division exact. */
+int cut3r_lpips_input(const float* a, const float* b, int B, int H, int W, float* out, void* stream);
+/* output size of a convolution along one axis, (in + 2 pad - k) / stride + 1; 0 when the arguments are not positive or nothing fits */
+int cut3r_lpips_conv_out(int in, int k, int stride, int pad);
+/* eval_utils.py:83,141 (the AlexNet `features` convolutions with their ReLU): x [n,H,W,Ci], w [KH,KW,Ci,Co], bias [Co] -> y [n,Ho,Wo,Co].
+ * One output is acc = bias[co]; acc = fmaf(w[k,co], x[k], acc) over k = (ky KW + kx) Ci + ci ascending, a padded tap contributing
+ * fmaf(w, 0, acc); then max(acc, 0).  impl 0: an implicit GEMM on v_mfma_f32_32x32x2_f32 (needs Co % 64 == 0), whose accumulation is
+ * that chain, in 128-row tiles when those fill the chip and 64-row tiles otherwise (impl 2 / 3 force one); impl 1: the chain as fmaf on
+ * the VALU.  The bits depend neither on n nor on impl.  Also refused: pad >= KH or KW, impl outside 0..3. */
+int cut3r_lpips_conv(const float* x, const float* w, const float* bias, float* y, int n, int H, int W, int Ci, int Co, int KH, int KW,
+                     int stride, int pad, int impl, void* stream);
+/* eval_utils.py:83,141 (the two 3x3 stride-2 max-pools of AlexNet `features`, no padding, floor): x [n,H,W,C] -> y [n,(H-3)/2+1,(W-3)/2+1,C];
+ * H or W < 3 is refused. */
+int cut3r_lpips_pool(const float* x, float* y, int n, int H, int W, int C, void* stream);
+/* eval_utils.py:83,141 (one tap of the metric: unit-normalise over channels, squared difference, the 1x1 `lin` layer, spatial mean).
+ * feat [2B,P,C] (C % 4 == 0), lin [C] -> v [B,P]: per pixel ss = fmaf(f_c, f_c, ss) over ascending c; n_c = f_c / sqrt(1e-8f + ss)
+ * (norm 0, torchmetrics) or f_c / (sqrt(ss) + 1e-10f) (norm 1, the lpips package); d = n0_c - n1_c; v = fmaf(lin_c, d * d, v).  Then
+ * score[b] (fp64, device) = (accumulate ? score[b] : 0) + sum_p v[b,p] / P, the sum in fp64 in a fixed order (no atomics). */
+int cut3r_lpips_tail(const float* feat, const float* lin, int B, int P, int C, int norm, int accumulate, float* v, double* score,
+                     void* stream);
+
 /* Measurement aid of bench.py's roofline (no reference counterpart; not on the product path): a bare MFMA loop (v_mfma_f32_16x16x32_f16,
  * 16 independent accumulator chains per wave, 8 waves per workgroup, `grid` workgroups, `iters` x 16 MFMAs per wave, operands = 16-byte
  * chunks of data[nhalf] fp16, nhalf a power of two >= 32768) with s_memtime / s_memrealtime stamps around the loop.  stamps [grid,2] u64 =
