@@ -204,6 +204,9 @@ SIGNATURES = {
     "cut3r_lpips_conv": [c_void_p] * 4 + [c_int] * 10 + [c_void_p],
     "cut3r_lpips_pool": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
     "cut3r_lpips_tail": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "cut3r_focal_workspace_bytes": [c_int, c_int, c_int],
+    "cut3r_focal_weiszfeld": [c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_ll, c_void_p],
+    "cut3r_focal_median": [c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_ll, c_void_p],
 }
 RESTYPES = {"cut3r_ba_workspace_floats": c_ll, "cut3r_gs_workspace_bytes": c_ll, "cut3r_schur_mono_prior_workspace_floats": c_ll,
             "cut3r_knn3_grid_workspace_bytes": c_ll, "cut3r_tsdf_mesh_workspace_bytes": c_ll, "cut3r_tsdf_sparse_assign_workspace_bytes": c_ll,
@@ -211,7 +214,7 @@ RESTYPES = {"cut3r_ba_workspace_floats": c_ll, "cut3r_gs_workspace_bytes": c_ll,
             "cut3r_nn_workspace_bytes": c_ll, "cut3r_icp_moments_workspace_bytes": c_ll, "cut3r_mesh_raster_workspace_bytes": c_ll,
             "cut3r_depth_l1_workspace_bytes": c_ll, "cut3r_depth_cloud_workspace_bytes": c_ll, "cut3r_cloud_bounds_workspace_bytes": c_ll,
             "cut3r_voxel_downsample_workspace_bytes": c_ll, "cut3r_exposure_partial_rows": c_ll, "cut3r_gs_pose_partial_rows": c_ll,
-            "cut3r_mesh_cluster_workspace_bytes": c_ll, "cut3r_mesh_components_workspace_bytes": c_ll}
+            "cut3r_mesh_cluster_workspace_bytes": c_ll, "cut3r_mesh_components_workspace_bytes": c_ll, "cut3r_focal_workspace_bytes": c_ll}
 
 _lib = None
 

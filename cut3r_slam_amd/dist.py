@@ -382,6 +382,8 @@ class ShardedTracker:
     def step(self, frames, t, kf_every, win, intr):
         """Advance world*wb windows (= world*wb*win*kf_every frames).  Returns the new frame counter."""
         slam, world, rank, wb = self.slam, self.world, self.rank, self.wb
+        if not getattr(slam.keyframes, "calibrated", True):
+            raise RuntimeError("ShardedTracker needs a calibrated keyframe store: multi-GPU self-calibration is not supported, pass intrinsics")
         if self._next_t0 is None:
             self._next_t0 = slam.tracker.t1 - 1
             self._f0 = self._next_t0          # first keyframe of the first window this driver schedules

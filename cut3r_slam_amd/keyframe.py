@@ -47,6 +47,7 @@ class KeyFrame:
         self.tstamp = torch.zeros(buffer, dtype=torch.float)                              # host (a device scalar write would block on the stream)
         self.image = torch.zeros(buffer, 3, ht, wd, device=dev, dtype=torch.uint8)
         self.intrinsic = torch.zeros(buffer, 4, dtype=torch.float)                       # host
+        self.calibrated = False          # true from the first append with intrinsics, or from set_intrinsics (a run without a calibration)
         self.pose = torch.zeros(buffer, 7, dtype=torch.float)                            # host, c2w (t, q_xyzw)
         self.pose[:] = torch.as_tensor([0, 0, 0, 0, 0, 0, 1], dtype=torch.float)
         self.w2c = torch.zeros(buffer, 12, device=dev, dtype=torch.float)                # device mirror of inverse(pose)
@@ -136,6 +137,13 @@ class KeyFrame:
             self.pose[int(k)] = torch.from_numpy(p[j])
             self.w2c[int(k)].copy_(torch.from_numpy(rows[j]))
 
+    def set_intrinsics(self, K) -> None:
+        """the calibration of a store that was filled without one (self_calib.SelfCalibration): (fx, fy, cx, cy) into the rows of every
+        keyframe stored so far; later appends without intrinsics copy row 0 as they always did"""
+        k4 = torch.as_tensor(K, dtype=torch.float).reshape(-1)[:4]
+        self.intrinsic[:max(self._counter, 1)] = k4
+        self.calibrated = True
+
     def pointmap_slot(self, kf: int, sub_num: int, t0: int):
         """(submap, slot) holding the current estimate of keyframe `kf` as seen from window `sub_num` starting at t0
         (track_frontend.py:251-255: earlier submaps contribute slots 0..4, the running window its own slots)."""
@@ -158,6 +166,7 @@ class KeyFrame:
             self.depth[i].copy_(torch.as_tensor(depth).to(self.device))
         if intrinsics is not None:
             self.intrinsic[i] = torch.as_tensor(intrinsics, dtype=torch.float).reshape(-1)[:4]
+            self.calibrated = True
         else:
             self.intrinsic[i] = self.intrinsic[0].clone()
         if feat is not None:

@@ -1485,3 +1485,56 @@ def lpips_tail(feat, lin, score, accumulate, norm="torchmetrics"):
     check(_lib.load().cut3r_lpips_tail(_p(feat), _p(lin), n // 2, H * W, Cc, LPIPS_NORMS[norm], int(bool(accumulate)), _p(v), _p(score),
                                        _stream()), "cut3r_lpips_tail")
     return v
+
+
+# ------------------------------------------------------------------------------------------------ focal length from self-view pointmaps
+def _focal_args(pts, pp, conf, conf_min):
+    _cuda(pts, pp, conf)
+    _req(pts.dim() == 4 and pts.shape[3] == 3 and pts.dtype == F32 and pts.is_contiguous(), "pts: contiguous fp32 [B,H,W,3]")
+    B, H, W, _ = pts.shape
+    _req(B >= 1 and H * W >= 1 and 2 * H * W < 2 ** 31, "pts: B >= 1 and 1 <= H W < 2^30")
+    _req(pp.shape == (B, 2) and pp.dtype == F32 and pp.is_contiguous() and pp.device == pts.device, "pp: contiguous fp32 [B,2] on the device of pts")
+    _req((conf is None) == (conf_min is None), "conf and conf_min go together")
+    if conf is not None:
+        _req(conf.shape == (B, H, W) and conf.dtype == F32 and conf.is_contiguous() and conf.device == pts.device,
+             "conf: contiguous fp32 [B,H,W] on the device of pts")
+    return B, H, W, float(conf_min) if conf_min is not None else 0.0
+
+
+def focal_workspace(B, H, W, device):
+    lib = _lib.load()
+    nbytes = lib.cut3r_focal_workspace_bytes(B, H, W)
+    _req(nbytes > 0, "focal workspace")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _focal_ws(B, H, W, device, workspace):
+    if workspace is None:
+        return focal_workspace(B, H, W, device)
+    _cuda(workspace)
+    _req(workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == device, "workspace: contiguous uint8 on the device of pts")
+    _req(workspace.numel() >= _lib.load().cut3r_focal_workspace_bytes(B, H, W), "workspace shorter than cut3r_focal_workspace_bytes(B, H, W)")
+    return workspace
+
+
+def focal_weiszfeld(pts, pp, iters=10, conf=None, conf_min=None, workspace=None):
+    """post_process.py:38-55 without the final clip -> focal fp32 [B] on the device (csrc/calib.hip states the arithmetic and the order of
+    the sums; tests/focal_oracle.py restates them).  pts fp32 [B,H,W,3], pp fp32 [B,2]; a pixel with conf < conf_min takes no part."""
+    B, H, W, cmin = _focal_args(pts, pp, conf, conf_min)
+    _req(int(iters) >= 0, "iters >= 0")
+    ws = _focal_ws(B, H, W, pts.device, workspace)
+    focal = torch.empty(B, dtype=F32, device=pts.device)
+    check(_lib.load().cut3r_focal_weiszfeld(_p(pts), _p(conf), cmin, _p(pp), B, H, W, int(iters), _p(focal), _p(ws), ws.numel(), _stream()),
+          "cut3r_focal_weiszfeld")
+    return focal
+
+
+def focal_median(pts, pp, conf=None, conf_min=None, workspace=None):
+    """post_process.py:27-36 without the final clip -> focal fp32 [B] on the device: torch.nanmedian of the 2 H W votes (u z) / x, (v z) / y
+    of every view by a radix select (csrc/calib.hip)."""
+    B, H, W, cmin = _focal_args(pts, pp, conf, conf_min)
+    ws = _focal_ws(B, H, W, pts.device, workspace)
+    focal = torch.empty(B, dtype=F32, device=pts.device)
+    check(_lib.load().cut3r_focal_median(_p(pts), _p(conf), cmin, _p(pp), B, H, W, _p(focal), _p(ws), ws.numel(), _stream()),
+          "cut3r_focal_median")
+    return focal

@@ -52,12 +52,24 @@ class Cut3rSlam:
         self.tracked_only = False
         # hi2.py:47-48: the Gaussian mapper (cut3r_slam_amd.gs_mapper.GSMapper); None = tracking only (BASELINE configs 1-4)
         self.mapper = None
+        # a run without a calibration (run(..., intrinsics=None, intrinsics_ds=None)): the tracker estimates the focal from its first
+        # window (self_calib.SelfCalibration, config section Tracking.calibration).  GSMapper needs the intrinsics at construction, so a
+        # caller that wants the mapper sets `mapper_factory`, a callable (fx, fy, cx, cy) -> mapper: it is invoked once, right after the
+        # calibration, if `mapper` is still None.  `calibration`: None, or {"intrinsics": (fx, fy, cx, cy), "per_view": [V] estimates}
+        self.mapper_factory = None
+        self.calibration = None
+        self.tracker.on_calibrated = self._on_calibrated
         self.traj_full = None                  # terminate(fill=True): (tstamps [n], poses [n,7] c2w) of every frame from the first keyframe on
         self.gs_iter_num = self.config.get("Mapping", {}).get("itr_num", 100)
         # hi2.py:84 reads `self.keyframes.depth[updated_idx][mask] = depth[mask]` with a LIST index: an advanced-index copy, so the
         # reference never changes keyframes.depth and later windows chain on the tracker's own depths.  Default = that effective
         # behaviour; True writes the mapper's scale-corrected depths back (what the line looks like it wants) -- a declared deviation
         self.gs_depth_writeback = False
+
+    def _on_calibrated(self, fx, fy, cx, cy):
+        self.calibration = {"intrinsics": (fx, fy, cx, cy), "per_view": self.tracker.calibration.per_view.copy()}
+        if self.mapper is None and self.mapper_factory is not None:
+            self.mapper = self.mapper_factory(fx, fy, cx, cy)
 
     def call_gs(self, viz_idx, submap_idx, iterations, intrinsics):
         """hi2.py:56-91: hand the window's keyframes to the mapper and take back its refined poses and pointmaps (the chain of later
@@ -67,6 +79,8 @@ class Cut3rSlam:
         kf = self.keyframes
         viz = list(viz_idx)
         n = len(viz)
+        if intrinsics is None:                     # a self-calibrated run: the store's calibration
+            intrinsics = kf.intrinsic[0]
         data = {"viz_idx": viz, "submap_idx": submap_idx, "tstamp": kf.tstamp[viz], "poses": kf.pose[viz], "images": kf.image[viz],
                 "pointmaps": kf.submap_ds[submap_idx][:n], "confs": kf.conf_ds[submap_idx][:n], "depths": kf.depth[viz],
                 "intrinsics": torch.as_tensor(intrinsics).reshape(-1)[:4]}
@@ -85,7 +99,8 @@ class Cut3rSlam:
 
     @torch.no_grad()
     def run(self, tstamp, image, intrinsics, image_ds, intrinsics_ds, second_last_frame=False, last_frame=False):
-        """hi2.py:101-133 (the GS mapper takes part when `self.mapper` is set): image_ds [1,3,H,W] uint8 at tracking resolution."""
+        """hi2.py:101-133 (the GS mapper takes part when `self.mapper` is set): image_ds [1,3,H,W] uint8 at tracking resolution.
+        intrinsics = intrinsics_ds = None: no calibration; the first window estimates it (see __init__)."""
         if self.keep_images:
             self.images[int(tstamp)] = image
         self.filterx.kfFilter(tstamp, image_ds, intrinsics=intrinsics_ds, second_last_frame=second_last_frame,

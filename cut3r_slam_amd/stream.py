@@ -74,9 +74,15 @@ def _decode(path: str) -> np.ndarray:
         return np.asarray(im.convert("RGB"), dtype=np.uint8)
 
 
-def mono_stream(imagedir, calib, undistort=False, cropborder=0, start=0, length=100000, device="cuda:0"):
+def mono_stream(imagedir, calib=None, undistort=False, cropborder=0, start=0, length=100000, device="cuda:0"):
     """yields (t, image [1,3,h2,w2] u8, intrinsics [1,4], image_ds [1,3,h1,w1] u8, intrinsics_ds [1,4], is_last);
-    the two images are device tensors, the intrinsics float64 host tensors as in the reference."""
+    the two images are device tensors, the intrinsics float64 host tensors as in the reference.  calib=None (no calibration: the tracker
+    estimates it, self_calib.py): both intrinsics are None; undistortion then has nothing to work with and is refused."""
+    if calib is None:
+        if undistort:
+            raise ValueError("undistort=True needs a calibration with distortion coefficients")
+        yield from _uncalibrated_stream(imagedir, cropborder, start, length, device)
+        return
     calib = load_calib(calib) if isinstance(calib, (str, os.PathLike)) else np.asarray(calib, np.float64)
     umap = None            # (ix, iy) device maps of cv2.undistort, built on the first frame (they depend on the frame size only)
     image_list = natsorted(os.listdir(imagedir))[start:start + length]
@@ -116,6 +122,44 @@ def mono_stream(imagedir, calib, undistort=False, cropborder=0, start=0, length=
         intrinsics[2] *= (w2 / w0)
         intrinsics[3] *= (h2 / h0)
         yield (t, image_map[None], intrinsics[None], image_ds[None], intrinsics_ds[None], t == len(image_list) - 1)
+
+
+def _uncalibrated_stream(imagedir, cropborder, start, length, device):
+    """mono_stream without a calibration: the same files, crop and two resizes, None for both intrinsics"""
+    image_list = natsorted(os.listdir(imagedir))[start:start + length]
+    for t, imfile in enumerate(image_list):
+        image = _decode(os.path.join(imagedir, imfile))
+        if cropborder > 0:
+            image = image[cropborder:-cropborder, cropborder:-cropborder]
+        h0, w0, _ = image.shape
+        src = torch.from_numpy(np.array(image, dtype=np.uint8, order="C")).to(device, non_blocking=True)
+        image_ds = ops.resize_linear_u8(src, *tracking_size(h0, w0), chw_out=True)
+        image_map = ops.resize_linear_u8(src, *mapping_size(h0, w0), chw_out=True)
+        yield (t, image_map[None], None, image_ds[None], None, t == len(image_list) - 1)
+
+
+def input_size(imagedir, start=0):
+    """(h, w) of the first frame mono_stream would yield, before any crop or resize (the header only: nothing is decoded)"""
+    from PIL import Image
+    with Image.open(os.path.join(imagedir, natsorted(os.listdir(imagedir))[start])) as im:
+        return im.size[1], im.size[0]
+
+
+def rescale_intrinsics(K4, size_from, size_to) -> np.ndarray:
+    """(fx, fy, cx, cy) of an image of size_from = (h, w) for the same image resized to size_to, by mono_stream's own arithmetic"""
+    (h_a, w_a), (h_b, w_b) = size_from, size_to
+    K = np.asarray(K4, np.float64).reshape(-1)[:4].copy()
+    K[0] *= w_b / w_a
+    K[1] *= h_b / h_a
+    K[2] *= w_b / w_a
+    K[3] *= h_b / h_a
+    return K
+
+
+def save_calib(path: str, K4) -> None:
+    """`fx fy cx cy` on one line, the format load_calib reads; 17 digits, so that a run handed the file computes the tracking-resolution
+    intrinsics the estimating run used, to the bit"""
+    np.savetxt(path, np.asarray(K4, np.float64).reshape(1, -1)[:, :4], fmt="%.17g", delimiter=" ")
 
 
 def frame_timestamps(imagedir, start=0) -> np.ndarray:

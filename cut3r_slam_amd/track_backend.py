@@ -219,6 +219,8 @@ class TrackBackend:
     # ------------------------------------------------------------------ entry point (track_backend.py:527-586)
     def run(self, t1=None):
         kf = self.keyframes
+        if not getattr(kf, "calibrated", True):
+            raise RuntimeError("loop closure needs a calibrated keyframe store: no intrinsics were passed and no window has self-calibrated yet")
         intr = kf.intrinsic[0].numpy() / self.downsample_ratio
         K4 = [float(intr[0]), float(intr[1]), float(intr[2]), float(intr[3])]
         t1 = kf.counter.value - 1 if t1 is None else int(t1)

@@ -17,6 +17,7 @@ import torch
 from . import geom_host as gh
 from . import ops
 from .factor_graph import AlignedPoints, SubmapStore
+from .self_calib import SelfCalibration
 
 
 def _check_scale(t0, s, stats=None):
@@ -103,6 +104,9 @@ class TrackFrontend:
         self._pose_host = torch.zeros(8, 7, dtype=torch.float32).pin_memory()
         self._ev = None
         self.scale_stats = new_scale_stats()     # chained-scale book-keeping of every steady-state window (see _check_scale)
+        # a run without a calibration: the policy that turns the first window's pointmaps into the run's intrinsics (never used otherwise)
+        self.calibration = SelfCalibration(getattr(slam, "config", None))
+        self.on_calibrated = None                # callable (fx, fy, cx, cy) -> None, invoked once after a self-calibration
 
     def prepare_input(self, images):
         return make_views(self.model, images)
@@ -281,6 +285,14 @@ class TrackFrontend:
             if self._counts is None or self._counts.shape[-1] < t1 - b0:
                 self._counts = torch.zeros(6, 2, max(256, 2 * (t1 - b0)), dtype=torch.int32, device=self.device)
                 self._counts_host = torch.zeros(6, 2, self._counts.shape[-1], dtype=torch.int32).pin_memory()
+            if not kf.calibrated:
+                # no calibration was handed in: the focal from this window's own pointmaps (one read-back of V floats, once per run), written
+                # into the rows of EVERY stored keyframe -- with look-ahead or window batching many are registered already.  It stays
+                # fixed for the rest of the run
+                K = self.calibration.from_window(pts, conf)
+                kf.set_intrinsics(K)
+                if self.on_calibrated is not None:
+                    self.on_calibrated(*K)
             intr = kf.intrinsic[t0:t1].numpy()
             # one call per run of keyframes with equal intrinsics (a sequence has ONE calibration: normally one call)
             groups, g0 = [], 0
@@ -385,6 +397,8 @@ class TrackFrontend:
         window_scalars; chain: scan state (updated in place).  gather_store(sub0, n, phase) completes the stride-2 stores (phase 0) /
         the depth rows (phase 1) of submaps sub0..sub0+n-1 on every rank; exchange_counts sums the owners' int32 counts."""
         kf, graph, ds = self.keyframes, self.graph, self.downsample_ratio
+        if not getattr(kf, "calibrated", True):
+            raise RuntimeError("sharded tracking needs a calibrated keyframe store: self-calibration runs on one GPU only, pass intrinsics")
         H, W = kf.ht, kf.wd
         h, w = kf.submap_ds.shape[2:4]
         n = len(ranges)

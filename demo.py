@@ -4,6 +4,9 @@
     python demo.py --imagedir data/Replica/room0/colors --calib calib/replica.txt --config config/replica_config.yaml \\
                    --output outputs/room0 [--kf_every 10] [--ckpt_path checkpoints/cut3r_512_dpt_4_64.pth]
 
+--calib is optional: without it the focal length comes from the first tracking window's own pointmaps (--calib-mode, the principal point at
+the image centre) and <output>/calib_estimated.txt holds it for the input frames, in the format --calib and --gt-calib read.
+
 Writes <output>/traj_kf.txt and <output>/intrinsics.npy exactly as the reference does (evo-compatible TUM rows); with --mesh also
 <output>/tsdf_mesh_w{W:.1f}.ply per --mesh-weight, the reference's post-run mesh (TSDF fusion on the GPU, cut3r_slam_amd/tsdf.py), and with
 --mesh-simplify CELL and / or --mesh-min-faces N next to each of them tsdf_mesh_w{W:.1f}_clean.ply, that mesh after vertex clustering and
@@ -51,7 +54,10 @@ def main(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--imagedir", type=str, required=True, help="path to image directory")
     p.add_argument("--posedir", type=str, default=None)
-    p.add_argument("--calib", type=str, required=True, help="path to calibration file")
+    p.add_argument("--calib", type=str, default=None, help="path to calibration file; without it the run estimates the focal length from "
+                   "the first tracking window's pointmaps (cut3r_slam_amd/self_calib.py) and writes <output>/calib_estimated.txt")
+    p.add_argument("--calib-mode", choices=("weiszfeld", "median"), default=None, help="estimator of a run without --calib "
+                   "(Tracking.calibration.mode; default weiszfeld)")
     p.add_argument("--config", type=str, default=None, help="path to configuration file")
     p.add_argument("--output", default="outputs/demo", help="path to save output")
     p.add_argument("--gtdepthdir", type=str, default=None, help="ground-truth 16-bit depth PNGs (read by --eval-dense only)")
@@ -124,6 +130,12 @@ def main(argv=None):
     args.gs = args.gs or args.fill
     if args.lpips_weights and not args.gs:
         p.error("--lpips-weights needs --gs (LPIPS scores the renderings of the Gaussian map)")
+    if args.undistort and not args.calib:
+        p.error("--undistort needs --calib (the distortion coefficients)")
+    if args.calib_mode and args.calib:
+        p.error("--calib-mode belongs to a run without --calib")
+    if args.eval_dense and not (args.calib or args.gt_calib):
+        p.error("--eval-dense needs the calibration of the GT depth maps: --calib or --gt-calib")
     if args.eval_dense and not (args.gtdepthdir and args.gt_traj):
         p.error("--eval-dense needs --gtdepthdir and --gt-traj")
     if args.gt_depth_scale <= 0 or args.dense_depth_trunc <= 0:
@@ -165,6 +177,8 @@ def main(argv=None):
     trk["frontend"]["window_batch"] = args.window_batch
     if args.loop_sim3:
         trk["frontend"]["loop_group"] = "sim3"
+    if args.calib_mode:
+        trk.setdefault("calibration", {})["mode"] = args.calib_mode
 
     if args.synthetic_weights:
         mcfg = tiny_config("dpt") if args.small else production_config()
@@ -189,20 +203,22 @@ def main(argv=None):
             from cut3r_slam_amd.gs_mapper import GSMapper
             if "Training" not in cfg or "opt_params" not in cfg:
                 raise SystemExit("--gs needs the Training and opt_params sections in --config")
-            k = [float(v) for v in intr_ds[0].reshape(-1)[:4]]
-            s_.mapper = GSMapper(cfg, k[0], k[1], k[2], k[3], downsample_ratio=s_.downsample_ratio, device=args.device)
+            s_.mapper_factory = lambda fx, fy, cx, cy: GSMapper(cfg, fx, fy, cx, cy, downsample_ratio=s_.downsample_ratio, device=args.device)
+            if intr_ds is not None:
+                s_.mapper = s_.mapper_factory(*[float(v) for v in intr_ds[0].reshape(-1)[:4]])
         return s_
 
     def items():
         # demo_s.py:158-159: a --length cut does NOT flush the tail window (the flags look at the directory, not at the cut)
         for t, image, intr, image_ds, intr_ds, is_last in frames:
-            yield (t, image, intr[0].float(), image_ds, intr_ds[0].float(), t + args.start == n_files - 2, t + args.start == n_files - 1)
+            yield (t, image, intr[0].float() if intr is not None else None, image_ds, intr_ds[0].float() if intr_ds is not None else None,
+                   t + args.start == n_files - 2, t + args.start == n_files - 1)
 
     if args.lookahead > 1:
         it = items()
         first = next(it, None)
         if first is not None:
-            slam = make_slam(first[3], first[4][None])
+            slam = make_slam(first[3], first[4][None] if first[4] is not None else None)
             counted = []
 
             def chain():
@@ -213,12 +229,24 @@ def main(argv=None):
     else:
         for item in items():
             if slam is None:
-                slam = make_slam(item[3], item[4][None])
+                slam = make_slam(item[3], item[4][None] if item[4] is not None else None)
             slam.run(item[0], item[1], item[2], item[3], item[4], second_last_frame=item[5], last_frame=item[6])
             nframes += 1
     if slam is None:
         raise SystemExit(f"{args.imagedir}: no frames")
     torch.cuda.synchronize()
+    if not args.calib:
+        if slam.calibration is None:
+            raise SystemExit("no calibration was passed and the run ended before its first tracking window could estimate one")
+        # the estimate holds at the tracking resolution; the file speaks of the input frames (crop undone), as a --calib file does
+        kf = slam.keyframes
+        h_in, w_in = stream.input_size(args.imagedir, args.start)
+        K_in = stream.rescale_intrinsics(slam.calibration["intrinsics"], (kf.ht, kf.wd), (h_in - 2 * args.cropborder, w_in - 2 * args.cropborder))
+        K_in[2:] += args.cropborder
+        stream.save_calib(os.path.join(args.output, "calib_estimated.txt"), K_in)
+        print(f"self-calibration ({slam.tracker.calibration.mode}): focal {slam.calibration['intrinsics'][0]:.3f} px at {kf.wd}x{kf.ht} (per view "
+              f"{[round(float(v), 3) for v in slam.calibration['per_view']]}); fx fy cx cy of the input frames = "
+              f"{' '.join(f'{v:.4f}' for v in K_in)} -> {args.output}/calib_estimated.txt")
     traj = stream.save_trajectory(slam, args.imagedir, args.output, start=args.start)
     if slam.mapper is not None and slam.mapper.viewpoints:
         fill = args.fill and getattr(slam.mapper, "initialized", False)

@@ -777,6 +777,26 @@ int cut3r_lpips_pool(const float* x, float* y, int n, int H, int W, int C, void*
 int cut3r_lpips_tail(const float* feat, const float* lin, int B, int P, int C, int norm, int accumulate, float* v, double* score,
                      void* stream);
 
+/* ---- Focal length from the self-view pointmaps (csrc/calib.hip) ---------------------------------------------------------------------------
+ * src/dust3r/post_process.py:12-64 estimate_focal_knowing_depth, both modes, without its final clip (one elementwise op of the caller).
+ * pts fp32 [B,H,W,3] contiguous, pp fp32 [B,2], conf fp32 [B,H,W] or NULL (a pixel with conf < conf_min takes no part), focal fp32 [B] on
+ * the device; pixel (row, col) has u = float(col) - ppx, v = float(row) - ppy.  fp32 per pixel, compiled without FMA contraction;
+ * tests/focal_oracle.py restates both.  No floating-point atomics, no barrier across workgroups, no host synchronisation.  Refused
+ * (CUT3R_ERR_ARG, before any launch): null pts / pp / focal / workspace, B < 1, H W < 1, 2 H W >= 2^31, a short or misaligned workspace. */
+long long cut3r_focal_workspace_bytes(int B, int H, int W);                   /* -1 on bad sizes */
+/* :38-55.  xz = x / z, yz = y / z (0 when not finite); a = xz u + yz v; b = xz xz + yz yz; f = float(double(sum a) / double(sum b)); then
+ * `iters` times (the reference: 10) w = 1 / fmaxf(sqrtf(du du + dv dv), 1e-8f) with du = u - f xz, dv = v - f yz, and
+ * f = float(double(sum fl32(w a)) / double(sum fl32(w b))).  fp64 sums in a fixed order: 16 workgroups per view over contiguous ranges of
+ * ceil(HW / 16) pixels, 256 strided thread sums, a halving tree, the 16 partial pairs in ascending order (the file header).  iters + 2
+ * launches; every workgroup re-adds the previous launch's partial pairs.  NaN for a view without a participating pixel or with sum b == 0. */
+int cut3r_focal_weiszfeld(const float* pts, const float* conf, float conf_min, const float* pp, int B, int H, int W, int iters, float* focal,
+                          void* workspace, long long workspace_bytes, void* stream);
+/* :27-36.  The vote of rank (n - 1) / 2 (ascending) among the n non-NaN votes (u z) / x and (v z) / y of the participating pixels, which is
+ * torch.nanmedian; +-inf votes take part; NaN when n == 0.  Radix select in four 8-bit passes over the order-preserving uint32 image of the
+ * float: LDS histograms, integer atomicAdd into the view's 256-bin table of the pass, the next pass reads the chosen bin from it. */
+int cut3r_focal_median(const float* pts, const float* conf, float conf_min, const float* pp, int B, int H, int W, float* focal,
+                       void* workspace, long long workspace_bytes, void* stream);
+
 /* Measurement aid of bench.py's roofline (no reference counterpart; not on the product path): a bare MFMA loop (v_mfma_f32_16x16x32_f16,
  * 16 independent accumulator chains per wave, 8 waves per workgroup, `grid` workgroups, `iters` x 16 MFMAs per wave, operands = 16-byte
  * chunks of data[nhalf] fp16, nhalf a power of two >= 32768) with s_memtime / s_memrealtime stamps around the loop.  stamps [grid,2] u64 =
