@@ -160,9 +160,25 @@ def dense_metrics(est, gt, *, depth_trunc=4.5, est_depth_trunc=None, size=None, 
 
 
 # ------------------------------------------------------------------------------------------------------------------------ sources
-def from_keyframes(keyframes, n, stamps=None) -> DepthViews:
+def filter_views(views, consistency, return_keep=False):
+    """the DepthViews with its depth maps cross-checked between neighbouring views (depth_consistency.ConsistencyOptions) and the rejected
+    pixels zeroed, which the clouds skip; every finite positive depth takes part, whatever the evaluation truncates later.  This is for
+    the RUN's depths: ground truth is never filtered."""
+    from . import depth_consistency
+    depth, poses, K, _, _ = _views(views, "views")
+    n = depth.shape[0]
+    K = np.broadcast_to(np.asarray(K.detach().cpu() if isinstance(K, torch.Tensor) else K, np.float64).reshape(-1, 4), (n, 4)).copy()
+    out, keep = depth_consistency.apply(depth.to(_device(), torch.float32), np.linalg.inv(poses)[:, :3], K, consistency, float("inf"))
+    v = DepthViews(*views)._replace(depth=out)
+    return (v, keep) if return_keep else v
+
+
+def from_keyframes(keyframes, n, stamps=None, consistency=None) -> DepthViews:
     """the tracker's keyframes 0..n-1 (the same ones as the trajectory): depth, pose (c2w [t, q xyzw]), intrinsic, tstamp, image.  stamps:
-    replaces the store's frame indices (demo.py passes the file stamps that traj_kf.txt carries)."""
+    replaces the store's frame indices (demo.py passes the file stamps that traj_kf.txt carries).  consistency: filter_views' options
+    (None: the depth maps as they are)."""
+    if consistency is not None:
+        return filter_views(from_keyframes(keyframes, n, stamps), consistency)
     n = int(n)
     if n <= 0:
         raise ValueError("no tracked keyframes")
@@ -182,10 +198,13 @@ def _mapper_frame_indices(mapper):
 
 
 @torch.no_grad()
-def from_mapper(mapper, stamps=None) -> DepthViews:
+def from_mapper(mapper, stamps=None, consistency=None) -> DepthViews:
     """every mapper keyframe rendered from the Gaussian map at its refined pose (tsdf.render_mapper_views: the depth quantised as the
-    reference's renders_kf/depth_after_opt PNGs).  stamps: one per keyframe in key order; default the keyframes' frame indices."""
+    reference's renders_kf/depth_after_opt PNGs).  stamps: one per keyframe in key order; default the keyframes' frame indices.
+    consistency: filter_views' options (None: the depth maps as they are)."""
     from .tsdf import render_mapper_views
+    if consistency is not None:
+        return filter_views(from_mapper(mapper, stamps), consistency)
     if not mapper.viewpoints:
         raise ValueError("the mapper has no keyframes")
     if stamps is None:
@@ -196,9 +215,12 @@ def from_mapper(mapper, stamps=None) -> DepthViews:
     return DepthViews(depth, np.linalg.inv(w), K.double().cpu().numpy(), np.asarray(stamps, np.float64), rgb)
 
 
-def from_slam(slam, source="auto", stamps_full=None) -> DepthViews:
+def from_slam(slam, source="auto", stamps_full=None, consistency=None) -> DepthViews:
     """the rule of Cut3rSlam.fuse / --mesh-source: "mapper", "tracker", or "auto" = the mapper when one with keyframes is attached.
-    stamps_full: the per-frame stamps (stream.frame_timestamps) that map the store's frame indices to the stamps of traj_kf.txt."""
+    stamps_full: the per-frame stamps (stream.frame_timestamps) that map the store's frame indices to the stamps of traj_kf.txt.
+    consistency: filter_views' options (None: the depth maps as they are)."""
+    if consistency is not None:
+        return filter_views(from_slam(slam, source, stamps_full), consistency)
     if source not in ("auto", "tracker", "mapper"):
         raise ValueError(f"source must be auto, tracker or mapper, not {source!r}")
     full = None if stamps_full is None else np.asarray(stamps_full, np.float64).reshape(-1)

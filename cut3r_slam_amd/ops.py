@@ -1538,3 +1538,51 @@ def focal_median(pts, pp, conf=None, conf_min=None, workspace=None):
     check(_lib.load().cut3r_focal_median(_p(pts), _p(conf), cmin, _p(pp), B, H, W, _p(focal), _p(ws), ws.numel(), _stream()),
           "cut3r_focal_median")
     return focal
+
+
+# ------------------------------------------------------------------------------------------------ multi-view depth consistency
+CONSISTENCY_MAX_SOURCES = 16
+CONSISTENCY_MAX_REFS = 65535
+
+
+def depth_consistency(depth, K, ref, src, fwd, bwd, depth_max, pix=1.0, rel=0.01, z_min=1e-3, average=False):
+    """cross-check R views of a depth stack against up to 16 source views each (csrc/consistency.hip; include/cut3r_hip.h states the rule,
+    tests/consistency_oracle.py restates it) -> (support u8 [R,H,W], violation u8 [R,H,W], depth_avg fp32 [R,H,W] or None).  depth fp32
+    [N,H,W] and K fp32 [N,4] on the GPU; ref [R] and src [R,S] HOST integer tables (src -1: no source), checked here against [0, N) since
+    the kernel cannot refuse what lies in device memory; fwd, bwd HOST fp64 [R,S,12], the rigid rows reference -> source and back
+    (depth_consistency.relative_rows)."""
+    import numpy as np
+    _cuda(depth, K)
+    _req(depth.dim() == 3 and depth.dtype == F32 and depth.is_contiguous(), "depth: contiguous fp32 [N,H,W]")
+    N, H, W = depth.shape
+    _req(N >= 1 and H > 0 and W > 0, "depth: empty")
+    _req(H * W < 2 ** 31 // 16, "depth_consistency: image too large")
+    _req(K.shape == (N, 4) and K.dtype == F32 and K.is_contiguous() and K.device == depth.device, "K: contiguous fp32 [N,4] on the device of depth")
+    ref = np.asarray(ref)
+    src = np.asarray(src)
+    _req(ref.ndim == 1 and src.ndim == 2 and src.shape[0] == ref.shape[0] and ref.dtype.kind in "iu" and src.dtype.kind in "iu",
+         "ref: integers [R], src: integers [R,S]")
+    R, S = src.shape
+    _req(1 <= R <= CONSISTENCY_MAX_REFS, f"ref: 1 .. {CONSISTENCY_MAX_REFS} views a launch")
+    _req(1 <= S <= CONSISTENCY_MAX_SOURCES, f"src: 1 .. {CONSISTENCY_MAX_SOURCES} sources a view")
+    _req(bool(((ref >= 0) & (ref < N)).all()), "ref: index outside the depth stack")
+    _req(bool(((src >= -1) & (src < N)).all()), "src: index outside the depth stack (-1: no source)")
+    _req(not bool((src == ref[:, None]).any()), "src: a view cannot be its own source")
+    fwd = np.ascontiguousarray(fwd, np.float64)
+    bwd = np.ascontiguousarray(bwd, np.float64)
+    _req(fwd.shape == (R, S, 12) and bwd.shape == (R, S, 12), "fwd, bwd: fp64 [R,S,12]")
+    used = src >= 0
+    _req(bool(np.isfinite(fwd[used]).all()) and bool(np.isfinite(bwd[used]).all()), "fwd / bwd: non-finite rows")
+    depth_max, pix, rel, z_min = float(depth_max), float(pix), float(rel), float(z_min)
+    _req(depth_max > 0 and pix > 0 and 0 < rel < 1 and z_min >= 0, "depth_max, pix > 0, 0 < rel < 1, z_min >= 0")
+    dev = depth.device
+    ref_d = torch.from_numpy(np.ascontiguousarray(ref, np.int32)).to(dev)
+    src_d = torch.from_numpy(np.ascontiguousarray(src, np.int32)).to(dev)
+    fwd_d = torch.from_numpy(np.where(used[..., None], fwd, 0.0)).to(dev)
+    bwd_d = torch.from_numpy(np.where(used[..., None], bwd, 0.0)).to(dev)
+    support = torch.empty(R, H, W, dtype=torch.uint8, device=dev)
+    violation = torch.empty(R, H, W, dtype=torch.uint8, device=dev)
+    avg = torch.empty(R, H, W, dtype=F32, device=dev) if average else None
+    check(_lib.load().cut3r_depth_consistency(_p(depth), _p(K), N, H, W, _p(ref_d), _p(src_d), R, S, _p(fwd_d), _p(bwd_d), depth_max, pix, rel,
+                                              z_min, _p(support), _p(violation), _p(avg), _stream()), "cut3r_depth_consistency")
+    return support, violation, avg

@@ -296,12 +296,14 @@ class Cut3rSlam:
         return self.keyframes.tstamp[:t].numpy().copy(), self.keyframes.pose[:t].numpy().copy()
 
     def fuse(self, voxel_size, depth_max=5.0, trunc_voxels=8.0, source="auto", conf_min=None, bounds=None, max_voxels=2 ** 30,
-             sparse=False):
+             sparse=False, consistency=None):
         """TSDF fusion of the run (tsdf.TSDFVolume; sparse=True: tsdf.SparseTSDFVolume, bricks near surfaces only, the same mesh as a set
         of triangles).  source "mapper": the Gaussian map rendered at every mapper keyframe (as hi2 +
         tsdf_integrate.py do); "tracker": the tracked keyframes' depths and images -- the same keyframes as trajectory(); "auto": the
-        mapper when one with keyframes is attached, else the tracker."""
+        mapper when one with keyframes is attached, else the tracker.  consistency: a depth_consistency.ConsistencyOptions, the multi-view
+        filter of the depth maps ahead of the fusion (None: the maps as they are)."""
         from . import tsdf
+        extra = {} if consistency is None else {"consistency": consistency}
         if source not in ("auto", "tracker", "mapper"):
             raise ValueError(f"source must be auto, tracker or mapper, not {source!r}")
         has_mapper = self.mapper is not None and bool(getattr(self.mapper, "viewpoints", None))
@@ -309,16 +311,18 @@ class Cut3rSlam:
             if not has_mapper:
                 raise ValueError("source='mapper' needs a Gaussian mapper with keyframes")
             return tsdf.fuse_mapper(self.mapper, voxel_size, trunc_voxels=trunc_voxels, depth_max=depth_max, bounds=bounds,
-                                    max_voxels=max_voxels, sparse=sparse)
+                                    max_voxels=max_voxels, sparse=sparse, **extra)
         n = self.keyframes.counter.value - 1
         if self.tracked_only:
             n = min(n, self.tracker.t1)
         return tsdf.fuse_keyframes(self.keyframes, n, voxel_size, trunc_voxels=trunc_voxels, depth_max=depth_max, conf_min=conf_min,
-                                   bounds=bounds, max_voxels=max_voxels, sparse=sparse)
+                                   bounds=bounds, max_voxels=max_voxels, sparse=sparse, **extra)
 
-    def reconstruct(self, voxel_size, depth_max=5.0, trunc_voxels=8.0, weight_threshold=1.0, source="auto", conf_min=None, sparse=False):
+    def reconstruct(self, voxel_size, depth_max=5.0, trunc_voxels=8.0, weight_threshold=1.0, source="auto", conf_min=None, sparse=False,
+                    consistency=None):
         """fuse() then the mesh at `weight_threshold` (tsdf.Mesh: vertices, colors, faces)"""
-        vol = self.fuse(voxel_size, depth_max=depth_max, trunc_voxels=trunc_voxels, source=source, conf_min=conf_min, sparse=sparse)
+        extra = {} if consistency is None else {"consistency": consistency}
+        vol = self.fuse(voxel_size, depth_max=depth_max, trunc_voxels=trunc_voxels, source=source, conf_min=conf_min, sparse=sparse, **extra)
         return vol.extract_mesh(weight_threshold)
 
     def save_trajectory(self, path, tstamps_full=None):

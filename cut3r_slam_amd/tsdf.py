@@ -373,8 +373,23 @@ def depth_bounds(depth, w2c, K, depth_max):
     return lo.cpu().numpy(), hi.cpu().numpy()
 
 
-def _fuse(depth, w2c, K, voxel_size, trunc_voxels, depth_max, bounds, max_voxels, device, sparse, **views):
-    """the volume over `bounds` (None: the AABB of the valid depths) with all the views fused; sparse: bricks allocated over all views first"""
+def _fuse(depth, w2c, K, voxel_size, trunc_voxels, depth_max, bounds, max_voxels, device, sparse, consistency=None, **views):
+    """the volume over `bounds` (None: the AABB of the valid depths) with all the views fused; sparse: bricks allocated over all views first.
+    consistency: a depth_consistency.ConsistencyOptions -- the depth stack is cross-checked between neighbouring views first and the
+    rejected pixels are zeroed before the bounds and the integration see them; the volume's `consistency` is then (pixels kept, pixels
+    valid before) as device scalars, None without the filter."""
+    stats = None
+    if consistency is not None:
+        from . import depth_consistency
+        valid = torch.isfinite(depth) & (depth > 0) & (depth <= depth_max)
+        depth, keep = depth_consistency.apply(depth, w2c, K, consistency, depth_max)
+        stats = (keep.sum(), valid.sum())
+    vol = _fuse_views(depth, w2c, K, voxel_size, trunc_voxels, depth_max, bounds, max_voxels, device, sparse, **views)
+    vol.consistency = stats
+    return vol
+
+
+def _fuse_views(depth, w2c, K, voxel_size, trunc_voxels, depth_max, bounds, max_voxels, device, sparse, **views):
     if bounds is None:
         bounds = depth_bounds(depth, w2c, K, depth_max)
         if bounds is None:
@@ -389,11 +404,13 @@ def _fuse(depth, w2c, K, voxel_size, trunc_voxels, depth_max, bounds, max_voxels
 
 
 @torch.no_grad()
-def fuse_keyframes(keyframes, n, voxel_size, trunc_voxels=8.0, depth_max=5.0, conf_min=None, bounds=None, max_voxels=2 ** 30, sparse=False):
+def fuse_keyframes(keyframes, n, voxel_size, trunc_voxels=8.0, depth_max=5.0, conf_min=None, bounds=None, max_voxels=2 ** 30, sparse=False,
+                   consistency=None):
     """the tracker's keyframes 0..n-1: depth (s*z at tracking resolution), image, the device world->camera rows and the intrinsics; with
     conf_min, pixels whose stored confidence (conf_ds[i // 5, i % 5], at the store's downsample ratio) is below it are skipped.
     bounds: (lo, hi) or None = the AABB of the valid depths padded by the truncation distance.  sparse: a SparseTSDFVolume (bricks
-    allocated over all views, then all views fused) in place of the dense grid; max_voxels does not apply to it."""
+    allocated over all views, then all views fused) in place of the dense grid; max_voxels does not apply to it.  consistency: a
+    depth_consistency.ConsistencyOptions, the multi-view filter of the depth maps ahead of the fusion (None: the maps as they are)."""
     kf = keyframes
     n = int(n)
     if n <= 0:
@@ -407,8 +424,8 @@ def fuse_keyframes(keyframes, n, voxel_size, trunc_voxels=8.0, depth_max=5.0, co
     if conf_min is not None:
         idx = torch.arange(n, device=dev)
         conf = kf.conf_ds[idx // 5, idx % 5].contiguous()
-    return _fuse(depth, w2c, K, voxel_size, trunc_voxels, depth_max, bounds, max_voxels, dev, sparse, rgb=rgb, conf=conf,
-                 conf_ds=kf.downsample_ratio, conf_min=conf_min)
+    return _fuse(depth, w2c, K, voxel_size, trunc_voxels, depth_max, bounds, max_voxels, dev, sparse, consistency=consistency, rgb=rgb,
+                 conf=conf, conf_ds=kf.downsample_ratio, conf_min=conf_min)
 
 
 @torch.no_grad()
@@ -435,10 +452,10 @@ def render_mapper_views(mapper):
 
 
 @torch.no_grad()
-def fuse_mapper(mapper, voxel_size, trunc_voxels=8.0, depth_max=5.0, bounds=None, max_voxels=2 ** 30, sparse=False):
+def fuse_mapper(mapper, voxel_size, trunc_voxels=8.0, depth_max=5.0, bounds=None, max_voxels=2 ** 30, sparse=False, consistency=None):
     """the reference's source (tsdf_integrate.py over renders_kf/*_after_opt): every mapper keyframe rendered at its refined pose.  The
-    intrinsics are the views' own, as the reference passes intrinsics.npy unchanged.  sparse: as in fuse_keyframes."""
+    intrinsics are the views' own, as the reference passes intrinsics.npy unchanged.  sparse, consistency: as in fuse_keyframes."""
     if not mapper.viewpoints:
         raise ValueError("the mapper has no keyframes to fuse")
     depth, rgb, w2c, K = render_mapper_views(mapper)
-    return _fuse(depth, w2c, K, voxel_size, trunc_voxels, depth_max, bounds, max_voxels, mapper.device, sparse, rgb=rgb)
+    return _fuse(depth, w2c, K, voxel_size, trunc_voxels, depth_max, bounds, max_voxels, mapper.device, sparse, consistency=consistency, rgb=rgb)

@@ -12,7 +12,8 @@ Writes <output>/traj_kf.txt and <output>/intrinsics.npy exactly as the reference
 --mesh-simplify CELL and / or --mesh-min-faces N next to each of them tsdf_mesh_w{W:.1f}_clean.ply, that mesh after vertex clustering and
 small-component removal (cut3r_slam_amd/mesh_clean.py; scored into eval_recon_w{W:.1f}_clean.txt with --gt-mesh); with
 --eval-dense --gtdepthdir G --gt-traj T also <output>/3D_eval_results.txt, the dense point-cloud metrics of the keyframe depths against
-the GT depth maps (scripts/eval7_scenes_dense.py, cut3r_slam_amd/eval_dense.py); with --fill (implies --gs) also <output>/traj_full.txt,
+the GT depth maps (scripts/eval7_scenes_dense.py, cut3r_slam_amd/eval_dense.py); with --depth-consistency the keyframe depth maps of --mesh and
+--eval-dense are first cross-checked between neighbouring views (cut3r_slam_amd/depth_consistency.py; not in the reference); with --fill (implies --gs) also <output>/traj_full.txt,
 a pose for every frame from the first keyframe on (hislam2/util/trajectory_filler.py), and with --eval-render
 <output>/psnr/after_opt/final_result.json and <output>/renders/ (gaussian/utils/eval_utils.py:14-105; with --lpips-weights FILE... also
 mean_lpips, cut3r_slam_amd/lpips.py).  The viewers are out of scope:
@@ -122,7 +123,21 @@ def main(argv=None):
     p.add_argument("--dense-depth-trunc", type=float, default=4.5, help="depths at or beyond this are not scored (the reference's Kinect range)")
     p.add_argument("--dense-source", choices=("auto", "tracker", "mapper"), default="auto",
                    help="depth maps of --eval-dense; auto: the Gaussian map's keyframe renders with --gs, else the tracked keyframes")
+    p.add_argument("--depth-consistency", action="store_true", help="with --mesh / --eval-dense: cross-check every keyframe depth map against "
+                   "its neighbours first and drop the pixels too few of them support or one of them sees through "
+                   "(cut3r_slam_amd/depth_consistency.py; the defaults below are MVSNet's, not tuned on real data)")
+    p.add_argument("--consistency-window", type=int, default=2, metavar="W", help="sources of keyframe i: i - W .. i + W (1 .. 8)")
+    p.add_argument("--consistency-min-support", type=int, default=2, metavar="K", help="sources that must agree with a pixel")
+    p.add_argument("--consistency-rel", type=float, default=0.01, metavar="R", help="relative depth difference of an agreeing source")
+    p.add_argument("--consistency-pix", type=float, default=1.0, metavar="P", help="reprojection distance of an agreeing source, pixels")
+    p.add_argument("--consistency-average", action="store_true", help="kept pixels take the mean of their own and the agreeing depths")
     args = p.parse_args(argv)
+    if args.depth_consistency and not (args.mesh or args.eval_dense):
+        p.error("--depth-consistency needs --mesh or --eval-dense")
+    if not 1 <= args.consistency_window <= 8:
+        p.error("--consistency-window must be in 1 .. 8")
+    if args.consistency_min_support < 0 or not 0 < args.consistency_rel < 1 or not args.consistency_pix > 0:
+        p.error("--consistency-min-support must be >= 0, --consistency-rel in (0, 1), --consistency-pix > 0")
     if args.eval_render and not args.fill:
         p.error("--eval-render needs --fill (the poses of the frames between the keyframes)")
     if args.fill_iters <= 0:
@@ -268,12 +283,22 @@ def main(argv=None):
         lp = f", LPIPS {ev['mean_lpips']:.4f}" if lpips is not None else ""
         print(f"GS mapper: {len(slam.mapper.gaussians)} Gaussians, {len(slam.mapper.viewpoints)} keyframes, PSNR {ev['mean_psnr']:.2f} dB, "
               f"SSIM {ev['mean_ssim']:.4f}{lp} -> {args.output}/gaussians.safetensors")
+    consistency = None
+    if args.depth_consistency:
+        from cut3r_slam_amd.depth_consistency import ConsistencyOptions
+        consistency = ConsistencyOptions(window=args.consistency_window, min_support=args.consistency_min_support, pix=args.consistency_pix,
+                                         rel=args.consistency_rel, average=args.consistency_average)
     if args.mesh:
         from cut3r_slam_amd.tsdf import write_ply
         t_int = time.time()
-        vol = slam.fuse(args.voxel_size, depth_max=args.depth_max, source=args.mesh_source, sparse=args.mesh_sparse)
+        extra = {} if consistency is None else {"consistency": consistency}
+        vol = slam.fuse(args.voxel_size, depth_max=args.depth_max, source=args.mesh_source, sparse=args.mesh_sparse, **extra)
         torch.cuda.synchronize()
         t_int = time.time() - t_int
+        if consistency is not None:
+            kept, valid = (int(v) for v in vol.consistency)
+            print(f"depth consistency (window {consistency.window}, support >= {consistency.min_support}): {kept} of {valid} valid pixels kept "
+                  f"({100.0 * kept / max(valid, 1):.1f} %) before the fusion")
         X, Y, Z = vol.dims
         if args.mesh_sparse:
             print(f"TSDF: {X}x{Y}x{Z} voxels of {vol.voxel_size:g}, {vol.n_bricks} of {vol.table.numel()} bricks allocated "
@@ -316,6 +341,11 @@ def main(argv=None):
     if args.eval_dense:
         from cut3r_slam_amd import eval_dense as ED
         est = ED.from_slam(slam, args.dense_source, stream.frame_timestamps(args.imagedir, args.start))
+        if consistency is not None:                                     # the run's depths only, never the ground truth
+            valid = int((torch.isfinite(torch.as_tensor(est.depth)) & (torch.as_tensor(est.depth) > 0)).sum())
+            est, keep = ED.filter_views(est, consistency, return_keep=True)
+            print(f"depth consistency (window {consistency.window}, support >= {consistency.min_support}): {int(keep.sum())} of {valid} valid "
+                  f"pixels kept ({100.0 * int(keep.sum()) / max(valid, 1):.1f} %) before the dense evaluation")
         gt = ED.load_depth_dir(args.gtdepthdir, args.gt_depth_scale, args.gt_traj, args.gt_calib or args.calib)
         res = ED.dense_metrics(est, gt, depth_trunc=args.dense_depth_trunc)
         ED.write_results(args.output, res)

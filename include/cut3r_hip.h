@@ -797,6 +797,27 @@ int cut3r_focal_weiszfeld(const float* pts, const float* conf, float conf_min, c
 int cut3r_focal_median(const float* pts, const float* conf, float conf_min, const float* pp, int B, int H, int W, float* focal,
                        void* workspace, long long workspace_bytes, void* stream);
 
+/* ---- Multi-view depth consistency ahead of fusion and clouds (csrc/consistency.hip) ------------------------------------------------------
+ * No reference counterpart: the geometric cross-check of MVSNet / Gipuma / COLMAP fusion with a free-space test.  depth [N,H,W] fp32 and
+ * K [N,4] fp32 = fx fy cx cy on the device; ref [R] int32 the views to check, src [R,S] int32 their sources (-1: none), S <= 16; fwd, bwd
+ * [R,S,12] fp64 (device) the rigid rows reference -> source and source -> reference.  One thread per reference pixel (u, v), the sources
+ * in order, everything in fp64 in exactly this order (compiled without FMA contraction; tests/consistency_oracle.py restates it):
+ *   a depth t is valid iff it is finite and 0 < t <= depth_max.  Invalid reference depth d: support = violation = 0, depth_avg = 0.
+ *   x = (u - cx) d / fx, y = (v - cy) d / fy; X = ((F0 x + F1 y) + F2 d) + F3, Y, Z alike; Z <= z_min: no observation.
+ *   us = fx_s X / Z + cx_s, vs alike; outside 0 <= us <= W - 1, 0 <= vs <= H - 1: no observation.
+ *   x0 = floor(us), x1 = min(x0 + 1, W - 1), y alike; the taps t00 (y0,x0) t01 (y0,x1) t10 (y1,x0) t11 (y1,x1); one invalid: no observation.
+ *   Z < t (1 - rel) for all four taps: violation += 1 (the source sees through the point), and this source gives no support.
+ *   ax = us - x0, ay = vs - y0, ds = (t00 (1 - ax) + t01 ax)(1 - ay) + (t10 (1 - ax) + t11 ax) ay; (us, vs, ds) back-projected with the
+ *   source's K, through bwd, projected with the reference's K -> (u2, v2, Z2); support += 1 and acc += Z2 (acc starts at d) iff
+ *   Z2 > z_min, (u2 - u)^2 + (v2 - v)^2 < pix^2 and |Z2 - d| < rel d.
+ *   support, violation [R,H,W] u8; depth_avg [R,H,W] fp32 = float(acc / (1 + support)), or NULL when not wanted.
+ * No atomics: the same bits on every run.  Refused (CUT3R_ERR_ARG, before any launch): null pointers (depth_avg excepted), sizes <= 0,
+ * S > 16, R > 65535, H W >= 2^31 / 16, depth_max or pix <= 0, rel outside (0, 1), z_min < 0, or a NaN among them.  A reference or source
+ * index outside [0, N) reads nothing (all-zero outputs / no observation); the callers refuse such tables before the launch. */
+int cut3r_depth_consistency(const float* depth, const float* K, int N, int H, int W, const int* ref, const int* src, int R, int S,
+                            const double* fwd, const double* bwd, double depth_max, double pix, double rel, double z_min,
+                            unsigned char* support, unsigned char* violation, float* depth_avg, void* stream);
+
 /* Measurement aid of bench.py's roofline (no reference counterpart; not on the product path): a bare MFMA loop (v_mfma_f32_16x16x32_f16,
  * 16 independent accumulator chains per wave, 8 waves per workgroup, `grid` workgroups, `iters` x 16 MFMAs per wave, operands = 16-byte
  * chunks of data[nhalf] fp16, nhalf a power of two >= 32768) with s_memtime / s_memrealtime stamps around the loop.  stamps [grid,2] u64 =
