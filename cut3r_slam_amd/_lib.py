@@ -165,6 +165,9 @@ SIGNATURES = {
     "cut3r_tsdf_sparse_mesh_workspace_bytes": [c_int],
     "cut3r_tsdf_sparse_mesh_count": [c_void_p] * 4 + [c_int] * 4 + [c_float, c_void_p, c_ll, c_void_p, c_void_p],
     "cut3r_tsdf_sparse_mesh_emit": [c_void_p] * 4 + [c_int] * 4 + [c_float] * 4 + [c_void_p, c_ll] + [c_void_p] * 3 + [c_ll, c_ll, c_void_p],
+    "cut3r_tsdf_ray_cast": [c_void_p] * 3 + [c_int] * 3 + [c_float] * 4 + [c_void_p, c_void_p] + [c_int] * 3 + [c_float] * 4 + [c_void_p] * 5,
+    "cut3r_tsdf_sparse_ray_cast": [c_void_p] * 5 + [c_int] * 4 + [c_float] * 4 + [c_void_p, c_void_p] + [c_int] * 3 + [c_float] * 4
+                                  + [c_void_p] * 5,
     "cut3r_mesh_cdf_workspace_bytes": [c_int],
     "cut3r_mesh_area_cdf": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_ll, c_void_p],
     "cut3r_mesh_sample": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_ll, C.c_ulonglong, C.c_ulonglong, c_void_p, c_void_p],

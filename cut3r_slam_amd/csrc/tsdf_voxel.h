@@ -203,6 +203,7 @@ inline int grid_for(long long N) {
 //   coords(n, i, j, k)                  the grid position of stored voxel n; false when that slot holds no voxel of the grid
 //   neighbour(n, i, j, k, di, dj, dk)   the stored index of the IN-GRID voxel (i + di, j + dj, k + dk), d in {-1,0,1}^3, or -1 when it is
 //                                       not stored
+//   index(i, j, k)                      the stored index of the in-grid voxel (i, j, k), or -1 when it is not stored (the ray cast's entry)
 //   kMayMiss                            whether neighbour() can return -1: where it cannot, the handling of -1 folds away at compile time
 
 // the dense grid: voxel n = (k*Y + j)*X + i (x fastest), every voxel stored
@@ -218,6 +219,7 @@ struct DenseStore {
         k = (int)kk;
         return true;
     }
+    DEVINL long long index(int i, int j, int k) const { return ((long long)k * Y + j) * X + i; }
     DEVINL long long neighbour(long long n, int, int, int, int di, int dj, int dk) const {
         return n + di + dj * (long long)X + dk * XY;
     }

@@ -215,14 +215,41 @@ def from_mapper(mapper, stamps=None, consistency=None) -> DepthViews:
     return DepthViews(depth, np.linalg.inv(w), K.double().cpu().numpy(), np.asarray(stamps, np.float64), rgb)
 
 
-def from_slam(slam, source="auto", stamps_full=None, consistency=None) -> DepthViews:
+def cast_views(volume, views, **cast):
+    """tsdf.RayCast of a fused volume (tsdf.TSDFVolume / SparseTSDFVolume) at the poses and intrinsics of `views` and the size of its
+    depth maps: world->camera = the fp64 inverse of each c2w.  cast: the options of the volume's ray_cast."""
+    depth, poses, K, _, _ = _views(views, "views")
+    n, (H, W) = depth.shape[0], depth.shape[1:]
+    K = np.broadcast_to(np.asarray(K.detach().cpu() if isinstance(K, torch.Tensor) else K, np.float64).reshape(-1, 4), (n, 4))
+    w2c = np.linalg.inv(poses)[:, :3].reshape(n, 12).astype(np.float32)
+    return volume.ray_cast(torch.from_numpy(w2c), torch.from_numpy(K.astype(np.float32)), H, W, **cast)
+
+
+def from_volume(volume, views, **cast) -> DepthViews:
+    """the fused model's own depth maps: `volume` ray-cast (csrc/tsdf_raycast.hip) at every pose of `views`, with their intrinsics, size
+    and stamps; 0 where a ray misses, which the clouds skip.  The colours are the volume's."""
+    rc = cast_views(volume, views, normals=False, **cast)
+    v = DepthViews(*views)
+    return DepthViews(rc.depth, v.c2w, v.K, v.stamps, rc.color)
+
+
+def from_slam(slam, source="auto", stamps_full=None, consistency=None, volume=None, fuse=None) -> DepthViews:
     """the rule of Cut3rSlam.fuse / --mesh-source: "mapper", "tracker", or "auto" = the mapper when one with keyframes is attached.
+    "fused": the run's TSDF volume ray-cast at each keyframe's pose and intrinsics (from_volume) -- `volume` when given, else
+    slam.fuse(**fuse), fuse = its arguments (voxel_size at least); the keyframes are those of fuse's source (default auto).
     stamps_full: the per-frame stamps (stream.frame_timestamps) that map the store's frame indices to the stamps of traj_kf.txt.
     consistency: filter_views' options (None: the depth maps as they are)."""
     if consistency is not None:
-        return filter_views(from_slam(slam, source, stamps_full), consistency)
+        return filter_views(from_slam(slam, source, stamps_full, volume=volume, fuse=fuse), consistency)
+    if source == "fused":
+        fuse = dict(fuse or {})
+        if volume is None:
+            if "voxel_size" not in fuse:
+                raise ValueError("source='fused' needs a volume, or fuse={'voxel_size': ...} to make one")
+            volume = slam.fuse(**fuse)
+        return from_volume(volume, from_slam(slam, fuse.get("source", "auto"), stamps_full))
     if source not in ("auto", "tracker", "mapper"):
-        raise ValueError(f"source must be auto, tracker or mapper, not {source!r}")
+        raise ValueError(f"source must be auto, tracker, mapper or fused, not {source!r}")
     full = None if stamps_full is None else np.asarray(stamps_full, np.float64).reshape(-1)
     lookup = (lambda idx: None) if full is None else (lambda idx: full[np.asarray(idx, np.float64).astype(int)])
     has_mapper = slam.mapper is not None and bool(getattr(slam.mapper, "viewpoints", None))

@@ -916,6 +916,56 @@ def tsdf_sparse_extract_mesh(tsdf, weight, color, table, bricks, dims, origin, v
         "tsdf_sparse", "sparse TSDF pool")
 
 
+# ------------------------------------------------------------------------------------------------ ray cast of the TSDF volumes
+def _tsdf_cast(what, dev, c2w, K, H, W, t_min, t_max, step, voxel, normals, colors, count):
+    """the views and the outputs of a ray-cast launch: c2w [B,12], K [B,4] fp32 on the GPU, B <= 16 -> (B, H, W, depth [B,H,W], normal
+    [B,H,W,3] or None, rgb u8 [B,3,H,W] or None, samples int32 [B,H,W] or None)"""
+    _cuda(c2w, K)
+    _req(c2w.dim() == 2 and c2w.shape[1] == 12 and c2w.dtype == F32 and c2w.is_contiguous(), "c2w: contiguous fp32 [B,12]")
+    B, H, W = c2w.shape[0], int(H), int(W)
+    _req(1 <= B <= TSDF_MAX_VIEWS, f"{what}: 1..{TSDF_MAX_VIEWS} views per launch")
+    _req(K.shape == (B, 4) and K.dtype == F32 and K.is_contiguous(), "K: contiguous fp32 [B,4]")
+    _req(H > 0 and W > 0 and B * H * W < 2 ** 31, "image: H, W > 0 and fewer than 2^31 pixels per launch")
+    _req(float(voxel) > 0 and float(step) > 0, "voxel size and step must be > 0")
+    _req(0 <= float(t_min) <= float(t_max), "ray range: 0 <= t_min <= t_max")
+    depth = torch.empty(B, H, W, dtype=F32, device=dev)
+    normal = torch.empty(B, H, W, 3, dtype=F32, device=dev) if normals else None
+    rgb = torch.empty(B, 3, H, W, dtype=torch.uint8, device=dev) if colors else None
+    samples = torch.empty(B, H, W, dtype=torch.int32, device=dev) if count else None
+    return B, H, W, depth, normal, rgb, samples
+
+
+def tsdf_ray_cast(tsdf, weight, color, origin, voxel, c2w, K, H, W, t_min, t_max, step, weight_threshold=1.0, normals=True, colors=True,
+                  count=False):
+    """ray cast of the dense planes (VoxelBlockGrid.ray_cast, tsdf_integrate.py:34) from B <= 16 views in one launch: c2w [B,12]
+    camera->world rows, K [B,4] -> (depth [B,H,W] z-depth, 0 on a miss; normal [B,H,W,3] world frame or None; rgb u8 [B,3,H,W] or None;
+    samples int32 [B,H,W] looked up per ray, or None)"""
+    X, Y, Z = _tsdf_planes(tsdf, weight, color)
+    B, H, W, depth, normal, rgb, samples = _tsdf_cast("tsdf_ray_cast", tsdf.device, c2w, K, H, W, t_min, t_max, step, voxel, normals, colors,
+                                                      count)
+    lib = _lib.load()
+    check(lib.cut3r_tsdf_ray_cast(_p(tsdf), _p(weight), _p(color), X, Y, Z, float(origin[0]), float(origin[1]), float(origin[2]), float(voxel),
+                                  _p(c2w), _p(K), B, H, W, float(t_min), float(t_max), float(step), float(weight_threshold), _p(depth),
+                                  _p(normal), _p(rgb), _p(samples), _stream()), "cut3r_tsdf_ray_cast")
+    return depth, normal, rgb, samples
+
+
+def tsdf_sparse_ray_cast(tsdf, weight, color, table, bricks, dims, origin, voxel, c2w, K, H, W, t_min, t_max, step, weight_threshold=1.0,
+                         normals=True, colors=True, count=False):
+    """tsdf_ray_cast over the brick pool: a voxel of a brick that is not allocated is not stored, and a cell with such a corner is invalid"""
+    X, Y, Z, T = _tsdf_sparse_grid(dims)
+    nb = _tsdf_pool(tsdf, weight, color, bricks, T)
+    _tsdf_table(table, "table", torch.int32, T)
+    B, H, W, depth, normal, rgb, samples = _tsdf_cast("tsdf_sparse_ray_cast", tsdf.device, c2w, K, H, W, t_min, t_max, step, voxel, normals,
+                                                      colors, count)
+    lib = _lib.load()
+    check(lib.cut3r_tsdf_sparse_ray_cast(_p(tsdf), _p(weight), _p(color), _p(table), _p(bricks), nb, X, Y, Z, float(origin[0]),
+                                         float(origin[1]), float(origin[2]), float(voxel), _p(c2w), _p(K), B, H, W, float(t_min), float(t_max),
+                                         float(step), float(weight_threshold), _p(depth), _p(normal), _p(rgb), _p(samples), _stream()),
+          "cut3r_tsdf_sparse_ray_cast")
+    return depth, normal, rgb, samples
+
+
 # ------------------------------------------------------------------------------------------------ reconstruction metrics
 def _points(t, name):
     _cuda(t)

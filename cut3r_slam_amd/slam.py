@@ -325,6 +325,17 @@ class Cut3rSlam:
         vol = self.fuse(voxel_size, depth_max=depth_max, trunc_voxels=trunc_voxels, source=source, conf_min=conf_min, sparse=sparse, **extra)
         return vol.extract_mesh(weight_threshold)
 
+    def ray_cast(self, volume=None, voxel_size=None, source="auto", **cast):
+        """the fused model seen from the run's keyframes: tsdf.RayCast (depth [n,H,W], normal [n,H,W,3], color u8 [n,3,H,W]) of `volume`
+        ray-cast at every keyframe's pose and intrinsics -- the keyframes of `source`, as fuse() picks them.  volume None: fuse(voxel_size,
+        source=source) first.  cast: the options of the volume's ray_cast (depth_min, depth_max, weight_threshold, step_voxels, ...)."""
+        from . import eval_dense
+        if volume is None:
+            if voxel_size is None:
+                raise ValueError("ray_cast needs a volume or a voxel_size to fuse one")
+            volume = self.fuse(voxel_size, source=source)
+        return eval_dense.cast_views(volume, eval_dense.from_slam(self, source), **cast)
+
     def save_trajectory(self, path, tstamps_full=None):
         ts, poses = self.trajectory()
         if tstamps_full is not None:

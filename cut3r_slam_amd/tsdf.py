@@ -10,6 +10,8 @@ of the Gaussian map go into an Open3D VoxelBlockGrid and `tsdf_mesh_w{w:.1f}.ply
   fuse_keyframes   the tracker's keyframe store (depth, image, w2c, intrinsics, optional confidence gate) -> TSDFVolume
   fuse_mapper      the reference's source: every mapper keyframe rendered at its refined pose, quantised as the reference's files are
                    (hislam2/gaussian/utils/eval_utils.py:124-134: depth uint16 at 6553.5 per metre, colour (x*255) truncated to u8)
+  ray_cast         (both volumes) depth, normal and colour images of the fused model at given poses, marched through the voxels
+                   (csrc/tsdf_raycast.hip: Open3D's VoxelBlockGrid.ray_cast); shade / write_previews turn them into PNGs
   write_ply / read_ply   binary little-endian PLY (x y z float, red green blue uchar, vertex_indices uchar count + int32)
 
 Truncation: tsdf_integrate.py passes no sdf_trunc, so Open3D's default of 8 voxels applies; that is the default here
@@ -32,6 +34,12 @@ class Mesh(NamedTuple):
     vertices: np.ndarray        # float32 [V,3]
     colors: np.ndarray          # uint8 [V,3]
     faces: np.ndarray           # int32 [F,3]
+
+
+class RayCast(NamedTuple):
+    depth: torch.Tensor         # float32 [B,H,W] z-depth of the surface, 0 where the ray misses
+    normal: torch.Tensor        # float32 [B,H,W,3] world frame, towards the viewer, 0 on a miss (None when not asked for)
+    color: torch.Tensor         # uint8 [B,3,H,W], 0 on a miss (None when not asked for)
 
 
 def _lattice(lo, hi, voxel_size, pad):
@@ -94,6 +102,31 @@ class _Volume:
     def extract_mesh(self, weight_threshold=1.0) -> Mesh:
         return Mesh(*(t.cpu().numpy() for t in self._extract(weight_threshold)))
 
+    @torch.no_grad()
+    def ray_cast(self, w2c, K, H, W, depth_min=0.0, depth_max=None, weight_threshold=1.0, step_voxels=0.5, normals=True, colors=True,
+                 count=False):
+        """the fused model seen from B views of H x W (Open3D VoxelBlockGrid.ray_cast), in launches of <= 16: w2c [B,12] (or [B,3,4] /
+        [B,4,4]) world->camera, K [4] or [B,4] fx fy cx cy.  Every pixel's ray is sampled at z-depths depth_min + k * step_voxels *
+        voxel_size up to depth_max (None: the volume's own); the surface lies between a sample with tsdf >= 0 and the next with tsdf <
+        0, both in cells whose corners all have weight >= weight_threshold.  A ray that meets a negative value first (the camera is
+        inside or behind a surface, or the ray comes out of unknown space) misses.  count=True: also the int32 [B,H,W] samples looked
+        up per ray, as a fourth value."""
+        w2c = torch.as_tensor(w2c).to(torch.float32)
+        w2c = (w2c.reshape(-1, w2c.shape[-2], 4)[:, :3] if w2c.shape[-2:] in ((3, 4), (4, 4)) else w2c).reshape(-1, 12)
+        B = w2c.shape[0]
+        c2w = torch.from_numpy(c2w_rows(w2c.cpu().numpy())).to(self.device)
+        K = torch.as_tensor(K).to(self.device, torch.float32).reshape(-1, 4)
+        K = (K.expand(B, 4) if K.shape[0] == 1 else K).contiguous()
+        if B < 1 or K.shape[0] != B:
+            raise ValueError(f"ray_cast: {B} poses, {K.shape[0]} intrinsics")
+        t_max = self.depth_max if depth_max is None else float(depth_max)
+        step = float(np.float32(step_voxels * self.voxel_size))
+        out = [self._ray_cast_batch(c2w[a:a + ops.TSDF_MAX_VIEWS], K[a:a + ops.TSDF_MAX_VIEWS], int(H), int(W), float(depth_min), t_max, step,
+                                    weight_threshold=weight_threshold, normals=normals, colors=colors, count=count)
+               for a in range(0, B, ops.TSDF_MAX_VIEWS)]
+        depth, normal, color, samples = (None if q[0] is None else torch.cat(q) for q in zip(*out))
+        return (RayCast(depth, normal, color), samples) if count else RayCast(depth, normal, color)
+
 
 class TSDFVolume(_Volume):
     """Dense TSDF grid: voxel (i, j, k) at origin + voxel_size * (i, j, k), planes [Z,Y,X] (x fastest); tsdf = 1, weight = color = 0 at start."""
@@ -137,6 +170,9 @@ class TSDFVolume(_Volume):
 
     def _extract(self, weight_threshold):
         return ops.tsdf_extract_mesh(self.tsdf, self.weight, self.color, self.origin, self.voxel_size, weight_threshold)
+
+    def _ray_cast_batch(self, c2w, K, H, W, t_min, t_max, step, **out):
+        return ops.tsdf_ray_cast(self.tsdf, self.weight, self.color, self.origin, self.voxel_size, c2w, K, H, W, t_min, t_max, step, **out)
 
 
 def c2w_rows(w2c):
@@ -246,6 +282,17 @@ class SparseTSDFVolume(_Volume):
         return ops.tsdf_sparse_extract_mesh(self.tsdf, self.weight, self.color, self.table, self.bricks, self.dims, self.origin,
                                             self.voxel_size, weight_threshold)
 
+    def _ray_cast_batch(self, c2w, K, H, W, t_min, t_max, step, weight_threshold=1.0, normals=True, colors=True, count=False):
+        if self.n_bricks == 0:                                          # nothing stored: every ray misses
+            B, dev = c2w.shape[0], self.device
+            return (torch.zeros(B, H, W, dtype=torch.float32, device=dev),
+                    torch.zeros(B, H, W, 3, dtype=torch.float32, device=dev) if normals else None,
+                    torch.zeros(B, 3, H, W, dtype=torch.uint8, device=dev) if colors else None,
+                    torch.zeros(B, H, W, dtype=torch.int32, device=dev) if count else None)
+        return ops.tsdf_sparse_ray_cast(self.tsdf, self.weight, self.color, self.table, self.bricks, self.dims, self.origin, self.voxel_size,
+                                        c2w, K, H, W, t_min, t_max, step, weight_threshold=weight_threshold, normals=normals, colors=colors,
+                                        count=count)
+
     @torch.no_grad()
     def allocated_mask(self):
         """bool [Z,Y,X]: the voxels of the virtual grid that are stored (raises above the dense limit of 2^31 - 1 voxels)"""
@@ -273,6 +320,45 @@ class SparseTSDFVolume(_Volume):
             d[bz, :, by, :, bx, :] = pool.reshape(-1, 8, 8, 8)
             out.append(d.reshape(BZ * 8, BY * 8, BX * 8)[:Z, :Y, :X].contiguous())
         return out[0], out[1], torch.stack(out[2:])
+
+
+# ------------------------------------------------------------------------------------------------------------------- previews
+@torch.no_grad()
+def shade(normal, w2c):
+    """a normal map of the ray cast as an image: normal [B,H,W,3] (world frame) rotated into each camera's frame by w2c [B,12] (or
+    [B,3,4] / [B,4,4]) and mapped (n_cam * 0.5 + 0.5) * 255 -> uint8 [B,H,W,3]; black where the normal is 0 (the ray missed)"""
+    B = normal.shape[0]
+    w = torch.as_tensor(w2c).to(normal.device, torch.float32)
+    R = (w.reshape(B, -1, 4)[:, :3, :3] if w.shape[-2:] in ((3, 4), (4, 4)) else w.reshape(B, 3, 4)[:, :, :3])
+    n = torch.einsum("bij,bhwj->bhwi", R, normal)
+    img = torch.floor((n * 0.5 + 0.5).clamp(0, 1) * 255 + 0.5).to(torch.uint8)
+    return img * (normal != 0).any(-1, keepdim=True)
+
+
+@torch.no_grad()
+def write_previews(volume, w2c, K, H, W, outdir, every=1, **cast):
+    """ray-cast every `every`-th view and write <outdir>/{i:05d}_depth.png (16 bits at DEPTH_SCALE per metre, 0 = no surface),
+    {i:05d}_normal.png (shade) and {i:05d}_color.png; i is the view's index in w2c.  cast: the options of ray_cast.  Returns the indices
+    written and the RayCast of those views."""
+    import os
+    from PIL import Image
+    if int(every) < 1:
+        raise ValueError("every must be >= 1")
+    w = torch.as_tensor(w2c).to(torch.float32)
+    w = (w.reshape(-1, w.shape[-2], 4)[:, :3] if w.shape[-2:] in ((3, 4), (4, 4)) else w).reshape(-1, 12)
+    idx = list(range(0, w.shape[0], int(every)))
+    K = torch.as_tensor(K).to(torch.float32).reshape(-1, 4)
+    K = K.expand(w.shape[0], 4) if K.shape[0] == 1 else K
+    rc = volume.ray_cast(w[idx], K[idx], H, W, normals=True, colors=True, **cast)
+    raw = torch.floor(torch.clamp(rc.depth * DEPTH_SCALE, 0, 65535)).cpu().numpy().astype(np.uint16)
+    nrm = shade(rc.normal, w[idx]).cpu().numpy()
+    col = rc.color.permute(0, 2, 3, 1).contiguous().cpu().numpy()
+    os.makedirs(outdir, exist_ok=True)
+    for n, i in enumerate(idx):
+        Image.fromarray(raw[n]).save(os.path.join(outdir, f"{i:05d}_depth.png"))
+        Image.fromarray(nrm[n]).save(os.path.join(outdir, f"{i:05d}_normal.png"))
+        Image.fromarray(col[n]).save(os.path.join(outdir, f"{i:05d}_color.png"))
+    return idx, rc
 
 
 # ------------------------------------------------------------------------------------------------------------------------ PLY

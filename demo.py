@@ -10,7 +10,9 @@ the image centre) and <output>/calib_estimated.txt holds it for the input frames
 Writes <output>/traj_kf.txt and <output>/intrinsics.npy exactly as the reference does (evo-compatible TUM rows); with --mesh also
 <output>/tsdf_mesh_w{W:.1f}.ply per --mesh-weight, the reference's post-run mesh (TSDF fusion on the GPU, cut3r_slam_amd/tsdf.py), and with
 --mesh-simplify CELL and / or --mesh-min-faces N next to each of them tsdf_mesh_w{W:.1f}_clean.ply, that mesh after vertex clustering and
-small-component removal (cut3r_slam_amd/mesh_clean.py; scored into eval_recon_w{W:.1f}_clean.txt with --gt-mesh); with
+small-component removal (cut3r_slam_amd/mesh_clean.py; scored into eval_recon_w{W:.1f}_clean.txt with --gt-mesh), and with
+--mesh-preview N <output>/tsdf_preview/{kf:05d}_{depth,normal,color}.png, the fused volume ray-cast at every N-th keyframe (--dense-source
+fused scores such depth maps in --eval-dense); with
 --eval-dense --gtdepthdir G --gt-traj T also <output>/3D_eval_results.txt, the dense point-cloud metrics of the keyframe depths against
 the GT depth maps (scripts/eval7_scenes_dense.py, cut3r_slam_amd/eval_dense.py); with --depth-consistency the keyframe depth maps of --mesh and
 --eval-dense are first cross-checked between neighbouring views (cut3r_slam_amd/depth_consistency.py; not in the reference); with --fill (implies --gs) also <output>/traj_full.txt,
@@ -104,6 +106,8 @@ def main(argv=None):
                    help="auto: the Gaussian map's keyframe renders with --gs, else the tracked keyframes")
     p.add_argument("--mesh-sparse", action="store_true", help="with --mesh: fuse into the sparse brick volume (bricks of 8^3 voxels near "
                    "surfaces only: the same mesh, memory by surface area, no 2^31-voxel limit)")
+    p.add_argument("--mesh-preview", type=int, default=None, metavar="N", help="with --mesh: ray-cast the fused volume at every N-th keyframe "
+                   "and write <output>/tsdf_preview/{kf:05d}_{depth,normal,color}.png (depth: 16 bits at 6553.5 per metre, 0 = no surface)")
     p.add_argument("--mesh-simplify", type=float, default=None, metavar="CELL", help="with --mesh: also write tsdf_mesh_w{W:.1f}_clean.ply, "
                    "the mesh after vertex clustering at this cell size (cut3r_slam_amd/mesh_clean.py)")
     p.add_argument("--mesh-min-faces", type=int, default=None, metavar="N", help="with --mesh: also write tsdf_mesh_w{W:.1f}_clean.ply, the "
@@ -121,8 +125,9 @@ def main(argv=None):
     p.add_argument("--gt-depth-scale", type=float, default=6553.5, help="raw units per metre of the --gtdepthdir PNGs")
     p.add_argument("--gt-calib", type=str, default=None, help="calibration of the GT depth maps (default: --calib)")
     p.add_argument("--dense-depth-trunc", type=float, default=4.5, help="depths at or beyond this are not scored (the reference's Kinect range)")
-    p.add_argument("--dense-source", choices=("auto", "tracker", "mapper"), default="auto",
-                   help="depth maps of --eval-dense; auto: the Gaussian map's keyframe renders with --gs, else the tracked keyframes")
+    p.add_argument("--dense-source", choices=("auto", "tracker", "mapper", "fused"), default="auto",
+                   help="depth maps of --eval-dense; auto: the Gaussian map's keyframe renders with --gs, else the tracked keyframes; fused: "
+                   "the TSDF volume (that of --mesh, else one fused at --voxel-size) ray-cast at every keyframe")
     p.add_argument("--depth-consistency", action="store_true", help="with --mesh / --eval-dense: cross-check every keyframe depth map against "
                    "its neighbours first and drop the pixels too few of them support or one of them sees through "
                    "(cut3r_slam_amd/depth_consistency.py; the defaults below are MVSNet's, not tuned on real data)")
@@ -159,6 +164,8 @@ def main(argv=None):
         p.error("--gt-mesh needs --mesh")
     if args.mesh_sparse and not args.mesh:
         p.error("--mesh-sparse needs --mesh")
+    if args.mesh_preview is not None and (not args.mesh or args.mesh_preview < 1):
+        p.error("--mesh-preview N needs --mesh and N >= 1")
     if (args.mesh_simplify is not None or args.mesh_min_faces is not None) and not args.mesh:
         p.error("--mesh-simplify and --mesh-min-faces need --mesh")
     if args.mesh_simplify is not None and not (0 < args.mesh_simplify < float("inf")):
@@ -288,6 +295,7 @@ def main(argv=None):
         from cut3r_slam_amd.depth_consistency import ConsistencyOptions
         consistency = ConsistencyOptions(window=args.consistency_window, min_support=args.consistency_min_support, pix=args.consistency_pix,
                                          rel=args.consistency_rel, average=args.consistency_average)
+    vol = None
     if args.mesh:
         from cut3r_slam_amd.tsdf import write_ply
         t_int = time.time()
@@ -305,6 +313,17 @@ def main(argv=None):
                   f"({vol.nbytes / 1e9:.2f} GB), allocated and integrated in {1e3 * t_int:.1f} ms")
         else:
             print(f"TSDF: {X}x{Y}x{Z} voxels of {vol.voxel_size:g} ({vol.nbytes / 1e9:.2f} GB), integrated in {1e3 * t_int:.1f} ms")
+        if args.mesh_preview is not None:
+            from cut3r_slam_amd import eval_dense as ED
+            from cut3r_slam_amd.tsdf import write_previews
+            import numpy as np
+            kfs = ED.from_slam(slam, args.mesh_source)
+            t_rc = time.time()
+            idx, _ = write_previews(vol, np.linalg.inv(ED.pose_matrices(kfs.c2w))[:, :3], kfs.K, *kfs.depth.shape[1:],
+                                    os.path.join(args.output, "tsdf_preview"), every=args.mesh_preview, weight_threshold=args.mesh_weight[0])
+            print(f"ray cast of {len(idx)} keyframes (every {args.mesh_preview}) in {1e3 * (time.time() - t_rc):.1f} ms -> "
+                  f"{args.output}/tsdf_preview")
+
         def score(mesh, w, tag):
             from cut3r_slam_amd import eval_recon as ER
             if args.gt_traj:
@@ -340,7 +359,10 @@ def main(argv=None):
                     score(cleaned, w, "_clean")
     if args.eval_dense:
         from cut3r_slam_amd import eval_dense as ED
-        est = ED.from_slam(slam, args.dense_source, stream.frame_timestamps(args.imagedir, args.start))
+        fused = {}
+        if args.dense_source == "fused":                                # the volume of --mesh when there is one
+            fused = {"volume": vol, "fuse": {"voxel_size": args.voxel_size, "depth_max": args.depth_max, "source": args.mesh_source}}
+        est = ED.from_slam(slam, args.dense_source, stream.frame_timestamps(args.imagedir, args.start), **fused)
         if consistency is not None:                                     # the run's depths only, never the ground truth
             valid = int((torch.isfinite(torch.as_tensor(est.depth)) & (torch.as_tensor(est.depth) > 0)).sum())
             est, keep = ED.filter_views(est, consistency, return_keep=True)

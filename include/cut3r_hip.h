@@ -604,6 +604,29 @@ int cut3r_tsdf_sparse_mesh_emit(const float* tsdf, const float* color, const int
                                 float ox, float oy, float oz, float voxel, const void* workspace, long long workspace_bytes, float* verts,
                                 unsigned char* colors, int* faces, long long nv, long long nf, void* stream);
 
+/* ---- Ray cast of the TSDF volumes (csrc/tsdf_raycast.hip) ----------------------------------------------------------------------------
+ * Replaces Open3D VoxelBlockGrid.ray_cast, the third operation of the grid that tsdf_integrate.py:34 builds: depth, normal and colour
+ * images of the fused model.  The planes / the pool with its table and brick list are those of the two families above.  c2w [B,12]
+ * camera->world rows and K [B,4] fx fy cx cy on the device, B in 1..16 views of H x W, one thread per pixel, a wave per 8 x 8 tile.
+ * Pixel (u, v): origin = the translation of c2w, direction d = R ((u - cx) / fx, (v - cy) / fy, 1), so the ray parameter is the
+ * z-depth.  Samples t_k = t_min + (float)k * step while t_k <= t_max (at most 2^30); per axis g = ((c + t_k d) - origin) / voxel, cell =
+ * floor(g).  A sample is valid when 0 <= cell < dim - 1 on every axis and the cell's eight corners are stored with weight >=
+ * weight_threshold; its value is the trilinear interpolation of tsdf.  An invalid sample forgets the predecessor, a valid one with
+ * value >= 0 becomes it, a valid one with value < 0 ends the ray: depth = t_{k-1} + (t_k - t_{k-1}) s_{k-1} / (s_{k-1} - s_k) when the
+ * predecessor is there, else 0 (a miss: no ray looks through a back face or out of unknown space).
+ * Outputs: depth [B,H,W] fp32; normal [B,H,W,3] fp32 or NULL, the normalised gradient of the interpolant at sample k (world frame,
+ * towards positive tsdf; 0 on a miss); rgb u8 [B,3,H,W] or NULL, the interpolated colour rounded floor(c + 0.5) (0 on a miss);
+ * samples int32 [B,H,W] or NULL, how many samples the ray looked up in the store.  Clipping to the grid and, in the brick pool, skipping
+ * inside unallocated bricks leave every output bit as the plain march gives it.
+ * CUT3R_ERR_ARG: a null plane, pose or depth, B outside 1..16, H, W, voxel or step <= 0, t_min < 0, t_max < t_min, bad dims or nb. */
+int cut3r_tsdf_ray_cast(const float* tsdf, const float* weight, const float* color, int X, int Y, int Z, float ox, float oy, float oz,
+                        float voxel, const float* c2w, const float* K, int B, int H, int W, float t_min, float t_max, float step,
+                        float weight_threshold, float* depth, float* normal, unsigned char* rgb, int* samples, void* stream);
+int cut3r_tsdf_sparse_ray_cast(const float* tsdf, const float* weight, const float* color, const int* table, const int* bricks, int nb,
+                               int X, int Y, int Z, float ox, float oy, float oz, float voxel, const float* c2w, const float* K, int B, int H,
+                               int W, float t_min, float t_max, float step, float weight_threshold, float* depth, float* normal,
+                               unsigned char* rgb, int* samples, void* stream);
+
 /* ---- Reconstruction metrics (csrc/recon.hip) ----------------------------------------------------------------------------------------
  * mesh_area_cdf / mesh_sample replace trimesh.sample.sample_surface (scripts/eval_recon.py:104-107).  verts [V,3] fp32, faces [F,3] int32
  * (a face with an index outside 0..V-1 has area 0).  area_cdf: area [F] fp32 = 0.5 |(b - a) x (c - a)|, cdf [F] fp64 = inclusive scan of
