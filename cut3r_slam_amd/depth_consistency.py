@@ -30,7 +30,7 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, views
 
 
 class ConsistencyOptions(NamedTuple):
@@ -54,16 +54,6 @@ def neighbour_table(n, window) -> np.ndarray:
     return out
 
 
-def _rows(w2c) -> np.ndarray:
-    """fp64 [n,3,4] of world->camera rows [n,12], [n,3,4] or [n,4,4]"""
-    w = np.asarray(w2c.detach().cpu() if isinstance(w2c, torch.Tensor) else w2c, np.float64)
-    if w.ndim == 3 and w.shape[1:] in ((3, 4), (4, 4)):
-        return np.ascontiguousarray(w[:, :3])
-    if w.ndim == 2 and w.shape[1] in (12, 16):
-        return np.ascontiguousarray(w.reshape(len(w), -1, 4)[:, :3])
-    raise ValueError(f"w2c: [n,12], [n,3,4] or [n,4,4], got {w.shape}")
-
-
 def _tables(n, ref, src):
     ref = np.asarray(ref)
     src = np.asarray(src)
@@ -82,11 +72,10 @@ def relative_rows(w2c, ref, src):
     """(fwd, bwd) fp64 [R,S,12]: fwd[r,k] = W_s . W_r^-1 carries camera coordinates of view ref[r] into view src[r,k], bwd the other way;
     the inverse of a rigid [R | t] is formed as [R^T | -R^T t].  Rows of a missing source (-1) are 0.  Refused: src == ref, an index
     outside the views, more than 16 sources."""
-    W = _rows(w2c)
+    W = np.ascontiguousarray(views.pose_rows(w2c))
     ref, src = _tables(len(W), ref, src)
     Rm, t = W[:, :, :3], W[:, :, 3]
-    Ri = Rm.transpose(0, 2, 1)
-    ti = -np.einsum("nij,nj->ni", Ri, t)
+    Ri, ti = views.inverse_rigid(W)
 
     def compose(a, b):             # W_a . W_b^-1 for index arrays a, b of one shape
         Rab = np.einsum("...ij,...jk->...ik", Rm[a], Ri[b])
@@ -116,8 +105,7 @@ def consistency(depth, w2c, K, src=None, window=2, depth_max=5.0, pix=1.0, rel=0
     ref = np.arange(N, dtype=np.int32)
     fwd, bwd = relative_rows(w2c, ref, src)
     src = np.asarray(src, np.int32)
-    K = torch.as_tensor(K).detach().to(depth.device, torch.float32).reshape(-1, 4)
-    K = (K.expand(N, 4) if K.shape[0] == 1 else K).contiguous()
+    K = views.intrinsics(K, N, torch.float32).to(depth.device)
     chunk = int(chunk)
     if not 1 <= chunk <= ops.CONSISTENCY_MAX_REFS:
         raise ValueError(f"chunk: 1 .. {ops.CONSISTENCY_MAX_REFS}")

@@ -30,6 +30,7 @@ from . import ops
 from .eval_ate import associate, load_tum, umeyama
 from .eval_recon import chamfer_distance_RMSE, icp_point_to_point
 from .stream import load_calib, natsorted
+from .views import intrinsics, inverse44, pose_matrices, run_views
 
 KEYS = ("RMSE_acc", "RMSE_comp", "Chamfer_distance")
 DEPTH_SCALE = 6553.5               # the run's depth PNGs (eval7_scenes_dense.py:203)
@@ -47,32 +48,10 @@ def _device():
     return torch.device("cuda", torch.cuda.current_device())
 
 
-def pose_matrices(c2w) -> np.ndarray:
-    """fp64 [n,4,4] from [n,4,4], [n,3,4] or TUM rows ([n,8] with the stamp first, [n,7] without): t, q = (x, y, z, w)"""
-    p = np.asarray(c2w.detach().cpu() if isinstance(c2w, torch.Tensor) else c2w, np.float64)
-    if p.ndim == 3 and p.shape[1:] in ((4, 4), (3, 4)):
-        out = np.tile(np.eye(4), (p.shape[0], 1, 1))
-        out[:, :3] = p[:, :3]
-        return out
-    if p.ndim != 2 or p.shape[1] not in (7, 8):
-        raise ValueError(f"poses: [n,4,4], [n,3,4], [n,8] or [n,7], got {p.shape}")
-    p = p[:, -7:]
-    t, q = p[:, :3], p[:, 3:]
-    q = q / np.linalg.norm(q, axis=1, keepdims=True)
-    x, y, z, w = q.T
-    R = np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
-                  2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
-                  2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], 1).reshape(-1, 3, 3)
-    out = np.tile(np.eye(4), (len(p), 1, 1))
-    out[:, :3, :3], out[:, :3, 3] = R, t
-    return out
-
-
 def grid_intrinsics(K, n, shape, size) -> np.ndarray:
     """fp64 [n,4]: the intrinsics of the H x W maps carried to the H1 x W1 sampling grid as vggt_resize does (eval7_scenes_dense.py:66-70):
     fx W1 / W, fy H1 / H, cx W1 / W, cy H1 / H"""
-    K = np.asarray(K.detach().cpu() if isinstance(K, torch.Tensor) else K, np.float64)
-    K = np.broadcast_to(K.reshape(-1, 4), (n, 4)).copy()
+    K = intrinsics(K, n)
     if size is not None:
         (H, W), (H1, W1) = shape, size
         K[:, [0, 2]] = K[:, [0, 2]] / (W / W1)
@@ -166,25 +145,26 @@ def filter_views(views, consistency, return_keep=False):
     the RUN's depths: ground truth is never filtered."""
     from . import depth_consistency
     depth, poses, K, _, _ = _views(views, "views")
-    n = depth.shape[0]
-    K = np.broadcast_to(np.asarray(K.detach().cpu() if isinstance(K, torch.Tensor) else K, np.float64).reshape(-1, 4), (n, 4)).copy()
-    out, keep = depth_consistency.apply(depth.to(_device(), torch.float32), np.linalg.inv(poses)[:, :3], K, consistency, float("inf"))
+    out, keep = depth_consistency.apply(depth.to(_device(), torch.float32), inverse44(poses)[:, :3], intrinsics(K, len(poses)), consistency,
+                                        float("inf"))
     v = DepthViews(*views)._replace(depth=out)
     return (v, keep) if return_keep else v
+
+
+def _filtered(views, consistency) -> DepthViews:
+    return views if consistency is None else filter_views(views, consistency)
 
 
 def from_keyframes(keyframes, n, stamps=None, consistency=None) -> DepthViews:
     """the tracker's keyframes 0..n-1 (the same ones as the trajectory): depth, pose (c2w [t, q xyzw]), intrinsic, tstamp, image.  stamps:
     replaces the store's frame indices (demo.py passes the file stamps that traj_kf.txt carries).  consistency: filter_views' options
     (None: the depth maps as they are)."""
-    if consistency is not None:
-        return filter_views(from_keyframes(keyframes, n, stamps), consistency)
     n = int(n)
     if n <= 0:
         raise ValueError("no tracked keyframes")
     kf = keyframes
-    return DepthViews(kf.depth[:n], kf.pose[:n].double().numpy(), kf.intrinsic[:n].double().numpy(),
-                      kf.tstamp[:n].double().numpy() if stamps is None else np.asarray(stamps, np.float64).reshape(-1)[:n], kf.image[:n])
+    stamps = kf.tstamp[:n].double().numpy() if stamps is None else np.asarray(stamps, np.float64).reshape(-1)[:n]
+    return _filtered(DepthViews(kf.depth[:n], kf.pose[:n].double().numpy(), kf.intrinsic[:n].double().numpy(), stamps, kf.image[:n]), consistency)
 
 
 def _mapper_frame_indices(mapper):
@@ -203,16 +183,12 @@ def from_mapper(mapper, stamps=None, consistency=None) -> DepthViews:
     reference's renders_kf/depth_after_opt PNGs).  stamps: one per keyframe in key order; default the keyframes' frame indices.
     consistency: filter_views' options (None: the depth maps as they are)."""
     from .tsdf import render_mapper_views
-    if consistency is not None:
-        return filter_views(from_mapper(mapper, stamps), consistency)
     if not mapper.viewpoints:
         raise ValueError("the mapper has no keyframes")
     if stamps is None:
         stamps = _mapper_frame_indices(mapper)
     depth, rgb, w2c, K = render_mapper_views(mapper)
-    w = np.tile(np.eye(4), (depth.shape[0], 1, 1))
-    w[:, :3] = w2c.double().cpu().numpy().reshape(-1, 3, 4)
-    return DepthViews(depth, np.linalg.inv(w), K.double().cpu().numpy(), np.asarray(stamps, np.float64), rgb)
+    return _filtered(DepthViews(depth, inverse44(pose_matrices(w2c)), K.double().cpu().numpy(), np.asarray(stamps, np.float64), rgb), consistency)
 
 
 def cast_views(volume, views, **cast):
@@ -220,9 +196,8 @@ def cast_views(volume, views, **cast):
     depth maps: world->camera = the fp64 inverse of each c2w.  cast: the options of the volume's ray_cast."""
     depth, poses, K, _, _ = _views(views, "views")
     n, (H, W) = depth.shape[0], depth.shape[1:]
-    K = np.broadcast_to(np.asarray(K.detach().cpu() if isinstance(K, torch.Tensor) else K, np.float64).reshape(-1, 4), (n, 4))
-    w2c = np.linalg.inv(poses)[:, :3].reshape(n, 12).astype(np.float32)
-    return volume.ray_cast(torch.from_numpy(w2c), torch.from_numpy(K.astype(np.float32)), H, W, **cast)
+    w2c = inverse44(poses)[:, :3].reshape(n, 12).astype(np.float32)
+    return volume.ray_cast(torch.from_numpy(w2c), torch.from_numpy(intrinsics(K, n).astype(np.float32)), H, W, **cast)
 
 
 def from_volume(volume, views, **cast) -> DepthViews:
@@ -234,33 +209,24 @@ def from_volume(volume, views, **cast) -> DepthViews:
 
 
 def from_slam(slam, source="auto", stamps_full=None, consistency=None, volume=None, fuse=None) -> DepthViews:
-    """the rule of Cut3rSlam.fuse / --mesh-source: "mapper", "tracker", or "auto" = the mapper when one with keyframes is attached.
+    """the keyframes views.run_views picks for `source` ("mapper", "tracker", "auto"), as Cut3rSlam.fuse / --mesh-source do.
     "fused": the run's TSDF volume ray-cast at each keyframe's pose and intrinsics (from_volume) -- `volume` when given, else
     slam.fuse(**fuse), fuse = its arguments (voxel_size at least); the keyframes are those of fuse's source (default auto).
     stamps_full: the per-frame stamps (stream.frame_timestamps) that map the store's frame indices to the stamps of traj_kf.txt.
     consistency: filter_views' options (None: the depth maps as they are)."""
-    if consistency is not None:
-        return filter_views(from_slam(slam, source, stamps_full, volume=volume, fuse=fuse), consistency)
     if source == "fused":
         fuse = dict(fuse or {})
         if volume is None:
             if "voxel_size" not in fuse:
                 raise ValueError("source='fused' needs a volume, or fuse={'voxel_size': ...} to make one")
             volume = slam.fuse(**fuse)
-        return from_volume(volume, from_slam(slam, fuse.get("source", "auto"), stamps_full))
-    if source not in ("auto", "tracker", "mapper"):
-        raise ValueError(f"source must be auto, tracker, mapper or fused, not {source!r}")
+        return _filtered(from_volume(volume, from_slam(slam, fuse.get("source", "auto"), stamps_full)), consistency)
+    kind, n = run_views(slam, source)
     full = None if stamps_full is None else np.asarray(stamps_full, np.float64).reshape(-1)
     lookup = (lambda idx: None) if full is None else (lambda idx: full[np.asarray(idx, np.float64).astype(int)])
-    has_mapper = slam.mapper is not None and bool(getattr(slam.mapper, "viewpoints", None))
-    if source == "mapper" or (source == "auto" and has_mapper):
-        if not has_mapper:
-            raise ValueError("source='mapper' needs a Gaussian mapper with keyframes")
-        return from_mapper(slam.mapper, lookup(_mapper_frame_indices(slam.mapper)))
-    n = slam.keyframes.counter.value - 1
-    if slam.tracked_only:
-        n = min(n, slam.tracker.t1)
-    return from_keyframes(slam.keyframes, n, lookup(slam.keyframes.tstamp[:max(n, 0)].numpy()))
+    if kind == "mapper":
+        return from_mapper(slam.mapper, lookup(_mapper_frame_indices(slam.mapper)), consistency)
+    return from_keyframes(slam.keyframes, n, lookup(slam.keyframes.tstamp[:max(n, 0)].numpy()), consistency)
 
 
 def read_depth_png(path, scale) -> np.ndarray:

@@ -22,34 +22,30 @@ import os
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, views
 from .eval_ate import load_tum
 from .eval_recon import _gpu_mesh, as_mesh, sample_surface
 from .tsdf import Mesh, write_ply
+from .views import tum_matrices as tum_to_c2w          # [n,4,4] camera-to-world from TUM rows (t x y z qx qy qz qw)
 
 EPS = 0.03                         # metres a vertex may lie behind the rendered surface and still count as seen
 UNSEEN_POINTS = 200000
 STREAM_UNSEEN = 3                  # sample stream of unseen_points (1 and 2 are the metric's two meshes)
 
 
-def _w2c(c2w):
-    return np.linalg.inv(np.asarray(c2w, np.float64).reshape(-1, 4, 4))[:, :3]
-
-
 def render_depth(mesh, c2w, K, H, W, z_near=0.0, z_far=20.0, face_id=False):
     """depth [B,H,W] fp32 on the GPU (0 = nothing hit) of a tsdf.Mesh or PLY path from the cameras c2w [B,4,4] (OpenCV axes), K = fx fy cx
     cy (one row, or one per view); with face_id=True also the int32 index of the face seen (-1 = nothing).  See ops.mesh_raster."""
     v, f = _gpu_mesh(as_mesh(mesh))
-    return ops.mesh_raster(v, f, _w2c(c2w), K, H, W, z_near=z_near, z_far=z_far, face_id=face_id)
+    return ops.mesh_raster(v, f, views.inverse44(c2w)[:, :3], K, H, W, z_near=z_near, z_far=z_far, face_id=face_id)
 
 
 def visible_vertices(mesh, w2c, K, H, W, eps=EPS, z_far=20.0) -> np.ndarray:
     """bool [V]: the vertices seen by one of the cameras w2c [B,3,4] / [B,4,4] (any B: 16 views are rendered and tested per launch, the
     flags OR-ed across the batches)"""
     v, f = _gpu_mesh(as_mesh(mesh))
-    w2c = np.asarray(w2c, np.float64)
-    w2c = w2c.reshape(len(w2c), -1)[:, :12]
-    K = np.array(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 4), (len(w2c), 4)))
+    w2c = views.pose_rows(w2c)
+    K = views.intrinsics(K, len(w2c))
     flags = torch.zeros(v.shape[0], dtype=torch.uint8, device=v.device)
     for b0 in range(0, len(w2c), ops.RASTER_MAX_VIEWS):
         w, k = w2c[b0:b0 + ops.RASTER_MAX_VIEWS], K[b0:b0 + ops.RASTER_MAX_VIEWS]
@@ -89,19 +85,6 @@ def unseen_points(mesh, w2c, K, H, W, count=UNSEEN_POINTS, seed=0, eps=EPS, z_fa
     return sample_surface(rest, count, seed=seed, stream=STREAM_UNSEEN).cpu().numpy()
 
 
-def tum_to_c2w(traj) -> np.ndarray:
-    """[n,4,4] camera-to-world from TUM rows (t x y z qx qy qz qw)"""
-    traj = np.asarray(traj, np.float64).reshape(-1, 8)
-    q = traj[:, 4:8] / np.linalg.norm(traj[:, 4:8], axis=1, keepdims=True)
-    x, y, z, w = q.T
-    M = np.tile(np.eye(4), (len(traj), 1, 1))
-    M[:, 0, :3] = np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)], 1)
-    M[:, 1, :3] = np.stack([2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)], 1)
-    M[:, 2, :3] = np.stack([2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], 1)
-    M[:, :3, 3] = traj[:, 1:4]
-    return M
-
-
 def main(argv=None):
     p = argparse.ArgumentParser(description="what a camera trajectory saw of a mesh (the culling rule is this project's, see the module text)")
     sub = p.add_subparsers(dest="cmd", required=True)
@@ -121,7 +104,7 @@ def main(argv=None):
         p.error("--calib takes four numbers")
     H, W = a.size
     mesh = as_mesh(a.mesh)
-    w2c = _w2c(tum_to_c2w(load_tum(a.traj)))
+    w2c = views.inverse44(tum_to_c2w(load_tum(a.traj)))[:, :3]
     keep = _split(mesh, visible_vertices(mesh, w2c, K, H, W, eps=a.eps, z_far=a.z_far))
     os.makedirs(a.out, exist_ok=True)
     name = os.path.splitext(os.path.basename(a.mesh))[0]

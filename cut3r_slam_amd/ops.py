@@ -11,7 +11,7 @@ from typing import Optional
 
 import torch
 
-from . import _lib
+from . import _lib, views
 from ._lib import GemmDesc, check
 
 F16, F32 = torch.float16, torch.float32
@@ -978,9 +978,8 @@ def _points(t, name):
 def _transform34(T, dev):
     if T is None:
         return None
-    T = torch.as_tensor(T, dtype=torch.float64).reshape(-1)
-    _req(T.numel() in (12, 16), "transform: 3x4 or 4x4")
-    T = T[:12].to(dev, F32).contiguous()
+    T = torch.as_tensor(T, dtype=torch.float64).reshape(1, -1)               # one 3x4 or 4x4 in any shape
+    T = views.pose_rows(T, torch.float64).reshape(12).to(dev, F32).contiguous()
     _req(bool(torch.isfinite(T).all()), "transform: non-finite entries")
     return T
 
@@ -1075,18 +1074,11 @@ RASTER_MAX_VIEWS = 16
 
 
 def _views(w2c, K, dev):
-    """(w2c [B,12] fp32, K [B,4] fp32, B) on `dev` from [B,12] / [B,3,4] / [B,4,4] poses and [B,4] (or one [4]) fx fy cx cy"""
-    w2c = torch.as_tensor(w2c)
-    _req(w2c.dim() in (2, 3) and w2c.shape[0] > 0, "w2c: [B,12], [B,3,4] or [B,4,4]")
+    """(w2c [B,12] fp32, K [B,4] fp32, B) on `dev` from the poses and intrinsics views.pose_rows / views.intrinsics take"""
+    w2c = views.pose_rows(w2c, F32).reshape(-1, 12).to(dev).contiguous()
     B = w2c.shape[0]
-    w2c = w2c.reshape(B, -1)
-    _req(w2c.shape[1] in (12, 16), "w2c: [B,12], [B,3,4] or [B,4,4]")
-    w2c = w2c[:, :12].to(dev, F32).contiguous()
-    K = torch.as_tensor(K).to(dev, F32)
-    if K.dim() == 1:
-        K = K[None].expand(B, -1)
-    _req(K.shape == (B, 4), "K: [B,4] fx fy cx cy")
-    K = K.contiguous()
+    _req(B > 0, "w2c: no poses")
+    K = views.intrinsics(K, B, F32).to(dev)
     _req(bool(torch.isfinite(w2c).all()) and bool(torch.isfinite(K).all()), "w2c / K: non-finite entries")
     _req(bool((K[:, :2] > 0).all()), "K: fx and fy must be > 0")
     return w2c, K, B
@@ -1213,16 +1205,9 @@ def depth_cloud(depth, c2w, K, depth_trunc, size=None, rgb=None):
     _req(max(H * W, H1 * W1) < 2 ** 31 // CLOUD_MAX_VIEWS, "depth_cloud: image too large")
     trunc = float(depth_trunc)
     _req(trunc > 0, "depth_trunc must be > 0")
-    c2w = torch.as_tensor(c2w).detach().to("cpu", torch.float64)
-    _req(c2w.dim() in (2, 3) and c2w.shape[0] == B, "c2w: [B,12], [B,3,4] or [B,4,4]")
-    c2w = c2w.reshape(B, -1)
-    _req(c2w.shape[1] in (12, 16), "c2w: [B,12], [B,3,4] or [B,4,4]")
-    c2w = c2w[:, :12].contiguous()
-    K = torch.as_tensor(K).detach().to("cpu", torch.float64)
-    if K.dim() == 1:
-        K = K[None].expand(B, -1)
-    _req(K.shape == (B, 4), "K: [B,4] or [4] fx fy cx cy")
-    K = K.contiguous()
+    c2w = views.pose_rows(c2w, torch.float64).reshape(-1, 12).cpu().contiguous()
+    _req(c2w.shape[0] == B, f"c2w: {c2w.shape[0]} poses for {B} depth maps")
+    K = views.intrinsics(K, B, torch.float64).cpu()
     _req(bool(torch.isfinite(c2w).all()) and bool(torch.isfinite(K).all()), "c2w / K: non-finite entries")
     _req(bool((K[:, :2] > 0).all()), "K: fx and fy must be > 0")
     if rgb is not None:

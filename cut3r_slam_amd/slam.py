@@ -15,6 +15,7 @@ from .keyframe import KeyFrame
 from .motion_filter import MotionFilter
 from .track_frontend import TrackFrontend
 from .track_backend import TrackBackend
+from .views import run_views
 
 DEFAULT_CONFIG = {
     "Tracking": {
@@ -290,9 +291,7 @@ class Cut3rSlam:
 
     def trajectory(self):
         """(tstamps [t], poses [t,7] c2w (t, q_xyzw)) of the tracked keyframes (demo_s.py:97-100)."""
-        t = self.keyframes.counter.value - 1
-        if self.tracked_only:
-            t = min(t, self.tracker.t1)
+        t = run_views(self, "tracker")[1]
         return self.keyframes.tstamp[:t].numpy().copy(), self.keyframes.pose[:t].numpy().copy()
 
     def fuse(self, voxel_size, depth_max=5.0, trunc_voxels=8.0, source="auto", conf_min=None, bounds=None, max_voxels=2 ** 30,
@@ -303,26 +302,19 @@ class Cut3rSlam:
         mapper when one with keyframes is attached, else the tracker.  consistency: a depth_consistency.ConsistencyOptions, the multi-view
         filter of the depth maps ahead of the fusion (None: the maps as they are)."""
         from . import tsdf
-        extra = {} if consistency is None else {"consistency": consistency}
-        if source not in ("auto", "tracker", "mapper"):
-            raise ValueError(f"source must be auto, tracker or mapper, not {source!r}")
-        has_mapper = self.mapper is not None and bool(getattr(self.mapper, "viewpoints", None))
-        if source == "mapper" or (source == "auto" and has_mapper):
-            if not has_mapper:
-                raise ValueError("source='mapper' needs a Gaussian mapper with keyframes")
-            return tsdf.fuse_mapper(self.mapper, voxel_size, trunc_voxels=trunc_voxels, depth_max=depth_max, bounds=bounds,
-                                    max_voxels=max_voxels, sparse=sparse, **extra)
-        n = self.keyframes.counter.value - 1
-        if self.tracked_only:
-            n = min(n, self.tracker.t1)
-        return tsdf.fuse_keyframes(self.keyframes, n, voxel_size, trunc_voxels=trunc_voxels, depth_max=depth_max, conf_min=conf_min,
-                                   bounds=bounds, max_voxels=max_voxels, sparse=sparse, **extra)
+        kind, n = run_views(self, source)
+        kw = dict(trunc_voxels=trunc_voxels, depth_max=depth_max, bounds=bounds, max_voxels=max_voxels, sparse=sparse)
+        if consistency is not None:                                       # the sources get the keyword only with the filter on
+            kw["consistency"] = consistency
+        if kind == "mapper":
+            return tsdf.fuse_mapper(self.mapper, voxel_size, **kw)
+        return tsdf.fuse_keyframes(self.keyframes, n, voxel_size, conf_min=conf_min, **kw)
 
     def reconstruct(self, voxel_size, depth_max=5.0, trunc_voxels=8.0, weight_threshold=1.0, source="auto", conf_min=None, sparse=False,
                     consistency=None):
         """fuse() then the mesh at `weight_threshold` (tsdf.Mesh: vertices, colors, faces)"""
-        extra = {} if consistency is None else {"consistency": consistency}
-        vol = self.fuse(voxel_size, depth_max=depth_max, trunc_voxels=trunc_voxels, source=source, conf_min=conf_min, sparse=sparse, **extra)
+        vol = self.fuse(voxel_size, depth_max=depth_max, trunc_voxels=trunc_voxels, source=source, conf_min=conf_min, sparse=sparse,
+                        consistency=consistency)
         return vol.extract_mesh(weight_threshold)
 
     def ray_cast(self, volume=None, voxel_size=None, source="auto", **cast):

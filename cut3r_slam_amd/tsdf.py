@@ -25,7 +25,8 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, views
+from .views import inverse_affine as c2w_rows     # camera->world rows fp32 [B,12] of world->camera rows: the mark kernel and the ray cast
 
 DEPTH_SCALE = 6553.5            # tsdf_integrate.py --depth_scale, eval_utils.py:131
 
@@ -51,16 +52,16 @@ def _lattice(lo, hi, voxel_size, pad):
     return lo, [int(math.ceil((h - l) / voxel_size - 1e-6)) + 1 for l, h in zip(lo, hi)]
 
 
-def _views(dev, depth, w2c, K, rgb, conf, conf_min):
+def _stack(dev, depth, w2c, K, rgb, conf, conf_min):
     """the views of integrate() as the kernels take them: depth [B,H,W], w2c [B,12], K [B,4] fp32, rgb u8, conf fp32 or None"""
     depth = torch.as_tensor(depth).to(dev, torch.float32).contiguous()
     if depth.dim() == 2:
         depth = depth[None]
     B = depth.shape[0]
-    w2c = torch.as_tensor(w2c).to(dev, torch.float32)
-    w2c = (w2c.reshape(B, -1, 4)[:, :3] if w2c.shape[-2:] in ((3, 4), (4, 4)) else w2c.reshape(B, 12)).reshape(B, 12).contiguous()
-    K = torch.as_tensor(K).to(dev, torch.float32).reshape(-1, 4)
-    K = (K.expand(B, 4) if K.shape[0] == 1 else K).contiguous()
+    w2c = views.pose_rows(w2c, torch.float32, single=True).reshape(-1, 12).to(dev).contiguous()
+    if w2c.shape[0] != B:
+        raise ValueError(f"{B} depth maps, {w2c.shape[0]} poses")
+    K = views.intrinsics(K, B, torch.float32).to(dev)
     if rgb is not None:
         rgb = torch.as_tensor(rgb).to(dev).contiguous()
     if conf is not None and conf_min is not None:
@@ -91,7 +92,7 @@ class _Volume:
         return cls(origin, voxel_size, dims, trunc_voxels=trunc_voxels, depth_max=depth_max, device=device)
 
     def _integrate(self, depth, w2c, K, rgb, conf, conf_ds, conf_min):
-        """the views (as _views returns them) through _integrate_batch, <= 16 at a time, in order"""
+        """the views (as _stack returns them) through _integrate_batch, <= 16 at a time, in order"""
         for a in range(0, depth.shape[0], ops.TSDF_MAX_VIEWS):
             b = a + ops.TSDF_MAX_VIEWS
             self._integrate_batch(depth[a:b], w2c[a:b], K[a:b], self.trunc, self.depth_max, rgb=None if rgb is None else rgb[a:b],
@@ -111,14 +112,12 @@ class _Volume:
         0, both in cells whose corners all have weight >= weight_threshold.  A ray that meets a negative value first (the camera is
         inside or behind a surface, or the ray comes out of unknown space) misses.  count=True: also the int32 [B,H,W] samples looked
         up per ray, as a fourth value."""
-        w2c = torch.as_tensor(w2c).to(torch.float32)
-        w2c = (w2c.reshape(-1, w2c.shape[-2], 4)[:, :3] if w2c.shape[-2:] in ((3, 4), (4, 4)) else w2c).reshape(-1, 12)
+        w2c = views.pose_rows(w2c, torch.float32, single=True).reshape(-1, 12)
         B = w2c.shape[0]
+        if B < 1:
+            raise ValueError("ray_cast: no poses")
         c2w = torch.from_numpy(c2w_rows(w2c.cpu().numpy())).to(self.device)
-        K = torch.as_tensor(K).to(self.device, torch.float32).reshape(-1, 4)
-        K = (K.expand(B, 4) if K.shape[0] == 1 else K).contiguous()
-        if B < 1 or K.shape[0] != B:
-            raise ValueError(f"ray_cast: {B} poses, {K.shape[0]} intrinsics")
+        K = views.intrinsics(K, B, torch.float32).to(self.device)
         t_max = self.depth_max if depth_max is None else float(depth_max)
         step = float(np.float32(step_voxels * self.voxel_size))
         out = [self._ray_cast_batch(c2w[a:a + ops.TSDF_MAX_VIEWS], K[a:a + ops.TSDF_MAX_VIEWS], int(H), int(W), float(depth_min), t_max, step,
@@ -163,7 +162,7 @@ class TSDFVolume(_Volume):
     def integrate(self, depth, w2c, K, rgb=None, conf=None, conf_ds=1, conf_min=None):
         """fuse B views in order, in launches of <= 16.  depth [B,H,W] metres; w2c [B,12] (or [B,3,4] / [B,4,4]) world->camera; K [4] or
         [B,4] fx fy cx cy; rgb u8 [B,3,H,W]; conf [B,h,w] at stride conf_ds, pixels with conf < conf_min skipped (conf_min None: no gate)."""
-        return self._integrate(*_views(self.device, depth, w2c, K, rgb, conf, conf_min), conf_ds, conf_min)
+        return self._integrate(*_stack(self.device, depth, w2c, K, rgb, conf, conf_min), conf_ds, conf_min)
 
     def _integrate_batch(self, *views, **gate):
         ops.tsdf_integrate(self.tsdf, self.weight, self.color, self.origin, self.voxel_size, *views, **gate)
@@ -173,15 +172,6 @@ class TSDFVolume(_Volume):
 
     def _ray_cast_batch(self, c2w, K, H, W, t_min, t_max, step, **out):
         return ops.tsdf_ray_cast(self.tsdf, self.weight, self.color, self.origin, self.voxel_size, c2w, K, H, W, t_min, t_max, step, **out)
-
-
-def c2w_rows(w2c):
-    """camera->world rows fp32 [B,12] of world->camera rows [B,12]: the inverse of each 3x4 affine map, in float64 on the host (the mark
-    kernel back-projects with them; any invertible w2c will do, a rigid one gives R^T, -R^T t)"""
-    w = np.asarray(w2c, np.float64).reshape(-1, 3, 4)
-    Ri = np.linalg.inv(w[:, :, :3])
-    ti = -(Ri @ w[:, :, 3:])
-    return np.ascontiguousarray(np.concatenate([Ri, ti], 2).reshape(-1, 12), dtype=np.float32)
 
 
 class SparseTSDFVolume(_Volume):
@@ -243,7 +233,7 @@ class SparseTSDFVolume(_Volume):
     def allocate(self, depth, w2c, K):
         """allocate the bricks the views can give a negative tsdf or a neighbour of one; returns how many were added.  Bricks already
         there keep their values; a new brick starts at tsdf = 1, weight = color = 0 and has missed every view integrated so far."""
-        depth, w2c, K, _, _ = _views(self.device, depth, w2c, K, None, None, None)
+        depth, w2c, K, _, _ = _stack(self.device, depth, w2c, K, None, None, None)
         c2w = torch.from_numpy(c2w_rows(w2c.cpu().numpy())).to(self.device)
         ops.tsdf_sparse_mark(self.flags, self.dims, self.origin, self.voxel_size, depth, c2w, K, self.trunc, self.depth_max)
         old = self.bricks
@@ -266,7 +256,7 @@ class SparseTSDFVolume(_Volume):
     def integrate(self, depth, w2c, K, rgb=None, conf=None, conf_ds=1, conf_min=None, allocate=True):
         """TSDFVolume.integrate over the allocated bricks.  allocate=True first allocates for ALL the views given (then fuses them in
         launches of <= 16): right for a fresh volume; on a volume that already holds views, the bricks it adds have missed those."""
-        depth, w2c, K, rgb, conf = _views(self.device, depth, w2c, K, rgb, conf, conf_min)
+        depth, w2c, K, rgb, conf = _stack(self.device, depth, w2c, K, rgb, conf, conf_min)
         if allocate:
             self.allocate(depth, w2c, K)
         if self.n_bricks == 0:
@@ -328,8 +318,9 @@ def shade(normal, w2c):
     """a normal map of the ray cast as an image: normal [B,H,W,3] (world frame) rotated into each camera's frame by w2c [B,12] (or
     [B,3,4] / [B,4,4]) and mapped (n_cam * 0.5 + 0.5) * 255 -> uint8 [B,H,W,3]; black where the normal is 0 (the ray missed)"""
     B = normal.shape[0]
-    w = torch.as_tensor(w2c).to(normal.device, torch.float32)
-    R = (w.reshape(B, -1, 4)[:, :3, :3] if w.shape[-2:] in ((3, 4), (4, 4)) else w.reshape(B, 3, 4)[:, :, :3])
+    R = views.pose_rows(w2c, torch.float32, single=True)[:, :, :3].to(normal.device)
+    if R.shape[0] != B:
+        raise ValueError(f"shade: {B} normal maps, {R.shape[0]} poses")
     n = torch.einsum("bij,bhwj->bhwi", R, normal)
     img = torch.floor((n * 0.5 + 0.5).clamp(0, 1) * 255 + 0.5).to(torch.uint8)
     return img * (normal != 0).any(-1, keepdim=True)
@@ -344,11 +335,9 @@ def write_previews(volume, w2c, K, H, W, outdir, every=1, **cast):
     from PIL import Image
     if int(every) < 1:
         raise ValueError("every must be >= 1")
-    w = torch.as_tensor(w2c).to(torch.float32)
-    w = (w.reshape(-1, w.shape[-2], 4)[:, :3] if w.shape[-2:] in ((3, 4), (4, 4)) else w).reshape(-1, 12)
+    w = views.pose_rows(w2c, torch.float32, single=True).reshape(-1, 12)
     idx = list(range(0, w.shape[0], int(every)))
-    K = torch.as_tensor(K).to(torch.float32).reshape(-1, 4)
-    K = K.expand(w.shape[0], 4) if K.shape[0] == 1 else K
+    K = views.intrinsics(K, w.shape[0], torch.float32)
     rc = volume.ray_cast(w[idx], K[idx], H, W, normals=True, colors=True, **cast)
     raw = torch.floor(torch.clamp(rc.depth * DEPTH_SCALE, 0, 65535)).cpu().numpy().astype(np.uint16)
     nrm = shade(rc.normal, w[idx]).cpu().numpy()
@@ -459,23 +448,17 @@ def depth_bounds(depth, w2c, K, depth_max):
     return lo.cpu().numpy(), hi.cpu().numpy()
 
 
-def _fuse(depth, w2c, K, voxel_size, trunc_voxels, depth_max, bounds, max_voxels, device, sparse, consistency=None, **views):
+def _fuse(depth, w2c, K, voxel_size, trunc_voxels, depth_max, bounds, max_voxels, device, sparse, consistency=None, **maps):
     """the volume over `bounds` (None: the AABB of the valid depths) with all the views fused; sparse: bricks allocated over all views first.
     consistency: a depth_consistency.ConsistencyOptions -- the depth stack is cross-checked between neighbouring views first and the
     rejected pixels are zeroed before the bounds and the integration see them; the volume's `consistency` is then (pixels kept, pixels
-    valid before) as device scalars, None without the filter."""
+    valid before) as device scalars, None without the filter.  maps: rgb and the confidence gate of integrate()."""
     stats = None
     if consistency is not None:
         from . import depth_consistency
         valid = torch.isfinite(depth) & (depth > 0) & (depth <= depth_max)
         depth, keep = depth_consistency.apply(depth, w2c, K, consistency, depth_max)
         stats = (keep.sum(), valid.sum())
-    vol = _fuse_views(depth, w2c, K, voxel_size, trunc_voxels, depth_max, bounds, max_voxels, device, sparse, **views)
-    vol.consistency = stats
-    return vol
-
-
-def _fuse_views(depth, w2c, K, voxel_size, trunc_voxels, depth_max, bounds, max_voxels, device, sparse, **views):
     if bounds is None:
         bounds = depth_bounds(depth, w2c, K, depth_max)
         if bounds is None:
@@ -483,10 +466,13 @@ def _fuse_views(depth, w2c, K, voxel_size, trunc_voxels, depth_max, bounds, max_
     if sparse:                                                       # max_voxels caps the dense grid only
         vol = SparseTSDFVolume.from_bounds(bounds[0], bounds[1], voxel_size, trunc_voxels=trunc_voxels, depth_max=depth_max, device=device)
         vol.allocate(depth, w2c, K)
-        return vol.integrate(depth, w2c, K, allocate=False, **views)
-    vol = TSDFVolume.from_bounds(bounds[0], bounds[1], voxel_size, max_voxels=max_voxels, trunc_voxels=trunc_voxels, depth_max=depth_max,
-                                 device=device)
-    return vol.integrate(depth, w2c, K, **views)
+        maps["allocate"] = False
+    else:
+        vol = TSDFVolume.from_bounds(bounds[0], bounds[1], voxel_size, max_voxels=max_voxels, trunc_voxels=trunc_voxels, depth_max=depth_max,
+                                     device=device)
+    vol.integrate(depth, w2c, K, **maps)
+    vol.consistency = stats
+    return vol
 
 
 @torch.no_grad()

@@ -299,8 +299,7 @@ def main(argv=None):
     if args.mesh:
         from cut3r_slam_amd.tsdf import write_ply
         t_int = time.time()
-        extra = {} if consistency is None else {"consistency": consistency}
-        vol = slam.fuse(args.voxel_size, depth_max=args.depth_max, source=args.mesh_source, sparse=args.mesh_sparse, **extra)
+        vol = slam.fuse(args.voxel_size, depth_max=args.depth_max, source=args.mesh_source, sparse=args.mesh_sparse, consistency=consistency)
         torch.cuda.synchronize()
         t_int = time.time() - t_int
         if consistency is not None:
@@ -316,10 +315,10 @@ def main(argv=None):
         if args.mesh_preview is not None:
             from cut3r_slam_amd import eval_dense as ED
             from cut3r_slam_amd.tsdf import write_previews
-            import numpy as np
+            from cut3r_slam_amd.views import inverse44
             kfs = ED.from_slam(slam, args.mesh_source)
             t_rc = time.time()
-            idx, _ = write_previews(vol, np.linalg.inv(ED.pose_matrices(kfs.c2w))[:, :3], kfs.K, *kfs.depth.shape[1:],
+            idx, _ = write_previews(vol, inverse44(ED.pose_matrices(kfs.c2w))[:, :3], kfs.K, *kfs.depth.shape[1:],
                                     os.path.join(args.output, "tsdf_preview"), every=args.mesh_preview, weight_threshold=args.mesh_weight[0])
             print(f"ray cast of {len(idx)} keyframes (every {args.mesh_preview}) in {1e3 * (time.time() - t_rc):.1f} ms -> "
                   f"{args.output}/tsdf_preview")
