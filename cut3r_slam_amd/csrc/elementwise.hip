@@ -575,6 +575,9 @@ __global__ __launch_bounds__(256) void remap_linear_u8_kernel(const unsigned cha
     }
 }
 
+// base pointers of the 16-byte (fp32 x 4, fp16 x 8) and 8-byte (fp16 x 4) vector accesses: a column-offset view must not reach a kernel
+inline bool misaligned(const void* p, uintptr_t mask) { return ((uintptr_t)p & mask) != 0; }
+
 }  // namespace
 
 extern "C" int cut3r_abi_version(void) { return 1; }
@@ -645,6 +648,9 @@ extern "C" int cut3r_layernorm(const float* x, int ldx, const float* gamma, cons
     if (!y16 && !y32) return CUT3R_ERR_ARG;
     if ((y16 && (ld16 & 3)) || (y32 && (ld32 & 3))) return CUT3R_ERR_ARG;
     if ((mod_scale == nullptr) != (mod_shift == nullptr)) return CUT3R_ERR_ARG;
+    if (misaligned(x, 15) || misaligned(gamma, 15) || misaligned(beta, 15) || misaligned(y32, 15) || misaligned(y16, 7) ||
+        misaligned(mod_scale, 15) || misaligned(mod_shift, 15))
+        return CUT3R_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     dim3 grid((M + 3) / 4), block(256);
     if (C == 768)
@@ -660,13 +666,16 @@ extern "C" int cut3r_layernorm(const float* x, int ldx, const float* gamma, cons
 
 extern "C" int cut3r_layernorm_dual(const float* x, int ldx, const float* g1, const float* b1, void* y1, int ld1, const float* g2,
                                     const float* b2, void* y2, int ld2, float eps, int M, int C, void* stream) {
-    if (!x || !g1 || !b1 || !y1 || !g2 || !b2 || !y2 || M <= 0 || (ldx & 3) || (ld1 & 3) || (ld2 & 3)) return CUT3R_ERR_ARG;
+    if (C != 768 && C != 1024 && C != 1536) return CUT3R_ERR_ARG;      // widths without the fast path: call cut3r_layernorm twice
+    if (!x || !g1 || !b1 || !y1 || !g2 || !b2 || !y2 || M <= 0 || (ldx & 3) || (ld1 & 3) || (ld2 & 3) || !(eps > 0.f)) return CUT3R_ERR_ARG;
+    if (misaligned(x, 15) || misaligned(g1, 15) || misaligned(b1, 15) || misaligned(g2, 15) || misaligned(b2, 15) || misaligned(y1, 7) ||
+        misaligned(y2, 7))
+        return CUT3R_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     dim3 grid((M + 3) / 4), block(256);
     if (C == 768) hipLaunchKernelGGL((layernorm_dual_kernel<3>), grid, block, 0, s, x, ldx, g1, b1, (h16*)y1, ld1, g2, b2, (h16*)y2, ld2, eps, M);
     else if (C == 1024) hipLaunchKernelGGL((layernorm_dual_kernel<4>), grid, block, 0, s, x, ldx, g1, b1, (h16*)y1, ld1, g2, b2, (h16*)y2, ld2, eps, M);
-    else if (C == 1536) hipLaunchKernelGGL((layernorm_dual_kernel<6>), grid, block, 0, s, x, ldx, g1, b1, (h16*)y1, ld1, g2, b2, (h16*)y2, ld2, eps, M);
-    else return CUT3R_ERR_ARG;      // widths without the fast path: call cut3r_layernorm twice
+    else hipLaunchKernelGGL((layernorm_dual_kernel<6>), grid, block, 0, s, x, ldx, g1, b1, (h16*)y1, ld1, g2, b2, (h16*)y2, ld2, eps, M);
     return cut3r_check_launch();
 }
 
@@ -681,7 +690,7 @@ extern "C" int cut3r_im2col_patch(const void* img, int u8, int B, int C, int H, 
 }
 
 extern "C" int cut3r_cast_f32_f16(const float* x, int ldx, void* y, int ldy, int M, int C, void* stream) {
-    if (!x || !y || M <= 0 || C <= 0 || (C & 3) || (ldx & 3) || (ldy & 3)) return CUT3R_ERR_ARG;
+    if (!x || !y || M <= 0 || C <= 0 || (C & 3) || (ldx & 3) || (ldy & 3) || misaligned(x, 15) || misaligned(y, 7)) return CUT3R_ERR_ARG;
     hipLaunchKernelGGL(cast_kernel, dim3(grid_for((size_t)M * (C / 4))), dim3(256), 0, (hipStream_t)stream, x, ldx, (h16*)y, ldy, M, C / 4);
     return cut3r_check_launch();
 }
@@ -700,7 +709,7 @@ extern "C" int cut3r_colmean_batched(const float* x, int B, long long stride_x, 
 }
 
 extern "C" int cut3r_upsample2x_nhwc(const void* in, void* out, int B, int H, int W, int C, void* stream) {
-    if (!in || !out || B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 7)) return CUT3R_ERR_ARG;
+    if (!in || !out || B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 7) || misaligned(in, 15) || misaligned(out, 15)) return CUT3R_ERR_ARG;
     const size_t total = (size_t)B * 2 * H * 2 * W * (C / 8);
     hipLaunchKernelGGL(upsample2x_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const h16*)in, (h16*)out, B, H, W, C / 8);
     return cut3r_check_launch();
@@ -710,6 +719,7 @@ extern "C" int cut3r_dpt_final(const void* in, int P, int Cin, const float* w, c
                                void* stream) {
     if (!in || !w || !b || !pts || P <= 0 || Cin <= 0 || (Cin & 7) || Cin > 2048 || (mode != 0 && mode != 1)) return CUT3R_ERR_ARG;
     if (mode == 0 && !conf) return CUT3R_ERR_ARG;
+    if (misaligned(in, 15)) return CUT3R_ERR_ARG;
     const int lpp = Cin / 8;
     if (lpp <= 64 && 64 % lpp == 0) {      // Cin in {8,16,...,512}: coalesced form
         const int ppw = 64 / lpp;

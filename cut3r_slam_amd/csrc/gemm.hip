@@ -1506,7 +1506,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_skinny_kernel(const GemmArgs g) 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Skinny GEMM (M <= 8 rows): weight-read-bound GEMV.  One wave per output column block, x rows kept in registers.
+// Skinny GEMM (M <= 64 rows, one pass over W per row): weight-read-bound GEMV.  One wave per output column block, x rows kept in registers.
 // Used for the 1-token pose-memory read, pose MLP and adaLN modulation (M = 1).
 __global__ __launch_bounds__(256) void gemv_kernel(const float* __restrict__ X, int ldx, const h16* __restrict__ W, int ldw,
                                                    const float* __restrict__ bias, float* __restrict__ Y, int ldy, int M,
@@ -1618,7 +1618,8 @@ static int fill_args(const cut3r_gemm_desc* d, GemmArgs& g) {
     g.dpt_w = g.dpt_b = nullptr; g.dpt_pts = g.dpt_conf = nullptr; g.dpt_pts_vs = g.dpt_conf_vs = 0;
     if ((d->ln_stats != nullptr) != (d->ln_colsum != nullptr) || (d->stats_out != nullptr) != (d->out16 != nullptr)) return CUT3R_ERR_ARG;
     if (d->ln_stats) {
-        if (!d->bias || d->conv_k == 3 || d->shuf || d->relu_in || batch_of(d) != 1 || d->ln_nslab * 64 != d->K || !(d->ln_eps > 0.f) ||
+        if (!d->bias || d->conv_k == 3 || d->shuf || d->relu_in || batch_of(d) != 1 || d->ln_nslab * 64 != d->K || d->ln_nslab > LN_MAXS ||
+            !(d->ln_eps > 0.f) ||
             ((uintptr_t)d->ln_stats & 7) || ((uintptr_t)d->ln_colsum & 15))
             return CUT3R_ERR_ARG;
     }
@@ -1871,6 +1872,7 @@ extern "C" int cut3r_gemm_f16_pair(const cut3r_gemm_desc* d0, const cut3r_gemm_d
 extern "C" int cut3r_gemv_f16w(const float* X, int ldx, const void* W, int ldw, const float* bias, float* Y, int ldy, int M,
                                int N, int K, int act, const float* res, int ldr, int silu_in, void* stream) {
     if (!X || !W || !Y || M <= 0 || M > 64 || N <= 0 || K <= 0 || (K & 7) || (ldw & 7)) return CUT3R_ERR_ARG;
+    if ((act != 0 && act != 1) || ((uintptr_t)W & 15)) return CUT3R_ERR_ARG;      // GELU or nothing; 16-byte loads of W
     hipLaunchKernelGGL(gemv_kernel, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream, X, ldx, (const h16*)W, ldw, bias, Y, ldy,
                        M, N, K, act, res, ldr, silu_in);
     return cut3r_check_launch();

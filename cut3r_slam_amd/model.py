@@ -193,8 +193,8 @@ class Cut3rModel:
         def fold(name, w, b, norm):
             """LayerNorm `norm` folded into the Linear (w, b) that consumes it: y = LN(x) W^T + b = rstd (x (gamma.W)^T - mu c) + d with the
             panel fp16(gamma . W), c_n = the row sums of THAT panel (so the constant part cancels exactly) and d = W beta + b"""
-            if not self.ln_fold or w.shape[1] % 64 or w.shape[0] % 4:
-                return
+            if not self.ln_fold or w.shape[1] % 64 or w.shape[0] % 4 or w.shape[1] > ops.LN_FOLD_MAX_K:
+                return              # wider rows than the folded epilogue normalises keep their LayerNorm launch
             gam, bet = sd[norm + ".weight"].double(), sd[norm + ".bias"].double()
             wd = w.double()
             L = _Lin((wd * gam[None, :]).float(), None, dev)

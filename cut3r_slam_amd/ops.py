@@ -30,6 +30,14 @@ def _req(cond, msg):
         raise ValueError(msg)
 
 
+def _aligned(nbytes, **ts):
+    """the base address of every tensor given by name is a multiple of nbytes: the kernels read and write 8- / 16-byte vectors, and a view
+    that starts at a column offset (big[:, 2:]) keeps an aligned row stride but not an aligned first element"""
+    for name, t in ts.items():
+        if t is not None:
+            _req(t.data_ptr() % nbytes == 0, f"{name} must start on a {nbytes}-byte boundary (a column-offset view?): address % {nbytes} = {t.data_ptr() % nbytes}")
+
+
 def _cuda(*ts):
     for t in ts:
         if t is not None:
@@ -140,6 +148,8 @@ def layernorm(x, gamma, beta, eps=1e-6, out16=None, out32=None, mod_scale=None, 
     for m in (mod_scale, mod_shift):
         if m is not None:
             _req(m.dtype == F32 and m.numel() == Cc and m.is_contiguous(), "modulation vectors must be fp32 [C]")
+    _aligned(16, x=x, gamma=gamma, beta=beta, out32=out32, mod_scale=mod_scale, mod_shift=mod_shift)
+    _aligned(8, out16=out16)
     lib = _lib.load()
     check(lib.cut3r_layernorm(_p(x), x.stride(0), _p(gamma), _p(beta), float(eps), M, Cc,
                               _p(out16), out16.stride(0) if out16 is not None else 0,
@@ -156,12 +166,16 @@ def layernorm_dual(x, g1, b1, out1, g2, b2, out2, eps=1e-6):
         _req(o.dtype == F16 and o.shape == (M, Cc) and o.stride(1) == 1, "outputs fp16 [M,C]")
     for t in (g1, b1, g2, b2):
         _req(t.dtype == F32 and t.numel() == Cc and t.is_contiguous(), "gamma/beta fp32 [C]")
+    _req(float(eps) > 0.0, f"layernorm_dual: eps must be > 0, got {eps}")
+    _aligned(16, x=x, g1=g1, b1=b1, g2=g2, b2=b2)
+    _aligned(8, out1=out1, out2=out2)
     lib = _lib.load()
     check(lib.cut3r_layernorm_dual(_p(x), x.stride(0), _p(g1), _p(b1), _p(out1), out1.stride(0), _p(g2), _p(b2), _p(out2), out2.stride(0),
                                    float(eps), M, Cc, _stream()), "cut3r_layernorm_dual")
 
 
 # ------------------------------------------------------------------------------------------------ GEMM
+LN_FOLD_MAX_K = 1024        # the folded epilogue reads at most 16 slabs of 64 columns per row (LN_MAXS in csrc/gemm.hip)
 GEMM_STAGES = int(os.environ.get("CUT3R_GEMM_STAGES", "0"))     # tuning override (0 = kernel default)
 
 
@@ -229,6 +243,7 @@ def _linear_desc(A, W, out, bias, act, res1, tile, rope=None, ln=None, emit=None
     if ln is not None:
         st, cs, eps = ln
         _cuda(st, cs)
+        _req(K <= LN_FOLD_MAX_K, f"LayerNorm fold: K = {K} > {LN_FOLD_MAX_K}, the widest row the folded epilogue normalises (run ops.layernorm in front instead)")
         _req(K % 64 == 0 and st.dtype == F32 and st.is_contiguous() and st.numel() == M * (K // 64) * 2, f"ln stats fp32 [K/64={K // 64}, M={M}, 2]")
         _req(cs.dtype == F32 and cs.is_contiguous() and cs.numel() == N and bias is not None and tile != 16, "ln colsum fp32 [N], folded bias required")
         d.ln_stats, d.ln_colsum, d.ln_nslab, d.ln_eps = st.data_ptr(), cs.data_ptr(), K // 64, float(eps)
@@ -349,6 +364,9 @@ def gemv(X, W, out, bias=None, act=0, res=None, silu_in=False):
         _req(bias.dtype == F32 and bias.numel() == N, "bias")
     if res is not None:
         _req(res.dtype == F32 and res.shape == (M, N) and res.stride(1) == 1, "res")
+    _req(act in (0, 1), f"gemv: act must be 0 (none) or 1 (GELU), got {act} (the kernel has no ReLU)")
+    _req(M <= 64 and K % 8 == 0 and W.stride(0) % 8 == 0, "gemv: M <= 64, K and the row stride of W multiples of 8")
+    _aligned(16, W=W)
     lib = _lib.load()
     check(lib.cut3r_gemv_f16w(_p(X), X.stride(0), _p(W), W.stride(0), _p(bias), _p(out), out.stride(0), M, N, K, act,
                               _p(res), res.stride(0) if res is not None else 0, int(silu_in), _stream()), "cut3r_gemv_f16w")
@@ -393,6 +411,8 @@ def cast_f16(x, out):
     _cuda(x, out)
     _req(x.dtype == F32 and out.dtype == F16 and x.shape == out.shape and x.dim() == 2, "cast: 2-D fp32 -> fp16")
     _req(x.stride(1) == 1 and out.stride(1) == 1, "unit inner stride")
+    _aligned(16, x=x)
+    _aligned(8, out=out)
     lib = _lib.load()
     check(lib.cut3r_cast_f32_f16(_p(x), x.stride(0), _p(out), out.stride(0), x.shape[0], x.shape[1], _stream()), "cut3r_cast_f32_f16")
     return out
@@ -421,6 +441,7 @@ def upsample2x(x, out):
     _cuda(x, out)
     B, H, W, Cc = x.shape
     _req(x.dtype == F16 and x.is_contiguous() and out.dtype == F16 and out.is_contiguous() and out.shape == (B, 2 * H, 2 * W, Cc), "upsample2x")
+    _aligned(16, x=x, out=out)
     lib = _lib.load()
     check(lib.cut3r_upsample2x_nhwc(_p(x), _p(out), B, H, W, Cc, _stream()), "cut3r_upsample2x_nhwc")
     return out
@@ -434,6 +455,7 @@ def dpt_final(x, w, b, mode, pts, conf=None):
     _req(b.dtype == F32 and b.numel() == nout and pts.dtype == F32 and pts.numel() == 3 * P and pts.is_contiguous(), "dpt_final b/pts")
     if mode == 0:
         _req(conf is not None and conf.dtype == F32 and conf.numel() == P and conf.is_contiguous(), "conf")
+    _aligned(16, x=x)
     lib = _lib.load()
     check(lib.cut3r_dpt_final(_p(x), P, Cin, _p(w), _p(b), mode, _p(pts), _p(conf), _stream()), "cut3r_dpt_final")
 

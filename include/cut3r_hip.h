@@ -40,7 +40,8 @@ int cut3r_rope2d_tab(void* t0, const int64_t* pos0, long long ntok0, long long s
 /* ---- LayerNorm (+adaLN modulation) -------------------------------------------------------------------------
  * replaces nn.LayerNorm(eps=1e-6) calls in croco/models/blocks.py:187-190, dust3r/blocks.py:292-297 and
  * ModLN (dust3r/blocks.py:356-379: y = LN(x)*(1+scale)+shift).  x fp32 [M,C] (row stride ldx).  Writes any of:
- * y16 (fp16, ld16) and y32 (fp32, ld32).  mod_scale/mod_shift: optional fp32 [C] (NULL = plain LN). */
+ * y16 (fp16, ld16) and y32 (fp32, ld32).  mod_scale/mod_shift: optional fp32 [C] (NULL = plain LN).
+ * Every fp32 pointer 16-byte aligned, y16 8-byte aligned, every row stride a multiple of 4 (vector accesses). */
 int cut3r_layernorm(const float* x, int ldx, const float* gamma, const float* beta, float eps, int M, int C,
                     void* y16, int ld16, float* y32, int ld32, const float* mod_scale, const float* mod_shift,
                     void* stream);
@@ -84,8 +85,8 @@ typedef struct cut3r_gemm_desc {
      * croco/models/blocks.py:187-190, dust3r/blocks.py:292-297).  y = LN(x) W^T + b = rstd (x (gamma.W)^T - mu c) + d.
      * CONSUMER: A = fp16 copy of the UN-normalised rows x, B = fp16(gamma . W), bias = d = W beta + b, ln_colsum = c
      * (c_n = sum_k B_nk, fp32 [N]), ln_stats = fp32 [K/64][M][2] (slab-major): (sum, m2 = sum (x - sum/64)^2) of every 64-column
-     * slab of every row, ln_nslab = K/64, ln_eps = the LayerNorm's eps.  The row's slabs are combined in slab order (parallel
-     * variance), the raw accumulator becomes acc*rstd - (rstd*mu)*c_n, then the usual epilogue runs (bias, GELU, RoPE, fp16).
+     * slab of every row, ln_nslab = K/64 <= 16 (K <= 1024; wider rows are a bad argument), ln_eps = the LayerNorm's eps.
+     * The row's slabs are combined in slab order (parallel variance), the raw accumulator becomes acc*rstd - (rstd*mu)*c_n, then the usual epilogue runs (bias, GELU, RoPE, fp16).
      * PRODUCER: an fp32-output GEMM with an fp32 residual (the one that writes the residual stream) also stores out16 = fp16
      * copy of its output rows (ld16) and stats_out = their slab statistics, fp32 [N/64][M][2] (N % 64 == 0), computed in one
      * fixed order in every tile kernel.  Tiles 256 / 128 / 64 (producer), + 128 x 192 (consumer); not the skinny tile. */
@@ -114,7 +115,8 @@ int cut3r_gemm_tile_for(const cut3r_gemm_desc* d);
  * carry the fused RoPE and both sides of the LayerNorm fold, each problem with its own flags. */
 int cut3r_gemm_f16_pair(const cut3r_gemm_desc* d0, const cut3r_gemm_desc* d1, void* stream);
 
-/* skinny M<=64 path: Y[M,N] = act(X[M,K] (fp32, optional SiLU on load) * W[N,K]^T (fp16) + bias) (+res) */
+/* skinny M<=64 path: Y[M,N] = act(X[M,K] (fp32, optional SiLU on load) * W[N,K]^T (fp16) + bias) (+res).
+ * act: 0 none or 1 exact GELU (anything else, ReLU's 2 included, is a bad argument); W 16-byte aligned, ldw % 8 == 0. */
 int cut3r_gemv_f16w(const float* X, int ldx, const void* W, int ldw, const float* bias, float* Y, int ldy,
                     int M, int N, int K, int act, const float* res, int ldr, int silu_in, void* stream);
 

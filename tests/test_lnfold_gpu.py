@@ -150,5 +150,8 @@ def test_fold_arguments_are_checked():
         ops.linear(x16[:32], Wf.to(DEV), out[:32], d.to(DEV), tile=16, ln=(st[:, :32].contiguous(), c.to(DEV), EPS))
     with pytest.raises(Exception):          # statistics of the wrong width
         ops.linear(x16, Wf.to(DEV), out, d.to(DEV), ln=(st[:2].contiguous(), c.to(DEV), EPS))
+    with pytest.raises(Exception):          # K = 1088: 17 slabs, one more than the folded epilogue reads (ops.LN_FOLD_MAX_K)
+        ops.linear(torch.zeros(130, 1088, dtype=F16, device=DEV), torch.zeros(128, 1088, dtype=F16, device=DEV), out, d.to(DEV),
+                   ln=(torch.ones(17, 130, 2, device=DEV), c.to(DEV), EPS))
     with pytest.raises(Exception):          # producer side needs an fp32 output with an fp32 residual
         ops.linear(x16, Wf.to(DEV), out, d.to(DEV), emit=(torch.empty(2, 130, 2, device=DEV), torch.empty(130, 128, dtype=F16, device=DEV)))
