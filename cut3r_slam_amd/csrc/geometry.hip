@@ -53,7 +53,6 @@ DEVINL int proj_valid(const float* __restrict__ m, float x, float y, float z, co
 // forward test: ONE pointmap, B cameras.  Each thread keeps one point in registers and sweeps all cameras (the
 // 3x4 matrices are wave-uniform -> scalar loads), so the pointmap is read from HBM exactly once.  Per-camera counts
 // are accumulated in LDS (wave popcount of the ballot) and flushed with one global atomic per (block, camera).
-constexpr int OVL_MAXB = 2048;
 struct AlignArgs { float P[12]; float s; };
 
 #ifndef CUT3R_FWD_PPT
@@ -453,6 +452,8 @@ extern "C" int cut3r_window_update(const float* pts, const float* conf, int V, i
     if (V < 1 || V > 6 || H <= 0 || W <= 0 || ds <= 0 || t0 < 0 || ldc < t0 + V || grp < 0 || (grp > 0 && grp_stride < grp)) return CUT3R_ERR_ARG;
     const int Nd = (H / ds) * (W / ds);
     if (((uintptr_t)store & 15) || (((size_t)Nd * 12) & 15)) return CUT3R_ERR_ARG;
+    const int last = t0 + V - 1;                  // newest keyframe: it sees cameras / pointmaps 0..last-1
+    if (last > 65535) return CUT3R_ERR_ARG;       // win_bwd_kernel's grid.y = last; refused before anything is launched
     WinArgs wa;
     for (int v = 0; v < V; v++)
         for (int i = 0; i < 12; i++) wa.P[v][i] = P_host[v * 12 + i];
@@ -462,7 +463,6 @@ extern "C" int cut3r_window_update(const float* pts, const float* conf, int V, i
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(win_align_kernel, dim3(grid_for((size_t)H * W), V), dim3(256), 0, st, pts, conf, H, W, wa, ds, pm_ds, conf_ds, depth,
                        w2c, counts, ldc, lsum_reset);
-    const int last = t0 + V - 1;                  // newest keyframe: it sees cameras / pointmaps 0..last-1
     if (last >= first && last >= 1) {
         const Cam camf = make_cam(fx, fy, cx, cy, W, H);
         hipLaunchKernelGGL(win_fwd_kernel, dim3((H * W + 256 * FWD_PPT - 1) / (256 * FWD_PPT), V, (last + CAM_CHUNK - 1) / CAM_CHUNK), dim3(256), 0, st, pts, H * W, w2c, camf, counts, ldc, wa);
@@ -472,7 +472,6 @@ extern "C" int cut3r_window_update(const float* pts, const float* conf, int V, i
         int gx = ((Nd >> 2) + 255) / 256;
         if (gx < 1) gx = 1;
         if (gx > 64) gx = 64;
-        if (last > 65535) return CUT3R_ERR_ARG;
         hipLaunchKernelGGL(win_bwd_kernel, dim3(gx, last), dim3(256), 0, st, store, Nd, grp, grp_stride, w2c, camb, counts, ldc, wa);
     }
     return cut3r_check_launch();
@@ -499,6 +498,7 @@ extern "C" int cut3r_logdepth_accum(const float* prev_depth, const float* pts, i
 extern "C" int cut3r_patch_overlap(const float* feat0, const float* feat1, int N, int C, float thr, void* ws, int32_t* count,
                                    void* stream) {
     if (!feat0 || !feat1 || !ws || !count || N < 2 || C <= 0 || (C & 7)) return CUT3R_ERR_ARG;
+    if (!(thr >= 0.f)) return CUT3R_ERR_ARG;      // the clamp at 0 and the atomicMax on float bits hold for a non-negative threshold only
     if (((uintptr_t)feat0 | (uintptr_t)feat1 | (uintptr_t)ws) & 15) return CUT3R_ERR_ARG;
     const int Nv = N - 1;
     hipStream_t s = (hipStream_t)stream;
@@ -519,6 +519,7 @@ extern "C" int cut3r_patch_overlap_chain(const float* feat_last, const float* fe
                                          const int32_t* forced_host, void* ws, int32_t* state, int32_t* counts, int32_t* decisions,
                                          void* stream) {
     if (!feat_last || !feats || !ws || !state || !counts || !decisions || B < 1 || N < 2 || C <= 0 || (C & 7)) return CUT3R_ERR_ARG;
+    if (!(thr_sim >= 0.f)) return CUT3R_ERR_ARG;  // as cut3r_patch_overlap
     if (((uintptr_t)feat_last | (uintptr_t)feats | (uintptr_t)ws) & 15) return CUT3R_ERR_ARG;
     const int Nv = N - 1;
     hipStream_t s = (hipStream_t)stream;

@@ -516,6 +516,7 @@ def patch_overlap_count(feat0, feat1, thr, ws, count):
     N, Cc = feat0.shape
     _req(feat0.dtype == F32 and feat1.dtype == F32 and feat1.shape == (N, Cc) and feat0.is_contiguous() and feat1.is_contiguous(), "features fp32 [N,C]")
     _req(ws.dtype == F32 and ws.numel() >= 2 * (N - 1) * Cc + (N - 1) and count.dtype == torch.int32, "workspace/count")
+    _req(float(thr) >= 0.0, "similarity threshold >= 0 (the row maxima are clamped at 0)")
     lib = _lib.load()
     check(lib.cut3r_patch_overlap(_p(feat0), _p(feat1), N, Cc, float(thr), _p(ws), _p(count), _stream()), "cut3r_patch_overlap")
 
@@ -531,6 +532,7 @@ def patch_overlap_chain(feat_last, feats, thr_sim, thr_ratio, forced, ws, state,
     _req(ws.dtype == F32 and ws.numel() >= (B + 1) * (N - 1) * Cc + (N - 1), "workspace of (B+1)*(N-1)*C + N-1 floats")
     _req(state.dtype == torch.int32 and counts.dtype == torch.int32 and decisions.dtype == torch.int32 and counts.numel() >= B and decisions.numel() >= B,
          "state / counts / decisions int32")
+    _req(float(thr_sim) >= 0.0, "similarity threshold >= 0 (the row maxima are clamped at 0)")
     arr = (C.c_int32 * B)(*[1 if f else 0 for f in forced]) if forced is not None else None
     lib = _lib.load()
     check(lib.cut3r_patch_overlap_chain(_p(feat_last), _p(feats), B, N, Cc, float(thr_sim), float(thr_ratio), arr, _p(ws), _p(state), _p(counts),

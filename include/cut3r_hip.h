@@ -177,7 +177,11 @@ int cut3r_postprocess_pose(const float* raw, int B, float* out, void* stream);
 /* ---- keyframe selection ---------------------------------------------------------------------------------------------
  * replaces compute_patch_overlap_ratio (hislam2/util/utils.py:726-736): rows 1.. of feat0/feat1 fp32 [N,C] are
  * L2-normalised, sim = f0 f1^T (exact fp32 MFMA), count = #rows with max_j sim > thr.  count: int32[1] (device),
- * zeroed by the call.  ws: 16-B aligned fp32 workspace of 2*(N-1)*C + (N-1) elements. */
+ * zeroed by the call.  ws: 16-B aligned fp32 workspace of 2*(N-1)*C + (N-1) elements.  After the call it holds, in this
+ * order: n0 fp32 [N-1][C], the normalised rows 1.. of feat0 (x / max(||x||, 1e-12)); n1 fp32 [N-1][C], the same of feat1;
+ * rmax [N-1], the bit patterns of the fp32 row maxima max(0, max_j n0[r] . n1[j]).  The clamp at 0 and the unsigned maximum
+ * on those bits are valid for thr >= 0 only: a negative or NaN thr is refused.  (cut3r_patch_overlap_chain keeps B+1
+ * normalised sets [B+1][N-1][C] -- feat_last, then the candidates -- followed by the same [N-1] maxima, left cleared.) */
 int cut3r_patch_overlap(const float* feat0, const float* feat1, int N, int C, float thr, void* ws, int32_t* count,
                         void* stream);
 /* The keyframe decisions of a whole look-ahead batch with no host round trip per candidate: replaces the decision loop of
@@ -217,7 +221,8 @@ int cut3r_overlap_bwd(const float* pms, int B, int N, int grp, int grp_stride, c
  * t0+V), zeroed here.  w2c_new_host (optional, V*12 HOST floats): rows t0..t0+V-1 of w2c are written from it first (the
  * keyframe store's device mirror, hislam2/keyframe.py:24 pose) -- no separate upload.  lsum_reset (optional): a
  * cut3r_logdepth_accum accumulator zeroed for the next window.  Three launches instead of ~6 per keyframe; every count
- * equals the per-keyframe entry points'. */
+ * equals the per-keyframe entry points'.  t0+V-1 <= 65535 (a grid dimension); like every other argument error this one is
+ * returned before anything is launched. */
 int cut3r_window_update(const float* pts, const float* conf, int V, int H, int W, const float* P_host, float s, int ds,
                         float* pm_ds, float* conf_ds, float* depth, const float* store, int grp, int grp_stride,
                         float* w2c, const float* w2c_new_host, int t0, int first, float fx, float fy, float cx, float cy,
