@@ -1149,11 +1149,11 @@ extern "C" int cut3r_gs_preprocess(int P, const float* means, const float* scale
     const int rc = gs_fill_cam(cam, viewmatrix_host, projmatrix_host, campos_host, W, H, tanfovx, tanfovy, kernel_size, scale_modifier, sh_degree,
                                sh_coeffs);
     if (rc != CUT3R_OK) return rc;
+    // (no size query here: the caller sized scan_ws with cut3r_gs_workspace_bytes; the library call refuses a buffer that is too small)
+    if (!scan_ws || scan_ws_bytes <= 0) return CUT3R_ERR_ARG;                  // refused before the first write
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(gs_preprocess_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, means, scales, rots, opacities, shs, colors_precomp, cam, geom,
                        radii, tiles_touched);
-    // (no size query here: the caller sized scan_ws with cut3r_gs_workspace_bytes; the library call refuses a buffer that is too small)
-    if (!scan_ws || scan_ws_bytes <= 0) return CUT3R_ERR_ARG;
     size_t need = (size_t)scan_ws_bytes;
     if (hipcub::DeviceScan::InclusiveSum(scan_ws, need, tiles_touched, offsets, P, s) != hipSuccess) return CUT3R_ERR_ARG;
     return cut3r_check_launch();
@@ -1172,19 +1172,19 @@ extern "C" int cut3r_gs_bin(int P, const float* geom, const unsigned* offsets, l
                             unsigned* vals_tmp, unsigned long long* keys_sorted, unsigned* point_list, unsigned* ranges, void* sort_ws,
                             long long sort_ws_bytes, int* overflow, void* stream) {
     if (P <= 0 || !geom || !offsets || W <= 0 || H <= 0 || !ranges || n_instances < 0 || n_instances > 0x7fffffffLL) return CUT3R_ERR_ARG;
+    // (without instances no buffer is needed; with instances a missing one is refused before `ranges` is cleared)
+    if (n_instances > 0 && (!keys_tmp || !vals_tmp || !keys_sorted || !point_list || !sort_ws || sort_ws_bytes <= 0)) return CUT3R_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     const int gx = (W + GS_TILE - 1) / GS_TILE, gy = (H + GS_TILE - 1) / GS_TILE;
     if (hipMemsetAsync(ranges, 0, sizeof(unsigned) * 2 * (size_t)gx * gy, s) != hipSuccess) return CUT3R_ERR_LAUNCH;
     if (n_instances == 0) return CUT3R_OK;
-    if (!keys_tmp || !vals_tmp || !keys_sorted || !point_list || !sort_ws) return CUT3R_ERR_ARG;
-    if (overflow)      // capacity mode: n_instances is a guess made without reading the count back; unused entries sort behind every tile
+    if (overflow)     // capacity mode: n_instances is a guess made without reading the count back; unused entries sort behind every tile
         hipLaunchKernelGGL(gs_pad_keys_kernel, dim3((unsigned)((n_instances + 255) / 256)), dim3(256), 0, s, (unsigned long long)n_instances,
                            (unsigned long long)(gx * gy) << 32, keys_tmp, vals_tmp);
     hipLaunchKernelGGL(gs_duplicate_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, geom, offsets, gx, (unsigned long long)n_instances, keys_tmp,
                        vals_tmp, overflow);
     int bits = 32;                                                             // tile id bits above the 32 depth bits
     for (int t = gx * gy; t > 0; t >>= 1) bits++;
-    if (sort_ws_bytes <= 0) return CUT3R_ERR_ARG;
     size_t need = (size_t)sort_ws_bytes;
     if (hipcub::DeviceRadixSort::SortPairs(sort_ws, need, keys_tmp, keys_sorted, vals_tmp, point_list, (int)n_instances, 0, bits, s) != hipSuccess)
         return CUT3R_ERR_ARG;
@@ -1353,7 +1353,7 @@ extern "C" int cut3r_pixel_loss_backward(const float* img, const float* gt_img, 
 
 extern "C" int cut3r_normal_agree_forward(const float* normal, const float* depth, int H, int W, float fx, float fy, float cx, float cy,
                                           float* sum, void* stream) {
-    if (!normal || !depth || !sum || H < 3 || W < 3) return CUT3R_ERR_ARG;
+    if (!normal || !depth || !sum || H <= 0 || W <= 0) return CUT3R_ERR_ARG;                 // (H or W < 3: no interior pixel, the sum is H W)
     hipStream_t s = (hipStream_t)stream;
     if (hipMemsetAsync(sum, 0, sizeof(float), s) != hipSuccess) return CUT3R_ERR_LAUNCH;
     hipLaunchKernelGGL(normal_agree_fwd_kernel, dim3((H * W + 255) / 256), dim3(256), 0, s, normal, depth, H, W, PixCam{fx, fy, cx, cy}, sum);
@@ -1362,7 +1362,7 @@ extern "C" int cut3r_normal_agree_forward(const float* normal, const float* dept
 
 extern "C" int cut3r_normal_agree_backward(const float* normal, const float* depth, int H, int W, float fx, float fy, float cx, float cy,
                                            float coef, float* grad_normal, float* grad_depth, void* stream) {
-    if (!normal || !depth || !grad_normal || !grad_depth || H < 3 || W < 3) return CUT3R_ERR_ARG;
+    if (!normal || !depth || !grad_normal || !grad_depth || H <= 0 || W <= 0) return CUT3R_ERR_ARG;
     hipLaunchKernelGGL(normal_agree_bwd_kernel, dim3((H * W + 255) / 256), dim3(256), 0, (hipStream_t)stream, normal, depth, H, W,
                        PixCam{fx, fy, cx, cy}, coef, grad_normal, grad_depth);
     return cut3r_check_launch();

@@ -407,7 +407,9 @@ int cut3r_remap_linear_u8(const void* src, int H, int W, int C, const int32_t* m
  *               that must not stop the host, e.g. inside a captured graph): n_instances is a capacity, unused entries are padded
  *               behind the last tile, *overflow is set to 1 on the device if the scene needed more.
  *   render:     forward.cu:429-692.  color/coord/mcoord/normal [3,H,W]; depth/mdepth/alpha [1,H,W]; n_contrib uint32 [2,H,W];
- *               aux float [2,H,W] (final transmittance, normal length: kept for the backward pass). */
+ *               aux float [2,H,W] (final transmittance, normal length: kept for the backward pass).
+ *   A refused call (CUT3R_ERR_ARG: a missing pointer or workspace, P <= 0, sh_degree outside 0..3, sh_coeffs < (sh_degree + 1)^2,
+ *   non-positive W, H or tanfov) writes nothing: every argument is checked before the first write. */
 int cut3r_gs_preprocess(int P, const float* means, const float* scales, const float* rots, const float* opacities, const float* shs,
                         int sh_degree, int sh_coeffs, const float* colors_precomp, const float* viewmatrix_host, const float* projmatrix_host,
                         const float* campos_host, int W, int H, float tanfovx, float tanfovy, float kernel_size, float scale_modifier, float* geom,
@@ -533,7 +535,8 @@ int cut3r_pixel_loss_backward(const float* img, const float* gt_img, const float
 /* global_BA's rendered-normal term (hislam2/gs_backend_per_frame.py:996-1001): mean over ALL pixels of 1 - N . n(depth), N the rendered
  * normal image [3,H,W], n(depth) the camera-frame normal of the rendered depth [H,W] (central differences of the back-projected
  * neighbours, zero on the border).  forward: sum[0] (device) = the pixel sum.  backward: coef = upstream gradient * weight / (H W);
- * grad_normal [3,H,W] is written, grad_depth [H,W] is ACCUMULATED into (after cut3r_pixel_loss_backward wrote it). */
+ * grad_normal [3,H,W] is written, grad_depth [H,W] is ACCUMULATED into (after cut3r_pixel_loss_backward wrote it).  An image without
+ * interior pixels (H < 3 or W < 3) is accepted: its sum is H W, grad_normal 0 and grad_depth unchanged. */
 int cut3r_normal_agree_forward(const float* normal, const float* depth, int H, int W, float fx, float fy, float cx, float cy, float* sum,
                                void* stream);
 int cut3r_normal_agree_backward(const float* normal, const float* depth, int H, int W, float fx, float fy, float cx, float cy, float coef,
