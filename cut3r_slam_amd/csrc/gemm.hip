@@ -1544,8 +1544,36 @@ __global__ __launch_bounds__(256) void gemv_kernel(const float* __restrict__ X, 
 // kernel's address, the grid and the workgroup size, and the fields of GemmArgs that dispatch decides: swz, prio, nblk0) and makes ONE launch.
 typedef void (*TileFn)(GemmArgs);
 typedef void (*PairFn)(GemmPairArgs);
-template <class Fn> struct Kern { Fn fn; unsigned block; };                   // a kernel instance and its workgroup size
+template <class Fn> struct Kern { Fn fn; unsigned block; int code; };        // a kernel instance, its workgroup size and its code (below)
 template <class Fn> struct Plan { Kern<Fn> k; dim3 grid; };
+
+// ---- instance codes (cut3r_gemm_kernel_for; the scheme is documented in include/cut3r_hip.h): six decimal digits, the first the family, the
+// others the template arguments, so two instances never share a code.  A selector names an instance through tk / pk / k256 / sk, which tie the
+// code to the kernel's address and register the instance once (a static data member per code, initialised when the library is loaded):
+// cut3r_gemm_kernel_count is the number of instances the selectors name, and no list of them exists anywhere else.
+// RING: 0 = launched whatever CUT3R_GEMM64_STAGES says; 3 | 4 | 6 = launched only at that ring depth of the default 64 x 64 kernels (ring64).
+static int g_ninst[7];
+template <int CODE, int RING> struct Inst { static const int seen; };
+template <int CODE, int RING> const int Inst<CODE, RING>::seen = ++g_ninst[RING];
+template <int CODE, int RING> static int registered() { return (void)&Inst<CODE, RING>::seen, CODE; }
+constexpr int tile_code(int family, int BM, int BN, int NS, int WM, int WN, int ADDR, int EPI) {
+    const int t = BM == 64 ? 1 : BM == 256 ? 5 : BM == 192 ? 4 : BN == 192 ? 3 : BN == 64 ? 6 : 2;      // 64^2, 128^2, 128x192, 192x128, 256x128, 128x64
+    const int w = WN == 4 ? 2 : WM == 4 ? 3 : 1;                                                       // waves 2 x 2, 2 x 4, 4 x 2
+    return family * 100000 + t * 10000 + NS * 1000 + w * 100 + ADDR * 10 + EPI;
+}
+template <int RING, int BM, int BN, int NS, int WM = 2, int WN = 2, int ADDR = 0, int EPI = 0>
+static Kern<TileFn> tk() { return {gemm_kernel<BM, BN, NS, WM, WN, ADDR, EPI>, 64u * WM * WN, registered<tile_code(1, BM, BN, NS, WM, WN, ADDR, EPI), RING>()}; }
+template <int BM, int BN, int NS, int WM = 2, int WN = 2, int ADDR = 0, int EPI = 0>
+static Kern<PairFn> pk() { return {gemm_pair_kernel<BM, BN, NS, WM, WN, ADDR, EPI>, 64u * WM * WN, registered<tile_code(2, BM, BN, NS, WM, WN, ADDR, EPI), 0>()}; }
+template <bool CONV3, bool RELU_IN, bool FAST_DMA = false, int EPI = 0, bool LN = false>
+static Kern<TileFn> k256() { return {gemm256_kernel<CONV3, RELU_IN, FAST_DMA, EPI, LN>, 512u, registered<300000 + CONV3 * 10000 + RELU_IN * 1000 + FAST_DMA * 100 + EPI * 10 + LN, 0>()}; }
+template <int NW, int MB>
+static Kern<TileFn> sk() { return {gemm_skinny_kernel<NW, MB>, 64u * NW, registered<500000 + NW * 10 + MB, 0>()}; }
+// ring depth of the default 64 x 64 kernels: their launches put <= 2 workgroups on a CU and wait on HBM for their weight panels
+static int ring64() {
+    static const int ns = [] { const char* e = getenv("CUT3R_GEMM64_STAGES"); return e ? atoi(e) : 3; }();
+    return ns == 6 ? 6 : ns == 4 ? 4 : 3;
+}
 
 static inline int batch_of(const cut3r_gemm_desc* d) { return d->batch > 0 ? d->batch : 1; }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
@@ -1649,86 +1677,85 @@ static int addr_mode_256(const GemmArgs& g) { return !gemm256_fast_ok(g) ? 0 : (
 // ---- one selection function per tile: (stages, addressing mode, compile-time epilogue[, ring depth]) -> instance.  An entry exists only
 // where that instance is launched; everything else falls to the tile's default kernel.
 static Kern<TileFn> kern16(int M, int K) {              // 1, 2 or 3..4 row blocks of 16; K >= 2048 splits over 8 waves, else 4
-    static const TileFn t[2][3] = {{gemm_skinny_kernel<4, 1>, gemm_skinny_kernel<4, 2>, gemm_skinny_kernel<4, 4>},
-                                   {gemm_skinny_kernel<8, 1>, gemm_skinny_kernel<8, 2>, gemm_skinny_kernel<8, 4>}};
+    static const Kern<TileFn> t[2][3] = {{sk<4, 1>(), sk<4, 2>(), sk<4, 4>()}, {sk<8, 1>(), sk<8, 2>(), sk<8, 4>()}};
     const int mb = cdiv(M, 16), w = K >= 2048;
-    return {t[w][mb <= 2 ? mb - 1 : 2], w ? 512u : 256u};
+    return t[w][mb <= 2 ? mb - 1 : 2];
 }
 
 // 4 waves, plain fast addressing: the compile-time epilogues of the one-window (M = 769) Linear layers (fp16 + bias, + GELU, fp32 + bias + fp32 residual)
-template <int NS> static TileFn fast64(int ep) {
-    static const TileFn t[4] = {gemm_kernel<64, 64, NS, 2, 2, 1>, gemm_kernel<64, 64, NS, 2, 2, 1, 1>, gemm_kernel<64, 64, NS, 2, 2, 1, 2>, gemm_kernel<64, 64, NS, 2, 2, 1, 3>};
+template <int NS> static Kern<TileFn> fast64(int ep) {
+    static const Kern<TileFn> t[4] = {tk<NS, 64, 64, NS, 2, 2, 1>(), tk<NS, 64, 64, NS, 2, 2, 1, 1>(), tk<NS, 64, 64, NS, 2, 2, 1, 2>(), tk<NS, 64, 64, NS, 2, 2, 1, 3>()};
     return t[ep >= 1 && ep <= 3 ? ep : 0];
 }
 static Kern<TileFn> kern64(int stages, int K, int am, int ep) {
-    if (stages == 2) return {gemm_kernel<64, 64, 2>, 256};
-    if (stages == 4) return {gemm_kernel<64, 64, 4>, 256};
+    if (stages == 2) return tk<0, 64, 64, 2>();
+    if (stages == 4) return tk<0, 64, 64, 4>();
     const bool wide = stages == 8 || (stages == 0 && K >= 2048);            // long K: 8 waves
     if (stages != 0) am = 0;        // the addressing mode counts on the default path only, the epilogue only with addressing mode 1
     if (am != 1) ep = 0;
-    // ring depth of the default kernels: their launches put <= 2 workgroups on a CU and wait on HBM for their weight panels
-    static const int ns = [] { const char* e = getenv("CUT3R_GEMM64_STAGES"); return e ? atoi(e) : 3; }();
+    const int ns = ring64();
     if (wide) {
-        static const TileFn res[3] = {gemm_kernel<64, 64, 3, 2, 4, 1, 3>, gemm_kernel<64, 64, 4, 2, 4, 1, 3>, gemm_kernel<64, 64, 6, 2, 4, 1, 3>};
-        if (ep == 3) return {res[ns == 6 ? 2 : ns == 4], 512};           // fc2 + residual at one window
-        if (am == 1) return {gemm_kernel<64, 64, 3, 2, 4, 1>, 512};
-        if (am == 2) return {gemm_kernel<64, 64, 3, 2, 4, 2>, 512};
-        return {gemm_kernel<64, 64, 3, 2, 4>, 512};
+        if (ep == 3) return ns == 6 ? tk<6, 64, 64, 6, 2, 4, 1, 3>() : ns == 4 ? tk<4, 64, 64, 4, 2, 4, 1, 3>() : tk<3, 64, 64, 3, 2, 4, 1, 3>();      // fc2 + residual at one window
+        if (am == 1) return tk<0, 64, 64, 3, 2, 4, 1>();
+        if (am == 2) return tk<0, 64, 64, 3, 2, 4, 2>();
+        return tk<0, 64, 64, 3, 2, 4>();
     }
-    if (am == 1) return {ns == 6 ? fast64<6>(ep) : ns == 4 ? fast64<4>(ep) : fast64<3>(ep), 256};
-    if (am == 2) return {gemm_kernel<64, 64, 3, 2, 2, 2>, 256};
-    return {gemm_kernel<64, 64, 3>, 256};
+    if (am == 1) return ns == 6 ? fast64<6>(ep) : ns == 4 ? fast64<4>(ep) : fast64<3>(ep);
+    if (am == 2) return tk<0, 64, 64, 3, 2, 2, 2>();
+    return tk<0, 64, 64, 3>();
 }
 
 static Kern<TileFn> kern128(int stages, int am, int ep) {
     switch (stages) {
-        case 3: return {gemm_kernel<128, 128, 3>, 256};
-        case 4: return {gemm_kernel<128, 128, 2>, 256};
-        case 8: return {gemm_kernel<128, 128, 2, 2, 4>, 512};          // 8 waves, 2 x 4
-        case 9: return {gemm_kernel<128, 128, 2, 4, 2>, 512};          // 8 waves, 4 x 2, generic addressing
-        case 10: return {gemm_kernel<128, 128, 3, 4, 2>, 512};
-        case 14: return {gemm_kernel<128, 128, 4, 4, 2>, 512};         // 128 KiB ring, one workgroup per CU
+        case 3: return tk<0, 128, 128, 3>();
+        case 4: return tk<0, 128, 128, 2>();
+        case 8: return tk<0, 128, 128, 2, 2, 4>();          // 8 waves, 2 x 4
+        case 9: return tk<0, 128, 128, 2, 4, 2>();          // 8 waves, 4 x 2, generic addressing
+        case 10: return tk<0, 128, 128, 3, 4, 2>();
+        case 14: return tk<0, 128, 128, 4, 4, 2>();         // 128 KiB ring, one workgroup per CU
     }
-    static const TileFn fast[4] = {gemm_kernel<128, 128, 2, 4, 2, 1>, gemm_kernel<128, 128, 2, 4, 2, 1, 1>, gemm_kernel<128, 128, 2, 4, 2, 1, 2>, gemm_kernel<128, 128, 2, 4, 2, 1, 3>};
-    if (am == 1) return {fast[ep >= 1 && ep <= 3 ? ep : 0], 512};
-    if (am == 2) return {gemm_kernel<128, 128, 2, 4, 2, 2>, 512};
-    return {gemm_kernel<128, 128, 2, 4, 2>, 512};
+    if (am == 1) {
+        static const Kern<TileFn> fast[4] = {tk<0, 128, 128, 2, 4, 2, 1>(), tk<0, 128, 128, 2, 4, 2, 1, 1>(), tk<0, 128, 128, 2, 4, 2, 1, 2>(), tk<0, 128, 128, 2, 4, 2, 1, 3>()};
+        return fast[ep >= 1 && ep <= 3 ? ep : 0];
+    }
+    if (am == 2) return tk<0, 128, 128, 2, 4, 2, 2>();
+    return tk<0, 128, 128, 2, 4, 2>();
 }
 
 static Kern<TileFn> kern192(int stages, int am, int ep) {
-    if (stages == 3) return {gemm_kernel<192, 128, 3, 4, 2>, 512};     // 120 KiB ring
-    if (am == 2 && ep == 1) return {gemm_kernel<192, 128, 2, 4, 2, 2, 1>, 512};
-    if (am == 2 && ep == 4) return {gemm_kernel<192, 128, 2, 4, 2, 2, 4>, 512};
-    if (am == 1) return {gemm_kernel<192, 128, 2, 4, 2, 1>, 512};
-    if (am == 2) return {gemm_kernel<192, 128, 2, 4, 2, 2>, 512};
-    return {gemm_kernel<192, 128, 2, 4, 2>, 512};
+    if (stages == 3) return tk<0, 192, 128, 3, 4, 2>();     // 120 KiB ring
+    if (am == 2 && ep == 1) return tk<0, 192, 128, 2, 4, 2, 2, 1>();
+    if (am == 2 && ep == 4) return tk<0, 192, 128, 2, 4, 2, 2, 4>();
+    if (am == 1) return tk<0, 192, 128, 2, 4, 2, 1>();
+    if (am == 2) return tk<0, 192, 128, 2, 4, 2, 2>();
+    return tk<0, 192, 128, 2, 4, 2>();
 }
 
 // gemm256_kernel<CONV3, RELU_IN, FAST_DMA, EPI, LN>; am = addr_mode_256, the epilogue counts only with fast addressing
-static TileFn kern256(bool conv, bool relu_in, int am, int ep, bool ln) {
+static Kern<TileFn> kern256(bool conv, bool relu_in, int am, int ep, bool ln) {
     if (conv) {                                                          // the eight convolution instances
-        if (!am) { if (relu_in) return gemm256_kernel<true, true>; return gemm256_kernel<true, false>; }
-        if (relu_in) { if (ep == 4) return gemm256_kernel<true, true, true, 4>; return gemm256_kernel<true, true, true>; }
+        if (!am) { if (relu_in) return k256<true, true>(); return k256<true, false>(); }
+        if (relu_in) { if (ep == 4) return k256<true, true, true, 4>(); return k256<true, true, true>(); }
         switch (ep) {
-            case 1: return gemm256_kernel<true, false, true, 1>;
-            case 4: return gemm256_kernel<true, false, true, 4>;
-            case 5: return gemm256_kernel<true, false, true, 5>;
-            default: return gemm256_kernel<true, false, true>;
+            case 1: return k256<true, false, true, 1>();
+            case 4: return k256<true, false, true, 4>();
+            case 5: return k256<true, false, true, 5>();
+            default: return k256<true, false, true>();
         }
     }
-    if (relu_in) return gemm256_kernel<false, true>;                     // (kept as it is: the generic loader even where the fast path would qualify)
-    if (!am) return gemm256_kernel<false, false>;
+    if (relu_in) return k256<false, true>();                             // (kept as it is: the generic loader even where the fast path would qualify)
+    if (!am) return k256<false, false>();
     if (ln) {                                                            // the consumer rule has left epilogues 1, 2 and 6
-        if (ep == 1) return gemm256_kernel<false, false, true, 1, true>;
-        if (ep == 2) return gemm256_kernel<false, false, true, 2, true>;
-        return gemm256_kernel<false, false, true, 6, true>;
+        if (ep == 1) return k256<false, false, true, 1, true>();
+        if (ep == 2) return k256<false, false, true, 2, true>();
+        return k256<false, false, true, 6, true>();
     }
     switch (ep) {
-        case 1: return gemm256_kernel<false, false, true, 1>;
-        case 2: return gemm256_kernel<false, false, true, 2>;
-        case 3: return gemm256_kernel<false, false, true, 3>;
-        case 6: return gemm256_kernel<false, false, true, 6>;
-        default: return gemm256_kernel<false, false, true>;
+        case 1: return k256<false, false, true, 1>();
+        case 2: return k256<false, false, true, 2>();
+        case 3: return k256<false, false, true, 3>();
+        case 6: return k256<false, false, true, 6>();
+        default: return k256<false, false, true>();
     }
 }
 
@@ -1750,24 +1777,35 @@ static int plan_single(const cut3r_gemm_desc* d, GemmArgs& g, Plan<TileFn>& p) {
         case 16: BM = 64, BN = 16; p.k = kern16(M, d->K); break;
         case 64: BM = 64, BN = 64; p.k = kern64(stages, d->K, am, ep); break;
         case 128: BM = 128, BN = 128; p.k = kern128(stages, am, ep); one_d = g.swz = stages == 13 || (stages == 0 && tiles_of(M, N, 128, 128) >= swz_min); break;
-        case 256: BM = 256, BN = 256; one_d = true; p.k = {kern256(d->conv_k == 3, d->relu_in, am, ep, g.ln_stats != nullptr), 512}; break;
+        case 256: BM = 256, BN = 256; one_d = true; p.k = kern256(d->conv_k == 3, d->relu_in, am, ep, g.ln_stats != nullptr); break;
         // 128 x 192 (four 48-wide or three 64-wide heads per tile), 8 waves (32 x 96 per wave), 80 KB LDS
-        case 128192: BM = 128, BN = 192; one_d = g.swz = 1; p.k = {gemm_kernel<128, 192, 2, 4, 2>, 512}; break;
+        case 128192: BM = 128, BN = 192; one_d = g.swz = 1; p.k = tk<0, 128, 192, 2, 4, 2>(); break;
         // 192 x 128, 8 waves (48 x 64 per wave), 80 KB LDS: two workgroups per CU
         case 192128: BM = 192, BN = 128; one_d = g.swz = 1; p.k = kern192(stages, am, ep); break;
-        case 256128: BM = 256, BN = 128; p.k = {stages == 3 ? (TileFn)gemm_kernel<256, 128, 3, 4, 2> : (TileFn)gemm_kernel<256, 128, 2, 4, 2>, 512}; break;     // 3: 144 KiB ring
-        case 12864: BM = 128, BN = 64; p.k = {stages == 3 ? (TileFn)gemm_kernel<128, 64, 3> : (TileFn)gemm_kernel<128, 64, 2>, 256}; break;
+        case 256128: BM = 256, BN = 128; p.k = stages == 3 ? tk<0, 256, 128, 3, 4, 2>() : tk<0, 256, 128, 2, 4, 2>(); break;     // 3: 144 KiB ring
+        case 12864: BM = 128, BN = 64; p.k = stages == 3 ? tk<0, 128, 64, 3>() : tk<0, 128, 64, 2>(); break;
         default: return CUT3R_ERR_ARG;
     }
     p.grid = tile_grid(M, N, BM, BN, one_d, batch);
     return CUT3R_OK;
 }
 
+// the whole selection of a single launch: the launcher and the instance query both run THIS, so the rule exists once
+static int select_single(const cut3r_gemm_desc* d, GemmArgs& g, Plan<TileFn>& p) {
+    const int rc = fill_args(d, g);
+    return rc == CUT3R_OK ? plan_single(d, g, p) : rc;
+}
+extern "C" int cut3r_gemm_kernel_for(const cut3r_gemm_desc* d) {
+    GemmArgs g;
+    Plan<TileFn> p;
+    return select_single(d, g, p) == CUT3R_OK ? p.k.code : 0;
+}
+extern "C" int cut3r_gemm_kernel_count(void) { return g_ninst[0] + g_ninst[ring64()]; }
+
 extern "C" int cut3r_gemm_f16(const cut3r_gemm_desc* d, void* stream) {
     GemmArgs g;
     Plan<TileFn> p;
-    int rc = fill_args(d, g);
-    if (rc == CUT3R_OK) rc = plan_single(d, g, p);
+    const int rc = select_single(d, g, p);
     if (rc != CUT3R_OK) return rc;
     hipLaunchKernelGGL(p.k.fn, p.grid, dim3(p.k.block), 0, (hipStream_t)stream, g);
     return cut3r_check_launch();
@@ -1778,15 +1816,15 @@ extern "C" int cut3r_gemm_f16(const cut3r_gemm_desc* d, void* stream) {
 // the run-time epilogue (fused RoPE of the image side next to the plain state side; LayerNorm fold consumer in either)
 static Kern<PairFn> pair64(bool wide, int am, int ep) {
     if (wide) {
-        if (ep == 3) return {gemm_pair_kernel<64, 64, 3, 2, 4, 1, 3>, 512};
-        if (am) return {gemm_pair_kernel<64, 64, 3, 2, 4, 1, 0>, 512};
-        return {gemm_pair_kernel<64, 64, 3, 2, 4, 0, 0>, 512};
+        if (ep == 3) return pk<64, 64, 3, 2, 4, 1, 3>();
+        if (am) return pk<64, 64, 3, 2, 4, 1, 0>();
+        return pk<64, 64, 3, 2, 4, 0, 0>();
     }
-    if (ep == 1) return {gemm_pair_kernel<64, 64, 3, 2, 2, 1, 1>, 256};
-    if (ep == 2) return {gemm_pair_kernel<64, 64, 3, 2, 2, 1, 2>, 256};
-    if (ep == 3) return {gemm_pair_kernel<64, 64, 3, 2, 2, 1, 3>, 256};
-    if (am) return {gemm_pair_kernel<64, 64, 3, 2, 2, 1, 0>, 256};
-    return {gemm_pair_kernel<64, 64, 3, 2, 2, 0, 0>, 256};
+    if (ep == 1) return pk<64, 64, 3, 2, 2, 1, 1>();
+    if (ep == 2) return pk<64, 64, 3, 2, 2, 1, 2>();
+    if (ep == 3) return pk<64, 64, 3, 2, 2, 1, 3>();
+    if (am) return pk<64, 64, 3, 2, 2, 1, 0>();
+    return pk<64, 64, 3, 2, 2, 0, 0>();
 }
 
 static int plan_pair(const cut3r_gemm_desc* d0, const cut3r_gemm_desc* d1, GemmPairArgs& a, Plan<PairFn>& p) {
@@ -1810,9 +1848,9 @@ static int plan_pair(const cut3r_gemm_desc* d0, const cut3r_gemm_desc* d1, GemmP
     int BM, BN, swz = 1;            // 1-D grid: tile (pid_m, pid_n) from the XCD-aware rasterisation of each problem
     switch (tile) {
         case 64: BM = 64, BN = 64; p.k = pair64(d0->K >= 2048, am, ep); break;
-        case 128: BM = 128, BN = 128; p.k = {gemm_pair_kernel<128, 128, 2, 4, 2>, 512}; break;
-        case 192128: BM = 192, BN = 128; p.k = {gemm_pair_kernel<192, 128, 2, 4, 2>, 512}; break;
-        case 256: BM = 256, BN = 256; p.k = {gemm256_pair_kernel, 512}; swz = 0; break;      // gemm256_body has its own tile order
+        case 128: BM = 128, BN = 128; p.k = pk<128, 128, 2, 4, 2>(); break;
+        case 192128: BM = 192, BN = 128; p.k = pk<192, 128, 2, 4, 2>(); break;
+        case 256: BM = 256, BN = 256; p.k = {gemm256_pair_kernel, 512, registered<400000, 0>()}; swz = 0; break;      // gemm256_body has its own tile order
         default: return CUT3R_ERR_ARG;
     }
     a.p[0].swz = a.p[1].swz = swz;
@@ -1835,7 +1873,7 @@ static int plan_dpt_final(const cut3r_gemm_desc* d, GemmArgs& g, Plan<TileFn>& p
     if ((((uintptr_t)g.dpt_b | (uintptr_t)g.dpt_pts | (uintptr_t)g.dpt_conf) & 3) || g.dpt_pts_vs < 0 || g.dpt_conf_vs < 0) return CUT3R_ERR_ARG;
     g.swz = 1;
     g.prio = 0;
-    p.k = {gemm_kernel<192, 128, 2, 4, 2, 2, 7>, 512};
+    p.k = {gemm_kernel<192, 128, 2, 4, 2, 2, 7>, 512, tile_code(1, 192, 128, 2, 4, 2, 2, 7)};      // (not registered: outside cut3r_gemm_kernel_count)
     p.grid = tile_grid(g.M, g.N, 192, 128, true, 1);
     return CUT3R_OK;
 }
@@ -1857,13 +1895,22 @@ extern "C" int cut3r_conv3x3_dpt_final(const cut3r_gemm_desc* d, const float* w,
     return cut3r_check_launch();
 }
 
-extern "C" int cut3r_gemm_f16_pair(const cut3r_gemm_desc* d0, const cut3r_gemm_desc* d1, void* stream) {
+static int select_pair(const cut3r_gemm_desc* d0, const cut3r_gemm_desc* d1, GemmPairArgs& a, Plan<PairFn>& p) {
     if (!d0 || !d1) return CUT3R_ERR_ARG;
-    GemmPairArgs a;
-    Plan<PairFn> p;
     int rc = fill_args(d0, a.p[0]);
     if (rc == CUT3R_OK) rc = fill_args(d1, a.p[1]);
-    if (rc == CUT3R_OK) rc = plan_pair(d0, d1, a, p);
+    return rc == CUT3R_OK ? plan_pair(d0, d1, a, p) : rc;
+}
+extern "C" int cut3r_gemm_pair_kernel_for(const cut3r_gemm_desc* d0, const cut3r_gemm_desc* d1) {
+    GemmPairArgs a;
+    Plan<PairFn> p;
+    return select_pair(d0, d1, a, p) == CUT3R_OK ? p.k.code : 0;
+}
+
+extern "C" int cut3r_gemm_f16_pair(const cut3r_gemm_desc* d0, const cut3r_gemm_desc* d1, void* stream) {
+    GemmPairArgs a;
+    Plan<PairFn> p;
+    const int rc = select_pair(d0, d1, a, p);
     if (rc != CUT3R_OK) return rc;
     hipLaunchKernelGGL(p.k.fn, p.grid, dim3(p.k.block), 0, (hipStream_t)stream, a);
     return cut3r_check_launch();

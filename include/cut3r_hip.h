@@ -114,6 +114,26 @@ int cut3r_gemm_tile_for(const cut3r_gemm_desc* d);
  * grids; below 128 tiles of 128 x 128 the 64 x 64 pair kernels (the one-window schedule: 2 x 156 tiles at M = 768 / 769), which also
  * carry the fused RoPE and both sides of the LayerNorm fold, each problem with its own flags. */
 int cut3r_gemm_f16_pair(const cut3r_gemm_desc* d0, const cut3r_gemm_desc* d1, void* stream);
+/* the kernel instance cut3r_gemm_f16 (cut3r_gemm_f16_pair) launches for this descriptor (pair), 0 if the call is refused.  Host only:
+ * launches nothing and reads none of the operands (pointer VALUES count: null tests and alignment, as in the launch).  The launchers take
+ * their kernel from the same selection, so the rule exists once.  The code is six decimal digits, the first the kernel family, the others
+ * the instance's template arguments (csrc/gemm.hip), so two instances never share a code:
+ *   1 T S W A E   gemm_kernel: T tile 1 = 64 x 64, 2 = 128 x 128, 3 = 128 x 192, 4 = 192 x 128, 5 = 256 x 128, 6 = 128 x 64; S depth of the
+ *                 LDS ring; W waves 1 = 2 x 2, 2 = 2 x 4, 3 = 4 x 2; A addressing 0 generic, 1 plain operands with whole K-tiles, 2 3x3
+ *                 convolution with a power-of-two Cin >= 64; E compile-time epilogue, 0 = decided at run time, 1 fp16 + bias, 2 + GELU,
+ *                 3 fp32 + bias + fp32 residual, 4 fp16 + bias + ReLU, (7: cut3r_conv3x3_dpt_final only, never returned here)
+ *   2 T S W A E   gemm_pair_kernel, the same digits
+ *   3 C R F E L   gemm256_kernel (256 x 256): C 3x3 convolution, R ReLU on load, F fast addressing, E epilogue (as above; 5 fp16 + bias +
+ *                 fp16 residuals, 6 fp16 + bias + RoPE of 64-wide heads), L LayerNorm-fold consumer
+ *   400000        gemm256_pair_kernel
+ *   5000 W M      gemm_skinny_kernel (tile 16): W = 4 | 8 waves splitting K, M = 1 | 2 | 4 row blocks of 16
+ * e.g. 113213 = gemm_kernel<64, 64, 3, 2, 4, 1, 3>, 310140 = gemm256_kernel<true, false, true, 4>.  Whether the grid is 1-D (XCD-aware order)
+ * and s_setprio (stages 12) are run-time arguments of an instance, not instances.
+ * cut3r_gemm_kernel_count: how many distinct instances the two launchers can launch in this process -- every instance the selectors name,
+ * those of the 64 x 64 ring depths that CUT3R_GEMM64_STAGES (read once per process) does not select left out.  (No reference counterpart.) */
+int cut3r_gemm_kernel_for(const cut3r_gemm_desc* d);
+int cut3r_gemm_pair_kernel_for(const cut3r_gemm_desc* d0, const cut3r_gemm_desc* d1);
+int cut3r_gemm_kernel_count(void);
 
 /* skinny M<=64 path: Y[M,N] = act(X[M,K] (fp32, optional SiLU on load) * W[N,K]^T (fp16) + bias) (+res).
  * act: 0 none or 1 exact GELU (anything else, ReLU's 2 included, is a bad argument); W 16-byte aligned, ldw % 8 == 0. */
