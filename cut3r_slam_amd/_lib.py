@@ -51,6 +51,8 @@ SIGNATURES = {
                         c_void_p, c_void_p, c_void_p],
     "cut3r_layernorm_dual": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_float, c_int,
                              c_int, c_void_p],
+    "cut3r_layernorm_tokens": [c_void_p, c_int, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p, c_ll, c_void_p, c_ll, c_void_p,
+                               c_ll, c_void_p, c_ll, c_void_p],
     "cut3r_gemm_f16": [C.POINTER(GemmDesc), c_void_p],
     "cut3r_gemm_tile_for": [C.POINTER(GemmDesc)],
     "cut3r_gemm_f16_pair": [C.POINTER(GemmDesc), C.POINTER(GemmDesc), c_void_p],
@@ -64,6 +66,7 @@ SIGNATURES = {
     "cut3r_attention_kernel_for": [c_int, c_int, c_int, c_int],
     "cut3r_attention_f16": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                             c_ll, c_ll, c_ll, c_ll, c_ll, c_ll, c_ll, c_ll, c_float, c_void_p],
+    "cut3r_attention_one_key_f16": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_ll, c_ll, c_ll, c_ll, c_void_p],
     "cut3r_im2col_patch": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "cut3r_cast_f32_f16": [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p],
     "cut3r_colmean": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],

@@ -738,7 +738,35 @@ int launch_attn(const AttnArgs& a, int B, int H, hipStream_t s) {
     return cut3r_check_launch();
 }
 
+// Attention over ONE key: the softmax of a single score is 1 whatever q and k are (exp2(s - s) = 1, l = 1), so every query row of
+// (b, h) is the value row v[b, 0, h, :].  A copy: one 16-byte chunk of one output row per thread, no LDS.  hd8 = H * D / 8.
+__global__ __launch_bounds__(256) void attn_one_key_kernel(const h16* __restrict__ v, h16* __restrict__ o, int Nq, int hd8, long long v_sb,
+                                                           long long o_sb, long long o_sn, long long total) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int c = (int)(i % hd8);
+    const long long r = i / hd8;
+    const int n = (int)(r % Nq);
+    const long long b = r / Nq;
+    const uint4 x = *reinterpret_cast<const uint4*>(v + b * v_sb + (long long)c * 8);
+    *reinterpret_cast<uint4*>(o + b * o_sb + (long long)n * o_sn + (long long)c * 8) = x;
+}
+
 }  // namespace
+
+extern "C" int cut3r_attention_one_key_f16(const void* v, void* out, int B, int H, int Nq, int D, long long v_sb, long long v_sn,
+                                           long long o_sb, long long o_sn, void* stream) {
+    if (!v || !out || B <= 0 || H <= 0 || Nq <= 0 || D <= 0 || (D & 7) || D > 256) return CUT3R_ERR_ARG;
+    if (((uintptr_t)v | (uintptr_t)out) & 15) return CUT3R_ERR_ARG;
+    if ((v_sb | v_sn | o_sb | o_sn) & 7) return CUT3R_ERR_ARG;                 // 16-B vector accesses
+    const long long hd = (long long)H * D;
+    if (v_sb < 0 || v_sn < 0 || o_sn < hd || o_sb < 0 || (B > 1 && o_sb < (long long)(Nq - 1) * o_sn + hd)) return CUT3R_ERR_ARG;
+    const long long total = (long long)B * Nq * (hd / 8);
+    if (hd / 8 > 0x7fffffffLL || (total + 255) / 256 > 0x7fffffffLL) return CUT3R_ERR_ARG;
+    hipLaunchKernelGGL(attn_one_key_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const h16*)v,
+                       (h16*)out, Nq, (int)(hd / 8), v_sb, o_sb, o_sn, total);
+    return cut3r_check_launch();
+}
 
 extern "C" int cut3r_attention_variant(int v) {
     if (v < 0) return g_attn_variant.load(std::memory_order_relaxed);

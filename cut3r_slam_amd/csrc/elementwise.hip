@@ -135,15 +135,11 @@ __global__ void rope2d_table_kernel(float* __restrict__ table, int pmin, int npo
 
 // ------------------------------------------------------------------------------------------------- LayerNorm
 // One wave per row; the row lives in registers (C <= 64*VPL*... handled by a strided loop), two-pass mean/variance
-// exactly as torch (biased variance of (x-mean)).
-__global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ gamma,
-                                                        const float* __restrict__ beta, float eps, int M, int C,
-                                                        h16* __restrict__ y16, int ld16, float* __restrict__ y32, int ld32,
-                                                        const float* __restrict__ mscale, const float* __restrict__ mshift) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= M) return;
-    const float* xr = x + (size_t)row * ldx;
+// exactly as torch (biased variance of (x-mean)).  The row bodies are shared by the plain and the token-scatter launch (same bits):
+// xr = the row, y16r / y32r = where its fp16 / fp32 result goes (either may be null).
+DEVINL void layernorm_row(const float* __restrict__ xr, const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int C,
+                          int lane, h16* __restrict__ y16r, float* __restrict__ y32r, const float* __restrict__ mscale,
+                          const float* __restrict__ mshift) {
     constexpr int MAXV = 8;                 // supports C <= 64*4*8 = 2048
     f32x4 v[MAXV];
     float s = 0.f;
@@ -182,27 +178,22 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 #pragma unroll
                 for (int e = 0; e < 4; e++) o[e] = o[e] * (1.0f + sc[e]) + sh[e];
             }
-            if (y32) *reinterpret_cast<f32x4*>(y32 + (size_t)row * ld32 + c4 * 4) = o;
-            if (y16) {
+            if (y32r) *reinterpret_cast<f32x4*>(y32r + c4 * 4) = o;
+            if (y16r) {
                 half4_t ho = {(h16)o[0], (h16)o[1], (h16)o[2], (h16)o[3]};
-                *reinterpret_cast<half4_t*>(y16 + (size_t)row * ld16 + c4 * 4) = ho;
+                *reinterpret_cast<half4_t*>(y16r + c4 * 4) = ho;
             }
         }
     }
 }
 
-// Specialised LayerNorm for C == 256*NV (768 / 1024 / 1536: every width of the production network): compile-time trip
+// Specialised row body for C == 256*NV (768 / 1024 / 1536: every width of the production network): compile-time trip
 // counts, the row AND gamma/beta are fetched up front (one memory round trip instead of two), 16-byte accesses.
 template <int NV>
-__global__ __launch_bounds__(256) void layernorm_fast_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ gamma,
-                                                             const float* __restrict__ beta, float eps, int M, h16* __restrict__ y16,
-                                                             int ld16, float* __restrict__ y32, int ld32,
-                                                             const float* __restrict__ mscale, const float* __restrict__ mshift) {
+DEVINL void layernorm_fast_row(const float* __restrict__ xr, const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                               int lane, h16* __restrict__ y16r, float* __restrict__ y32r, const float* __restrict__ mscale,
+                               const float* __restrict__ mshift) {
     constexpr int C = 256 * NV;
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= M) return;
-    const float* xr = x + (size_t)row * ldx;
     f32x4 v[NV], g[NV], bt[NV];
 #pragma unroll
     for (int i = 0; i < NV; i++) v[i] = *reinterpret_cast<const f32x4*>(xr + (lane + i * 64) * 4);
@@ -233,12 +224,66 @@ __global__ __launch_bounds__(256) void layernorm_fast_kernel(const float* __rest
 #pragma unroll
             for (int e = 0; e < 4; e++) o[e] = o[e] * (1.0f + sc[e]) + sh[e];
         }
-        if (y32) *reinterpret_cast<f32x4*>(y32 + (size_t)row * ld32 + c) = o;
-        if (y16) {
+        if (y32r) *reinterpret_cast<f32x4*>(y32r + c) = o;
+        if (y16r) {
             const half4_t ho = {(h16)o[0], (h16)o[1], (h16)o[2], (h16)o[3]};
-            *reinterpret_cast<half4_t*>(y16 + (size_t)row * ld16 + c) = ho;
+            *reinterpret_cast<half4_t*>(y16r + c) = ho;
         }
     }
+}
+
+__global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ gamma,
+                                                        const float* __restrict__ beta, float eps, int M, int C,
+                                                        h16* __restrict__ y16, int ld16, float* __restrict__ y32, int ld32,
+                                                        const float* __restrict__ mscale, const float* __restrict__ mshift) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    layernorm_row(x + (size_t)row * ldx, gamma, beta, eps, C, lane, y16 ? y16 + (size_t)row * ld16 : nullptr,
+                  y32 ? y32 + (size_t)row * ld32 : nullptr, mscale, mshift);
+}
+
+template <int NV>
+__global__ __launch_bounds__(256) void layernorm_fast_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ gamma,
+                                                             const float* __restrict__ beta, float eps, int M, h16* __restrict__ y16,
+                                                             int ld16, float* __restrict__ y32, int ld32,
+                                                             const float* __restrict__ mscale, const float* __restrict__ mshift) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    layernorm_fast_row<NV>(x + (size_t)row * ldx, gamma, beta, eps, lane, y16 ? y16 + (size_t)row * ld16 : nullptr,
+                           y32 ? y32 + (size_t)row * ld32 : nullptr, mscale, mshift);
+}
+
+// The decoder's final norm of a view, written where its consumers read it: the rows are Wn groups of N + 1 tokens (pose token, N image
+// tokens); row 0 of group w goes to pose32 + w * pose32_gs (fp32) and pose16 + w * pose16_gs (fp16), row 1 + n to tok16 + w * tok16_gs + n * C
+// (fp16) and, when tok32 is given, to tok32 + w * tok32_gs + n * C (fp32).  NV = 0: the generic row body.  Same row arithmetic as the
+// plain launch, so the same bits as that launch followed by the strided copies.
+struct LnTokDst {
+    float* pose32; h16* pose16; h16* tok16; float* tok32;
+    long long pose32_gs, pose16_gs, tok16_gs, tok32_gs;
+};
+
+template <int NV>
+__global__ __launch_bounds__(256) void layernorm_tokens_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ gamma,
+                                                               const float* __restrict__ beta, float eps, int M, int C, int N1,
+                                                               const LnTokDst d) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    const int w = row / N1, n = row - w * N1;
+    h16* y16r;
+    float* y32r;
+    if (n == 0) {
+        y16r = d.pose16 + (size_t)w * d.pose16_gs;
+        y32r = d.pose32 + (size_t)w * d.pose32_gs;
+    } else {
+        y16r = d.tok16 + (size_t)w * d.tok16_gs + (size_t)(n - 1) * C;
+        y32r = d.tok32 ? d.tok32 + (size_t)w * d.tok32_gs + (size_t)(n - 1) * C : nullptr;
+    }
+    const float* xr = x + (size_t)row * ldx;
+    if constexpr (NV > 0) layernorm_fast_row<NV>(xr, gamma, beta, eps, lane, y16r, y32r, nullptr, nullptr);
+    else layernorm_row(xr, gamma, beta, eps, C, lane, y16r, y32r, nullptr, nullptr);
 }
 
 // LayerNorm of ONE tensor with TWO affine parameter sets -> two fp16 outputs (the row statistics are shared).  In a
@@ -676,6 +721,30 @@ extern "C" int cut3r_layernorm_dual(const float* x, int ldx, const float* g1, co
     if (C == 768) hipLaunchKernelGGL((layernorm_dual_kernel<3>), grid, block, 0, s, x, ldx, g1, b1, (h16*)y1, ld1, g2, b2, (h16*)y2, ld2, eps, M);
     else if (C == 1024) hipLaunchKernelGGL((layernorm_dual_kernel<4>), grid, block, 0, s, x, ldx, g1, b1, (h16*)y1, ld1, g2, b2, (h16*)y2, ld2, eps, M);
     else hipLaunchKernelGGL((layernorm_dual_kernel<6>), grid, block, 0, s, x, ldx, g1, b1, (h16*)y1, ld1, g2, b2, (h16*)y2, ld2, eps, M);
+    return cut3r_check_launch();
+}
+
+extern "C" int cut3r_layernorm_tokens(const float* x, int ldx, const float* gamma, const float* beta, float eps, int Wn, int N, int C,
+                                      float* pose32, long long pose32_gs, void* pose16, long long pose16_gs, void* tok16,
+                                      long long tok16_gs, float* tok32, long long tok32_gs, void* stream) {
+    if (!x || !gamma || !beta || !pose32 || !pose16 || !tok16 || Wn <= 0 || N <= 0 || C <= 0 || (C & 3) || C > 2048) return CUT3R_ERR_ARG;
+    if (ldx < C || (ldx & 3) || !(eps > 0.f)) return CUT3R_ERR_ARG;
+    if ((long long)Wn * ((long long)N + 1) > 0x7fffffffLL) return CUT3R_ERR_ARG;
+    // a group's rows must fit between two group starts, and every vector store must be aligned
+    const long long tok_rows = (long long)N * C;
+    if (pose32_gs < C || pose16_gs < C || tok16_gs < tok_rows || (tok32 && tok32_gs < tok_rows)) return CUT3R_ERR_ARG;
+    if ((pose32_gs | pose16_gs | tok16_gs | (tok32 ? tok32_gs : 0)) & 3) return CUT3R_ERR_ARG;
+    if (misaligned(x, 15) || misaligned(gamma, 15) || misaligned(beta, 15) || misaligned(pose32, 15) || misaligned(tok32, 15) ||
+        misaligned(pose16, 7) || misaligned(tok16, 7))
+        return CUT3R_ERR_ARG;
+    const int M = Wn * (N + 1);
+    const LnTokDst d{pose32, (h16*)pose16, (h16*)tok16, tok32, pose32_gs, pose16_gs, tok16_gs, tok32_gs};
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid((M + 3) / 4), block(256);
+    if (C == 768) hipLaunchKernelGGL((layernorm_tokens_kernel<3>), grid, block, 0, s, x, ldx, gamma, beta, eps, M, C, N + 1, d);
+    else if (C == 1024) hipLaunchKernelGGL((layernorm_tokens_kernel<4>), grid, block, 0, s, x, ldx, gamma, beta, eps, M, C, N + 1, d);
+    else if (C == 1536) hipLaunchKernelGGL((layernorm_tokens_kernel<6>), grid, block, 0, s, x, ldx, gamma, beta, eps, M, C, N + 1, d);
+    else hipLaunchKernelGGL((layernorm_tokens_kernel<0>), grid, block, 0, s, x, ldx, gamma, beta, eps, M, C, N + 1, d);
     return cut3r_check_launch();
 }
 

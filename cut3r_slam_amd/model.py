@@ -137,6 +137,9 @@ class Cut3rModel:
         self.head_overlap = _env_flag("CUT3R_HEAD_OVERLAP", True)    # DPT head of view i on a third stream beside the decoder of view i+1
         self.dpt_fuse = _env_flag("CUT3R_DPT_FUSE", True)            # head.2 + head.4 + activations in one launch
         self.head_chunk = max(1, _env_int("CUT3R_HEAD_CHUNK", 28))   # windows per DPT-head pass of a view ("DPT head chunk")
+        # work the result does not need, left out (0: the parent's launches, for A/B runs; same bits): attention over one key and the
+        # projections only it reads (pose memory), the view tail and the head inputs written / read in place, q and k RoPE in one launch
+        self.one_key = _env_flag("CUT3R_ONE_KEY", True)
         # LayerNorm folded into the GEMMs: 0 off, 1 decoder only, 2 encoder as well ("LayerNorm fold").  The folded panels
         # are built in _prep, so the value can be lowered on a constructed model but not raised
         self.ln_fold = _env_int("CUT3R_LN_FOLD", 1)
@@ -317,18 +320,26 @@ class Cut3rModel:
             ln = (ln, L.c, self.cfg.ln_eps)
         return L, rope, ln
 
-    def _linear(self, x16, name, out, act=0, res1=None, res2=None, skinny=False, rope=None, ln=None, emit=None):
+    def _linear(self, x16, name, out, act=0, res1=None, res2=None, skinny=False, rope=None, ln=None, emit=None, cols=None):
         """skinny: the operand has ONE row per independent sequence (pose token of a tracking window): weight-streaming
         kernel whose per-row result does not depend on how many windows are batched.
         rope = (positions [B,N,2], cols, head width): RoPE of the first `cols` output columns fused into the GEMM epilogue.
         ln = slab statistics of the rows of `x16` (then x16 is the fp16 copy of the UN-normalised residual stream and the LayerNorm in front
-        of this Linear runs inside its epilogue through the folded panel `name@ln`); emit = (stats, x16) this GEMM writes for the next one."""
+        of this Linear runs inside its epilogue through the folded panel `name@ln`); emit = (stats, x16) this GEMM writes for the next one.
+        cols = (lo, hi): only the output columns lo..hi (contiguous weight rows and bias) -- skinny only: that kernel computes every output
+        column on its own, in an order that depends on K alone, so the columns keep their bits."""
         L, rope, ln = self._panel(name, rope, ln)
-        return ops.linear(x16, L.w, out, L.b, act, res1, res2, tile=16 if skinny else 0, rope=rope, ln=ln, emit=emit)
+        w, b = L.w, L.b
+        if cols is not None:
+            assert skinny and rope is None and ln is None and emit is None, "a column range: the skinny kernel only"
+            w, b = w[cols[0]:cols[1]], (b[cols[0]:cols[1]] if b is not None else None)
+        return ops.linear(x16, w, out, b, act, res1, res2, tile=16 if skinny else 0, rope=rope, ln=ln, emit=emit)
 
     def _project(self, probs, act=0):
         """one projection step of a decoder layer, probs = the keyword arguments of `_linear` per block: one block -> ops.linear; the state-side
         and the image-side block -> both problems in ONE grid (ops.linear_pair; same rows, bit for bit)"""
+        if not probs:
+            return None
         if len(probs) == 1:
             return self._linear(act=act, **probs[0])
 
@@ -533,10 +544,17 @@ class Cut3rModel:
 
         rows = lambda t: t.view(-1, t.shape[-2] * t.shape[-1])        # [B,N,heads,D] -> [B*N,C]
         skx, sky = (lambda s: s.Nx == 1), (lambda s: s.Ny == 1)
+        # one key: its softmax is 1 and the attention output is the value row (ops.attention_one_key), so q and k are never read.  Self
+        # attention of ONE token (Nx == 1, the pose-memory read blocks): only the V columns of qkv are projected, straight into `attn`
+        # (every skx projection is the skinny kernel at any B -- ops.linear chunks it -- which `_linear(cols=)` needs).  Cross attention to
+        # ONE token (Ny == 1, the write blocks): no norm2, no projq, no q RoPE
+        one_x, one_y = (lambda s: self.one_key and s.Nx == 1), (lambda s: self.one_key and s.Ny == 1)
         # ---- self attention
         each(lambda s: self._ln(s.x.x, s.p + ".norm1", out16=s.ln16), lambda s: not (s.fold_x or s.pre_ln))
         self._project([dict(x16=s.x.x16 if s.fold_x else s.ln16, name=s.p + ".attn.qkv", out=s.qkv, skinny=skx(s),
-                            rope=(s.xpos, 2 * s.C, s.D) if fuse_x(s) else None, ln=s.x.st if s.fold_x else None) for s in blocks])
+                            rope=(s.xpos, 2 * s.C, s.D) if fuse_x(s) else None, ln=s.x.st if s.fold_x else None)
+                       if not one_x(s) else
+                       dict(x16=s.ln16, name=s.p + ".attn.qkv", out=rows(s.attn), skinny=True, cols=(2 * s.C, 3 * s.C)) for s in blocks])
 
         def self_attn(s):
             v5 = s.qkv.view(s.B, s.Nx, 3, s.heads, s.D)
@@ -544,28 +562,35 @@ class Cut3rModel:
             if s.xpos is not None and not fuse_x(s):
                 ops.rope_2d_pair(q, s.xpos, k, s.xpos, self.cfg.rope_freq, 1.0)
             ops.attention(q, k, v, s.attn, s.D ** -0.5)
-        each(self_attn)
+        each(self_attn, lambda s: not one_x(s))
         self._project([dict(x16=rows(s.attn), name=s.p + ".attn.proj", out=s.out.x, res1=s.x.x, skinny=skx(s), emit=s.emit) for s in blocks])
         # ---- cross attention: queries from x, keys / values from y
-        each(lambda s: self._ln(s.out.x, s.p + ".norm2", out16=s.ln16), lambda s: not s.fold_o)
+        each(lambda s: self._ln(s.out.x, s.p + ".norm2", out16=s.ln16), lambda s: not (s.fold_o or one_y(s)))
         self._project([dict(x16=s.out.x16 if s.fold_o else s.ln16, name=s.p + ".cross_attn.projq", out=rows(s.q), skinny=skx(s),
-                            rope=(s.xpos, s.C, s.D) if fuse_x(s) else None, ln=s.out.st if s.fold_o else None) for s in blocks])
-        rope_q = lambda s: s.xpos is not None and not fuse_x(s)
+                            rope=(s.xpos, s.C, s.D) if fuse_x(s) else None, ln=s.out.st if s.fold_o else None) for s in blocks if not one_y(s)])
+        rope_q = lambda s: s.xpos is not None and not fuse_x(s) and not one_y(s)
+        rope_k = lambda s: s.ypos is not None and not fuse_y(s) and not one_y(s)
+        # q and k both rotated by a launch (the 48-wide heads): ONE launch behind projk|projv covers both token ranges
+        rope_qk = lambda s: self.one_key and rope_q(s) and rope_k(s)
         norm_y = lambda s: not (s.fold_y or s.pre_ln)
 
         def q_rope_and_norm_y(s):
-            if rope_q(s):
+            if rope_q(s) and not rope_qk(s):
                 self._rope(s.q, s.xpos)
             if norm_y(s):
                 self._ln(s.y.x, s.p + ".norm_y", out16=s.y16)
-        each(q_rope_and_norm_y, lambda s: rope_q(s) or norm_y(s))
+        each(q_rope_and_norm_y, lambda s: (rope_q(s) and not rope_qk(s)) or norm_y(s))
         self._project([dict(x16=s.y.x16 if s.fold_y else s.y16, name=s.p + ".cross_attn.projkv", out=s.kv, skinny=sky(s),
                             rope=(s.ypos, s.C, s.D) if fuse_y(s) else None, ln=s.y.st if s.fold_y else None) for s in blocks])
 
         def cross_attn(s):
             kv4 = s.kv.view(s.B, s.Ny, 2, s.heads, s.D)
             k, v = kv4[:, :, 0], kv4[:, :, 1]
-            if s.ypos is not None and not fuse_y(s):
+            if one_y(s):
+                return ops.attention_one_key(v, s.cattn)
+            if rope_qk(s):
+                ops.rope_2d_pair(s.q, s.xpos, k, s.ypos, self.cfg.rope_freq, 1.0)
+            elif s.ypos is not None and not fuse_y(s):
                 self._rope(k, s.ypos)
             ops.attention(s.q, k, v, s.cattn, s.D ** -0.5)
         each(cross_attn)
@@ -625,7 +650,11 @@ class Cut3rModel:
         L = self.w[name]
         B, H, W, Cc = x.shape
         out = self.buf(tag or name, (B, H, W, L.npad), F16)
-        ops.linear(x.view(-1, Cc), L.w, out.view(-1, L.npad), L.b)
+        if x.is_contiguous():
+            ops.linear(x.view(-1, Cc), L.w, out.view(-1, L.npad), L.b)
+        else:       # one view of several windows, read where it lies (batch stride = one window): a problem per batch element, same bits
+            ops.linear_batched(x.view(B, H * W, Cc), L.w.unsqueeze(0).expand(B, -1, -1), out.view(B, H * W, L.npad),
+                               None if L.b is None else L.b.unsqueeze(0).expand(B, -1))
         return out
 
     def _convT(self, x, name):
@@ -650,7 +679,7 @@ class Cut3rModel:
         return self._conv1(out, p + ".out_conv")
 
     def _dpt(self, p, toks16: List[torch.Tensor], B, nh, nw, last=True):
-        """toks16: 4 fp16 tensors [B*nh*nw, C_i] (NHWC token maps).  Returns fp16 [B*H*W, last_dim] features (last=False: the
+        """toks16: 4 fp16 tensors [B*nh*nw, C_i] (NHWC token maps), or [B, nh*nw, C_i] views with a batch stride.  Returns fp16 [B*H*W, last_dim] features (last=False: the
         input of head.2, for a caller that runs head.2 together with the output stage)."""
         a = p + ".act_postprocess"
         t = [x.view(B, nh, nw, -1) for x in toks16]
@@ -788,8 +817,9 @@ class Cut3rModel:
         pose_tok16 = self.buf("head.pose_tok16", (Wn, V, D), F16)
         g32 = self.buf("dec.g32", (Wn, E), F32)
         g16 = self.buf("dec.g16", (Wn, E), F16)
-        dn32 = self.buf("dec.dn32", (Wn * (N + 1), D), F32)
-        dn16 = self.buf("dec.dn16", (Wn * (N + 1), D), F16)
+        if not self.one_key:
+            dn32 = self.buf("dec.dn32", (Wn * (N + 1), D), F32)
+            dn16 = self.buf("dec.dn16", (Wn * (N + 1), D), F16)
         Lde = self.w["decoder_embed"]
         w_de = Lde.w.unsqueeze(0).expand(Wn, -1, -1)
         b_de = Lde.b.unsqueeze(0).expand(Wn, -1)
@@ -854,15 +884,19 @@ class Cut3rModel:
             if not dead_tail:
                 self._ln(s_a.x, "dec_norm_state", out32=s_b.x)
             new_state = s_b
-            self._ln(a.x, "dec_norm", out16=dn16, out32=dn32)
-            dn16v, dn32v = dn16.view(Wn, N + 1, D), dn32.view(Wn, N + 1, D)
-            tok3[:, i].copy_(dn16v[:, 1:])
-            if tok3_32 is not None:
-                tok3_32[:, i].copy_(dn32v[:, 1:])
-            pose_tok[:, i].copy_(dn32v[:, 0])
-            pose_tok16[:, i].copy_(dn16v[:, 0])
+            if self.one_key:        # every row straight to where the heads and the pose memory read it
+                ops.layernorm_tokens(a.x, *self.w["dec_norm"], cfg.ln_eps, pose_tok[:, i], pose_tok16[:, i], tok3[:, i],
+                                     None if tok3_32 is None else tok3_32[:, i])
+            else:
+                self._ln(a.x, "dec_norm", out16=dn16, out32=dn32)
+                dn16v, dn32v = dn16.view(Wn, N + 1, D), dn32.view(Wn, N + 1, D)
+                tok3[:, i].copy_(dn16v[:, 1:])
+                if tok3_32 is not None:
+                    tok3_32[:, i].copy_(dn32v[:, 1:])
+                pose_tok[:, i].copy_(dn32v[:, 0])
+                pose_tok16[:, i].copy_(dn16v[:, 0])
             if not dead_tail:
-                self._mem_update(mem[cm], g16, dn32v[:, 0], mem[cm ^ 1], Wn)
+                self._mem_update(mem[cm], g16, pose_tok[:, i], mem[cm ^ 1], Wn)
                 cm ^= 1
             if head_fork:
                 # fork: this view's DPT head (batch = the Wn windows) runs beside the decoder of the next view
@@ -874,6 +908,9 @@ class Cut3rModel:
                         nb = c1 - c0
                         tk = []
                         for name, src, dim in (("f", feat16, E), ("t1", tok1, D), ("t2", tok2, D), ("t3", tok3, D)):
+                            if self.one_key:        # the 1 x 1 convolutions read view i of the windows where it lies (_conv1)
+                                tk.append(src[c0:c1, i])
+                                continue
                             t = self.buf("head.view." + name, (nb, N, dim), F16)
                             t.copy_(src[c0:c1, i])
                             tk.append(t.view(nb * N, dim))

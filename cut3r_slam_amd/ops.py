@@ -174,6 +174,31 @@ def layernorm_dual(x, g1, b1, out1, g2, b2, out2, eps=1e-6):
                                    float(eps), M, Cc, _stream()), "cut3r_layernorm_dual")
 
 
+def layernorm_tokens(x, gamma, beta, eps, pose32, pose16, tok16, tok32=None):
+    """LayerNorm of Wn groups of N + 1 rows (x fp32 [Wn * (N + 1), C]) written where the consumers read it, in one launch: row 0 of group w
+    -> pose32[w] (fp32 [Wn,C]) and pose16[w] (fp16 [Wn,C]); rows 1..N -> tok16[w] (fp16 [Wn,N,C]) and, if given, tok32[w] (fp32 [Wn,N,C]).  The
+    destinations may be slices of larger tensors (any group stride, rows of a group contiguous).  Same bits as `layernorm` + copies."""
+    _cuda(x, gamma, beta, pose32, pose16, tok16, tok32)
+    _req(x.dtype == F32 and x.dim() == 2 and x.stride(1) == 1, "x must be fp32 [M,C] with unit inner stride")
+    _req(tok16.dim() == 3, "tok16 [Wn,N,C]")
+    Wn, N, Cc = tok16.shape
+    _req(Wn > 0 and N > 0 and x.shape == (Wn * (N + 1), Cc), f"x must hold Wn * (N + 1) = {Wn * (N + 1)} rows of {Cc}")
+    _req(gamma.dtype == F32 and beta.dtype == F32 and gamma.numel() == Cc and beta.numel() == Cc, "gamma/beta [C] fp32")
+    _req(gamma.is_contiguous() and beta.is_contiguous(), "gamma/beta contiguous")
+    _req(float(eps) > 0.0, f"layernorm_tokens: eps must be > 0, got {eps}")
+    for o, dt in ((pose32, F32), (pose16, F16)):
+        _req(o.dtype == dt and o.shape == (Wn, Cc) and o.stride(1) == 1, "pose outputs [Wn,C] with unit inner stride")
+    for o, dt in ((tok16, F16), (tok32, F32)):
+        if o is not None:
+            _req(o.dtype == dt and o.shape == (Wn, N, Cc) and o.stride(2) == 1 and o.stride(1) == Cc, "token outputs [Wn,N,C], rows of a group contiguous")
+    _aligned(16, x=x, gamma=gamma, beta=beta, pose32=pose32, tok32=tok32)
+    _aligned(8, pose16=pose16, tok16=tok16)
+    lib = _lib.load()
+    check(lib.cut3r_layernorm_tokens(_p(x), x.stride(0), _p(gamma), _p(beta), float(eps), Wn, N, Cc, _p(pose32), pose32.stride(0),
+                                     _p(pose16), pose16.stride(0), _p(tok16), tok16.stride(0), _p(tok32),
+                                     tok32.stride(0) if tok32 is not None else 0, _stream()), "cut3r_layernorm_tokens")
+
+
 # ------------------------------------------------------------------------------------------------ GEMM
 LN_FOLD_MAX_K = 1024        # the folded epilogue reads at most 16 slabs of 64 columns per row (LN_MAXS in csrc/gemm.hip)
 GEMM_STAGES = int(os.environ.get("CUT3R_GEMM_STAGES", "0"))     # tuning override (0 = kernel default)
@@ -393,6 +418,22 @@ def attention(q, k, v, out, scale):
     check(lib.cut3r_attention_f16(_p(q), _p(k), _p(v), _p(out), B, H, Nq, Nk, D, q.stride(0), q.stride(1), k.stride(0),
                                   k.stride(1), v.stride(0), v.stride(1), out.stride(0), out.stride(1), float(scale),
                                   _stream()), f"cut3r_attention_f16 B={B} H={H} Nq={Nq} Nk={Nk} D={D}")
+    return out
+
+
+def attention_one_key(v, out):
+    """`attention` over ONE key without the work: v [B,1,H,D], out [B,Nq,H,D] fp16 views as in `attention`; every query row of (b, h) becomes
+    v[b, 0, h, :] -- the softmax of one score is 1, and these are the bits `attention` writes (finite q and k)."""
+    _cuda(v, out)
+    for t in (v, out):
+        _req(t.dtype == F16 and t.dim() == 4 and t.stride(3) == 1 and t.stride(2) == t.shape[3], "attention operands: fp16 (B,N,H,D) views")
+    B, Nq, H, D = out.shape
+    _req(v.shape == (B, 1, H, D), "attention_one_key: v [B,1,H,D]")
+    _req(D % 8 == 0 and D <= 256, f"unsupported head dim {D}")
+    _aligned(16, v=v, out=out)
+    lib = _lib.load()
+    check(lib.cut3r_attention_one_key_f16(_p(v), _p(out), B, H, Nq, D, v.stride(0), v.stride(1), out.stride(0), out.stride(1), _stream()),
+          f"cut3r_attention_one_key_f16 B={B} H={H} Nq={Nq} D={D}")
     return out
 
 

@@ -49,6 +49,15 @@ int cut3r_layernorm(const float* x, int ldx, const float* gamma, const float* be
  * the other act on the same tokens (dust3r/blocks.py:292-297).  C in {768, 1024, 1536}. */
 int cut3r_layernorm_dual(const float* x, int ldx, const float* g1, const float* b1, void* y1, int ld1, const float* g2,
                          const float* b2, void* y2, int ld2, float eps, int M, int C, void* stream);
+/* the decoder's final norm of a view (dust3r/model.py:694-697) written where its consumers read it: x fp32 holds Wn groups of N + 1 rows
+ * (pose token, N image tokens; row stride ldx).  Row 0 of group w goes to pose32 + w * pose32_gs (fp32) and pose16 + w * pose16_gs (fp16);
+ * row 1 + n goes to tok16 + w * tok16_gs + n * C (fp16) and, if tok32 is not NULL, to tok32 + w * tok32_gs + n * C (fp32).  Group strides in
+ * elements: >= the rows they separate, multiples of 4.  The row arithmetic is cut3r_layernorm's (the same kernels' row bodies), so the
+ * bits are those of cut3r_layernorm followed by strided copies.  Alignment as for cut3r_layernorm; eps > 0; no modulation.  A bad
+ * argument is refused with CUT3R_ERR_ARG before the launch. */
+int cut3r_layernorm_tokens(const float* x, int ldx, const float* gamma, const float* beta, float eps, int Wn, int N, int C,
+                           float* pose32, long long pose32_gs, void* pose16, long long pose16_gs, void* tok16, long long tok16_gs,
+                           float* tok32, long long tok32_gs, void* stream);
 
 /* ---- GEMM family ---------------------------------------------------------------------------------------------
  * replaces nn.Linear / nn.Conv2d / nn.ConvTranspose2d(+bias)(+GELU|ReLU)(+residual) in the ViT and DPT stacks
@@ -148,6 +157,16 @@ int cut3r_gemv_f16w(const float* X, int ldx, const void* W, int ldw, const float
 int cut3r_attention_f16(const void* q, const void* k, const void* v, void* out, int B, int H, int Nq, int Nk, int D,
                         long long q_sb, long long q_sn, long long k_sb, long long k_sn, long long v_sb, long long v_sn,
                         long long o_sb, long long o_sn, float scale, void* stream);
+
+/* cut3r_attention_f16 with Nk = 1, without the work: the softmax of one score is 1, so out[b, n, h, :] = v[b, 0, h, :] for all Nq query
+ * rows -- the bits cut3r_attention_f16 writes (P = 1, l = 1, O = 1 v + 0).  The pose memory runs this: its write blocks attend to one
+ * token per window, its read blocks have one token per window attending to itself (dust3r/model.py:204-222).  v and out as in
+ * cut3r_attention_f16 (v_sn is checked, never used).  One difference: a non-finite score (non-finite q or k) gives NaN there and v here;
+ * the network never forms the score on this path.  16-byte accesses: v, out 16-byte aligned, every stride a multiple of 8, D % 8 == 0,
+ * D <= 256, o_sn >= H D and batches of out that do not overlap.  Anything else, a null pointer or B, H, Nq <= 0: CUT3R_ERR_ARG, nothing
+ * is launched.  (No reference counterpart: the reference calls F.scaled_dot_product_attention here too.) */
+int cut3r_attention_one_key_f16(const void* v, void* out, int B, int H, int Nq, int D, long long v_sb, long long v_sn, long long o_sb,
+                                long long o_sn, void* stream);
 
 /* which kernel serves the 48- and 64-wide heads: 1 (default) the software-pipelined LDS-DMA kernel, 0 the register-staged one.
  * Both give the same bits (tests/test_kernels_gpu.py); the switch exists for that test and for A/B timing.  v < 0 only queries.
