@@ -182,6 +182,12 @@ SIGNATURES = {
     "cut3r_nn_query": [c_int, c_void_p, c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_ll, c_void_p],
     "cut3r_icp_moments_workspace_bytes": [c_int],
     "cut3r_icp_moments": [c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 5 + [c_ll, c_void_p],
+    "cut3r_dist_stats_workspace_bytes": [c_int],
+    "cut3r_dist_stats": [c_void_p, c_int, C.c_double, C.c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_void_p],
+    "cut3r_dist_median_workspace_bytes": [c_int],
+    "cut3r_dist_median": [c_void_p, c_int, c_void_p, c_void_p, c_ll, c_void_p],
+    "cut3r_icp_moments_scaled_workspace_bytes": [c_int],
+    "cut3r_icp_moments_scaled": [c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 5 + [c_ll, c_void_p],
     "cut3r_mesh_raster_workspace_bytes": [c_int, c_int, c_int, c_int],
     "cut3r_mesh_raster": [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p,
                           c_void_p, c_ll, c_void_p],
@@ -225,7 +231,9 @@ RESTYPES = {"cut3r_ba_workspace_floats": c_ll, "cut3r_gs_workspace_bytes": c_ll,
             "cut3r_nn_workspace_bytes": c_ll, "cut3r_icp_moments_workspace_bytes": c_ll, "cut3r_mesh_raster_workspace_bytes": c_ll,
             "cut3r_depth_l1_workspace_bytes": c_ll, "cut3r_depth_cloud_workspace_bytes": c_ll, "cut3r_cloud_bounds_workspace_bytes": c_ll,
             "cut3r_voxel_downsample_workspace_bytes": c_ll, "cut3r_exposure_partial_rows": c_ll, "cut3r_gs_pose_partial_rows": c_ll,
-            "cut3r_mesh_cluster_workspace_bytes": c_ll, "cut3r_mesh_components_workspace_bytes": c_ll, "cut3r_focal_workspace_bytes": c_ll}
+            "cut3r_mesh_cluster_workspace_bytes": c_ll, "cut3r_mesh_components_workspace_bytes": c_ll, "cut3r_focal_workspace_bytes": c_ll,
+            "cut3r_dist_stats_workspace_bytes": c_ll, "cut3r_dist_median_workspace_bytes": c_ll,
+            "cut3r_icp_moments_scaled_workspace_bytes": c_ll}
 
 _lib = None
 

@@ -11,6 +11,8 @@ viewpoints inside the room) and the clipped Chamfer distances of geometry_eval_u
   chamfer_distance / chamfer_distance_RMSE     geometry_eval_utils.py:79-110
   voxel_down_sample                            Open3D's PointCloud.voxel_down_sample (eval7_scenes_dense.py:238-250), output sorted by voxel
   sim3_from_trajectories                       the Sim(3) that run_replica.py:45-46 applies to the mesh before it is scored
+  run_evaluation / precision_recall / align_coarse_to_fine     evaluate_3d_reconstruction.run_evaluation (eval_recon.py:232-235): the keys
+                                               run_replica.py:54-57 reads; written from the published Tanks-and-Temples evaluation
 
 The evaluation against ground-truth DEPTH MAPS instead of a mesh (scripts/eval7_scenes_dense.py) is cut3r_slam_amd/eval_dense.py; it uses
 icp_point_to_point and chamfer_distance_RMSE from here and the GPU voxel downsample ops.voxel_downsample.
@@ -119,24 +121,50 @@ def rigid_from_moments(m) -> np.ndarray:
     return T
 
 
-def icp_point_to_point(source, target, threshold, init=None, max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6) -> ICPResult:
+def sim3_from_moments(m) -> np.ndarray:
+    """the least-squares similarity src -> dst, 4x4 (s R | t), from the fp64 moments of NNGrid.moments_scaled (eval_ate.umeyama with
+    with_scale=True restated on sums: the variance of src = sum |src|^2 / n - |mu_src|^2, s = trace(D S) / variance); identity without
+    correspondences, and the rigid motion (s = 1) when the source points coincide (variance <= 1e-12 of the mean |src|^2)"""
+    m = np.asarray(m, np.float64)
+    n = m[0]
+    T = np.eye(4)
+    if n <= 0:
+        return T
+    mu_s, mu_d = m[2:5] / n, m[5:8] / n
+    cov = m[8:17].reshape(3, 3).T / n - np.outer(mu_d, mu_s)
+    var = m[17] / n - mu_s @ mu_s
+    U, D, Vt = np.linalg.svd(cov)
+    S = np.eye(3)
+    if np.linalg.det(U) * np.linalg.det(Vt) < 0:
+        S[2, 2] = -1
+    R = U @ S @ Vt
+    s = float(np.trace(np.diag(D) @ S) / var) if var > 1e-12 * m[17] / n else 1.0       # below: the rounding of the subtraction
+    T[:3, :3] = s * R
+    T[:3, 3] = mu_d - s * R @ mu_s
+    return T
+
+
+def icp_point_to_point(source, target, threshold, init=None, max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6,
+                       with_scaling=False) -> ICPResult:
     """Open3D registration_icp with TransformationEstimationPointToPoint and ICPConvergenceCriteria's defaults: correspondences (d2 <=
     threshold^2), update, T = update @ T, correspondences again, stop when fitness and inlier RMSE both moved by less than the criteria.
-    The source is never rewritten: the kernel applies fp32(T) to each source point as it loads it."""
+    The source is never rewritten: the kernel applies fp32(T) to each source point as it loads it.  with_scaling: the update is the
+    similarity of sim3_from_moments (TransformationEstimationPointToPoint(with_scaling=True)), T = [s R | t] @ T."""
     src, dst = as_points(source), as_points(target)
     grid = ops.NNGrid(dst, src.shape[0])
     T = np.eye(4) if init is None else np.asarray(init, np.float64).reshape(4, 4).copy()
+    moments, update = (grid.moments_scaled, sim3_from_moments) if with_scaling else (grid.moments, rigid_from_moments)
 
     def evaluate(T):
         d2, idx = grid.query(src, max_dist=threshold, transform=T)
-        m = grid.moments(src, d2, idx, transform=T).cpu().numpy()
+        m = moments(src, d2, idx, transform=T).cpu().numpy()
         n = m[0]
         return m, n / src.shape[0], (math.sqrt(m[1] / n) if n > 0 else 0.0)
 
     m, fitness, rmse = evaluate(T)
     it = 0
     for i in range(max_iteration):
-        T = rigid_from_moments(m) @ T
+        T = update(m) @ T
         prev_fitness, prev_rmse = fitness, rmse
         m, fitness, rmse = evaluate(T)
         it = i + 1
@@ -163,15 +191,157 @@ def calc_3d_metric(rec_mesh, gt_mesh, align=True, samples=N_SAMPLES, seed=0):
     return {"accuracy": acc * 100, "completion": comp * 100, "completion_ratio": ratio * 100}
 
 
-def eval_recon(rec_mesh, gt_mesh, eval_3d=True, align=True, samples=N_SAMPLES, seed=0, eval_2d=False, n_imgs=10, unseen=None):
-    """eval_recon.py:226-250 without the external run_evaluation; the 2-D depth metric (n_imgs views, 10 as eval_recon.py:238) only with
-    eval_2d"""
+def eval_recon(rec_mesh, gt_mesh, eval_3d=True, align=True, samples=N_SAMPLES, seed=0, eval_2d=False, n_imgs=10, unseen=None, pr=False,
+               pr_thresh=0.05, pr_scale=False, pr_out=None):
+    """eval_recon.py:226-250; the 2-D depth metric (n_imgs views, 10 as eval_recon.py:238) only with eval_2d, the keys of the external
+    run_evaluation (eval_recon.py:232-235: precision, recall, F-score) only with pr"""
     result = {}
     if eval_3d:
         result.update(calc_3d_metric(rec_mesh, gt_mesh, align=align, samples=samples, seed=seed))
+    if pr:
+        result.update(run_evaluation(rec_mesh, gt_mesh, distance_thresh=pr_thresh, icp_align=align, with_scaling=pr_scale, samples=samples,
+                                     seed=seed, out_dir=pr_out))
     if eval_2d:
         result.update(calc_2d_metric(rec_mesh, gt_mesh, align=align, n_imgs=n_imgs, unseen=unseen, seed=seed))
     return result
+
+
+# ------------------------------------------------------------------------------------------------- precision, recall, F-score
+# evaluate_3d_reconstruction.run_evaluation (eval_recon.py:9,232-235) is the Tanks-and-Temples evaluation; its library is not available
+# here, so what follows is written from the published evaluation and PARITY WITH THE LIBRARY IS UNPINNED.  What is pinned is the rule
+# stated here, against tests/pr_oracle.py.
+class PRResult(NamedTuple):
+    precision: float               # share of the rec points closer than tau to the GT cloud (strict <)
+    recall: float                  # share of the GT points closer than tau to the rec cloud
+    fscore: float                  # 2 p r / (p + r), 0 when both are 0
+    mean_rec: float                # rec -> GT distances: mean, median (the mean of the two middle ranks), population std, min, max
+    median_rec: float
+    std_rec: float
+    min_rec: float
+    max_rec: float
+    mean_gt: float                 # GT -> rec distances
+    median_gt: float
+    std_gt: float
+    min_gt: float
+    max_gt: float
+    edges: np.ndarray              # fp64 [nbins + 1] = arange(nbins + 1) * tau / bins_per_tau, nbins = stretch * bins_per_tau
+    cum_rec: np.ndarray            # fp64 [nbins]: share of the rec points with d < edges[k + 1] (precision as a function of the threshold)
+    cum_gt: np.ndarray             # fp64 [nbins]: the same for the GT points (recall)
+    dist2_rec: torch.Tensor        # fp32 [n_rec] squared distance of every rec point to the GT cloud, on the GPU
+    dist2_gt: torch.Tensor         # fp32 [n_gt]
+    rec_points: torch.Tensor       # fp32 [n_rec,3] the (downsampled) clouds the distances belong to, on the GPU
+    gt_points: torch.Tensor        # fp32 [n_gt,3]
+
+
+def _one_way(dist2, tau, w, nbins):
+    counts, moments, hist = ops.dist_stats(dist2, tau, w, nbins)
+    med = ops.dist_median(dist2)
+    counts, moments, hist, med = counts.cpu().numpy(), moments.cpu().numpy(), hist.cpu().numpy(), med.cpu().numpy().astype(np.float64)
+    good, below, bad = (int(c) for c in counts)
+    if bad:
+        raise ValueError(f"{bad} of {len(dist2)} nearest-neighbour distances are NaN, negative or infinite")
+    mean = moments[0] / good
+    std = math.sqrt(max(moments[1] / good - mean * mean, 0.0))
+    median = 0.5 * (math.sqrt(med[0]) + math.sqrt(med[1]))
+    return below / good, (float(mean), float(median), std, float(moments[2]), float(moments[3])), np.cumsum(hist).astype(np.float64) / good
+
+
+def precision_recall(rec_pts, gt_pts, tau=0.05, voxel=None, stretch=5, bins_per_tau=100) -> PRResult:
+    """the two clouds are voxel-downsampled (ops.voxel_downsample; voxel=None: tau / 2, voxel=0: not at all), the exact nearest neighbour
+    is searched both ways, and ops.dist_stats / ops.dist_median reduce the two sets of distances on the GPU.  The histograms have
+    bins_per_tau bins per tau out to stretch * tau (at most 4096 bins); a distance beyond it counts in the means but in no bin."""
+    tau = float(tau)
+    nbins = int(stretch) * int(bins_per_tau)
+    if not (tau > 0 and 0 < nbins <= ops.DIST_STATS_MAX_BINS):
+        raise ValueError(f"tau must be > 0 and stretch * bins_per_tau in 1 .. {ops.DIST_STATS_MAX_BINS}")
+    voxel = 0.5 * tau if voxel is None else float(voxel)
+    rec, gt = as_points(rec_pts), as_points(gt_pts)
+    if voxel > 0:
+        rec, gt = ops.voxel_downsample(rec, voxel)[0], ops.voxel_downsample(gt, voxel)[0]
+    w = tau / int(bins_per_tau)
+    d2_rec, _ = ops.nn_query(gt, rec)
+    d2_gt, _ = ops.nn_query(rec, gt)
+    p, s_rec, cum_rec = _one_way(d2_rec, tau, w, nbins)
+    r, s_gt, cum_gt = _one_way(d2_gt, tau, w, nbins)
+    f = 2 * p * r / (p + r) if p + r > 0 else 0.0
+    return PRResult(p, r, f, *s_rec, *s_gt, np.arange(nbins + 1, dtype=np.float64) * w, cum_rec, cum_gt, d2_rec, d2_gt, rec, gt)
+
+
+def align_coarse_to_fine(rec_pts, gt_pts, tau, with_scaling=False) -> np.ndarray:
+    """the published registration schedule, rec -> GT, 4x4: ICP on the clouds downsampled at voxel tau with threshold 80 tau, on the clouds
+    at voxel tau / 2 with threshold 20 tau, and on those again with threshold 2 tau; 20 iterations each, each from the result before.  The
+    clouds are downsampled once, as they come (the library downsamples the source after moving it by the running estimate)."""
+    tau = float(tau)
+    rec, gt = as_points(rec_pts), as_points(gt_pts)
+    coarse = ops.voxel_downsample(rec, tau)[0], ops.voxel_downsample(gt, tau)[0]
+    fine = ops.voxel_downsample(rec, 0.5 * tau)[0], ops.voxel_downsample(gt, 0.5 * tau)[0]
+    T = np.eye(4)
+    for (src, dst), threshold in ((coarse, 80 * tau), (fine, 20 * tau), (fine, 2 * tau)):
+        T = icp_point_to_point(src, dst, threshold, T, max_iteration=20, with_scaling=with_scaling).transformation
+    return T
+
+
+def transform_points(points, M) -> torch.Tensor:
+    """fp32 [N,3]: ((M00 x + M01 y) + M02 z) + M03 per row in fp64, every product and sum rounded on its own, then rounded to fp32"""
+    p = as_points(points).double()
+    M = np.asarray(M, np.float64).reshape(4, 4)
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    return torch.stack([((x * M[r, 0] + y * M[r, 1]) + z * M[r, 2]) + M[r, 3] for r in range(3)], 1).float().contiguous()
+
+
+HOT_R = ((0.0, (1.0, 1.0, 1.0)), (1 - 0.746032, (1.0, 1.0, 0.0)), (1 - 0.365079, (1.0, 0.0, 0.0)), (1.0, (0.0416, 0.0, 0.0)))
+
+
+def error_colors(dist, tau) -> torch.Tensor:
+    """uint8 [N,3]: x = min(d, 3 tau) / (3 tau) through matplotlib's "hot" reversed, i.e. linear between white at x = 0, (1, 1, 0) at
+    1 - 0.746032, (1, 0, 0) at 1 - 0.365079 and (0.0416, 0, 0) at x = 1 (hot's breakpoints; matplotlib's 256-entry table is not
+    reproduced), each channel floor(255 c + 0.5)"""
+    d = torch.as_tensor(dist, dtype=torch.float64)
+    x = torch.clamp(d, max=3 * float(tau)) / (3 * float(tau))
+    c = torch.zeros(x.shape + (3,), dtype=torch.float64, device=x.device)
+    for (x0, c0), (x1, c1) in zip(HOT_R[:-1], HOT_R[1:]):
+        inside = ((x >= x0) & (x <= x1))[..., None]
+        u = ((x - x0) / (x1 - x0))[..., None]
+        c = torch.where(inside, torch.tensor(c0, dtype=torch.float64, device=x.device) * (1 - u)
+                        + torch.tensor(c1, dtype=torch.float64, device=x.device) * u, c)
+    return torch.floor(255 * c + 0.5).to(torch.uint8)
+
+
+def evaluate_points(rec_pts, gt_pts, tau=0.05, icp_align=True, with_scaling=False):
+    """(PRResult, 4x4 applied to rec_pts): align_coarse_to_fine (identity without icp_align), then precision_recall at voxel tau / 2"""
+    T = align_coarse_to_fine(rec_pts, gt_pts, tau, with_scaling) if icp_align else np.eye(4)
+    moved = transform_points(rec_pts, T) if icp_align else as_points(rec_pts)
+    return precision_recall(moved, gt_pts, tau), T
+
+
+def pr_dict(res: PRResult) -> dict:
+    """the keys of run_evaluation that the reference's scripts read: shares in %, distances in cm"""
+    return {"precision": res.precision * 100, "recall": res.recall * 100, "f-score": res.fscore * 100,
+            "mean precision": res.mean_rec * 100, "mean recall": res.mean_gt * 100,
+            "median precision": res.median_rec * 100, "median recall": res.median_gt * 100}
+
+
+def run_evaluation(rec_mesh, gt_mesh, distance_thresh=0.05, icp_align=True, with_scaling=False, samples=N_SAMPLES, seed=0, out_dir=None):
+    """evaluate_3d_reconstruction.run_evaluation as eval_recon.py:232-235 calls it: `samples` surface samples per mesh (the streams of
+    calc_3d_metric), the coarse-to-fine alignment of the rec samples onto the GT samples, precision / recall / F-score at distance_thresh
+    over the clouds downsampled at half of it.  Returns plain floats: 'precision', 'recall', 'f-score' (%), 'mean precision', 'mean
+    recall', 'median precision', 'median recall' (cm; "precision" distances run rec -> GT, "recall" distances GT -> rec).  out_dir:
+    precision.ply / recall.ply (the downsampled rec / GT cloud coloured by error_colors) and pr_curve.txt (threshold, precision and
+    recall up to it, one line per histogram edge); no plot."""
+    rec_pc = sample_surface(rec_mesh, samples, seed=seed, stream=STREAM_REC)
+    gt_pc = sample_surface(gt_mesh, samples, seed=seed, stream=STREAM_GT)
+    res, _ = evaluate_points(rec_pc, gt_pc, distance_thresh, icp_align, with_scaling)
+    if out_dir is not None:
+        from .tsdf import write_ply
+        os.makedirs(out_dir, exist_ok=True)
+        for name, pts, d2 in (("precision", res.rec_points, res.dist2_rec), ("recall", res.gt_points, res.dist2_gt)):
+            col = error_colors(d2.double().sqrt(), distance_thresh)
+            write_ply(os.path.join(out_dir, f"{name}.ply"), Mesh(pts.cpu().numpy(), col.cpu().numpy(), np.zeros((0, 3), np.int32)))
+        with open(os.path.join(out_dir, "pr_curve.txt"), "w") as fh:
+            fh.write("# threshold precision recall\n")
+            for e, p, r in zip(res.edges[1:], res.cum_rec, res.cum_gt):
+                fh.write(f"{e:.9g} {p:.9g} {r:.9g}\n")
+    return pr_dict(res)
 
 
 # ------------------------------------------------------------------------------------------------------------------- 2-D metric
@@ -378,7 +548,16 @@ def parse_args(argv=None):
     p.add_argument("--traj-gt", type=str, default=None, help="TUM ground-truth trajectory")
     p.add_argument("--samples", type=int, default=N_SAMPLES, help="surface samples per mesh")
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--pr", action="store_true", help="also precision, recall and F-score (the reference's external run_evaluation): the keys "
+                   "'precision', 'recall', 'f-score' (%%), 'mean precision', 'mean recall', 'median precision', 'median recall' (cm)")
+    p.add_argument("--pr-thresh", type=float, default=0.05, help="distance threshold of --pr, metres")
+    p.add_argument("--pr-scale", action="store_true", help="the alignment of --pr also estimates a scale")
+    p.add_argument("--pr-out", type=str, default=None, metavar="DIR", help="write precision.ply, recall.ply and pr_curve.txt of --pr here")
     a = p.parse_args(argv)
+    if not a.pr and (a.pr_scale or a.pr_out is not None):
+        p.error("--pr-scale and --pr-out belong to --pr")
+    if not 0 < a.pr_thresh < float("inf"):
+        p.error("--pr-thresh must be > 0 and finite")
     if (a.traj_est is None) != (a.traj_gt is None):
         p.error("--traj-est and --traj-gt go together")
     if a.samples <= 0:
@@ -396,6 +575,8 @@ def main(argv=None):
     if a.traj_est is not None:
         rec = apply_transform(rec, sim3_from_trajectories(a.traj_est, a.traj_gt))
     extra = dict(eval_2d=True, n_imgs=a.n_imgs, unseen=None if a.unseen is None else np.load(a.unseen)) if a.eval_2d else {}
+    if a.pr:
+        extra.update(pr=True, pr_thresh=a.pr_thresh, pr_scale=a.pr_scale, pr_out=a.pr_out)
     result = eval_recon(rec, a.gt_mesh, eval_3d=True, align=not a.no_align, samples=a.samples, seed=a.seed, **extra)
     print(result)
     if a.save:

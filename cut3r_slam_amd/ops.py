@@ -1128,10 +1128,73 @@ class NNGrid:
                                     _stream()), "cut3r_icp_moments")
         return out
 
+    def moments_scaled(self, query, dist2, idx, transform=None):
+        """fp64 [18]: the 17 of moments(), bit for bit, and sum |src|^2 (csrc/prstats.hip): what a similarity update needs"""
+        Q = _points(query, "query")
+        _cuda(dist2, idx)
+        _req(dist2.shape == (Q,) and dist2.dtype == F32 and idx.shape == (Q,) and idx.dtype == torch.int32, "dist2 / idx of this query")
+        _req(int(idx.max()) < self.P, "idx: reference index out of range")
+        T = _transform34(transform, query.device)
+        lib = _lib.load()
+        nbytes = lib.cut3r_icp_moments_scaled_workspace_bytes(Q)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=query.device)
+        out = torch.empty(18, dtype=torch.float64, device=query.device)
+        check(lib.cut3r_icp_moments_scaled(_p(query), Q, _p(self.ref), self.P, _p(T), _p(dist2.contiguous()), _p(idx.contiguous()), _p(out),
+                                           _p(ws), nbytes, _stream()), "cut3r_icp_moments_scaled")
+        return out
+
 
 def nn_query(ref, query, max_dist=None, transform=None):
     """one-shot NNGrid(ref).query(query)"""
     return NNGrid(ref, query.shape[0] if query.dim() == 2 else 0).query(query, max_dist=max_dist, transform=transform)
+
+
+# ------------------------------------------------------------------------------------------------ precision / recall reductions
+DIST_STATS_MAX_BINS = 4096
+
+
+def _dist2(dist2):
+    _cuda(dist2)
+    _req(dist2.dim() == 1 and dist2.dtype == F32 and dist2.is_contiguous(), "dist2: contiguous fp32 [Q]")
+    _req(0 < dist2.shape[0] < 2 ** 31, "dist2: 1 .. 2^31 - 1 entries")
+    return dist2.shape[0]
+
+
+def dist_stats(dist2, tau, bin_width=None, nbins=0):
+    """(counts int64 [3], moments fp64 [4], hist int64 [nbins]) on the device, over the squared distances dist2 fp32 [Q] of NNGrid.query
+    (csrc/prstats.hip; include/cut3r_hip.h states the rule and the order of the sums): counts = (good entries, good entries with d =
+    sqrt(dist2) < tau, bad entries: NaN, negative, +inf), moments = (sum d, sum dist2, min d, max d), hist[k] = entries with k bin_width
+    <= d < (k + 1) bin_width.  nbins = 0: no histogram (bin_width may be None)."""
+    Q = _dist2(dist2)
+    nbins = int(nbins)
+    _req(0 <= nbins <= DIST_STATS_MAX_BINS, f"nbins: 0 .. {DIST_STATS_MAX_BINS}")
+    bin_width = float(tau) if bin_width is None and nbins == 0 else bin_width
+    _req(bin_width is not None, "bin_width: needed with nbins > 0")
+    tau, bin_width = float(tau), float(bin_width)
+    _req(tau > 0 and bin_width > 0, "tau and bin_width must be > 0")
+    lib = _lib.load()
+    nbytes = lib.cut3r_dist_stats_workspace_bytes(Q)
+    _req(nbytes > 0, "dist_stats workspace")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dist2.device)
+    counts = torch.empty(3, dtype=torch.int64, device=dist2.device)
+    moments = torch.empty(4, dtype=torch.float64, device=dist2.device)
+    hist = torch.empty(nbins, dtype=torch.int32, device=dist2.device)          # uint32 counts: Q < 2^31, so no sign
+    check(lib.cut3r_dist_stats(_p(dist2), Q, tau, bin_width, nbins, _p(counts), _p(moments), _p(hist) if nbins else _p(None), _p(ws), nbytes,
+                               _stream()), "cut3r_dist_stats")
+    return counts, moments, hist.long()
+
+
+def dist_median(dist2):
+    """fp32 [2] on the device: the dist2 values of ascending ranks (n - 1) / 2 and n / 2 among the n good entries of dist2 fp32 [Q] (NaN
+    when there is none), by a radix select (csrc/prstats.hip)"""
+    Q = _dist2(dist2)
+    lib = _lib.load()
+    nbytes = lib.cut3r_dist_median_workspace_bytes(Q)
+    _req(nbytes > 0, "dist_median workspace")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dist2.device)
+    out = torch.empty(2, dtype=F32, device=dist2.device)
+    check(lib.cut3r_dist_median(_p(dist2), Q, _p(out), _p(ws), nbytes, _stream()), "cut3r_dist_median")
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ mesh depth rasteriser, 2-D metric

@@ -10,7 +10,8 @@ the image centre) and <output>/calib_estimated.txt holds it for the input frames
 Writes <output>/traj_kf.txt and <output>/intrinsics.npy exactly as the reference does (evo-compatible TUM rows); with --mesh also
 <output>/tsdf_mesh_w{W:.1f}.ply per --mesh-weight, the reference's post-run mesh (TSDF fusion on the GPU, cut3r_slam_amd/tsdf.py), and with
 --mesh-simplify CELL and / or --mesh-min-faces N next to each of them tsdf_mesh_w{W:.1f}_clean.ply, that mesh after vertex clustering and
-small-component removal (cut3r_slam_amd/mesh_clean.py; scored into eval_recon_w{W:.1f}_clean.txt with --gt-mesh), and with
+small-component removal (cut3r_slam_amd/mesh_clean.py; scored into eval_recon_w{W:.1f}_clean.txt with --gt-mesh; --eval-pr adds
+precision, recall and F-score, the keys scripts/run_replica.py reads, to those files), and with
 --mesh-preview N <output>/tsdf_preview/{kf:05d}_{depth,normal,color}.png, the fused volume ray-cast at every N-th keyframe (--dense-source
 fused scores such depth maps in --eval-dense); with
 --eval-dense --gtdepthdir G --gt-traj T also <output>/3D_eval_results.txt, the dense point-cloud metrics of the keyframe depths against
@@ -118,6 +119,9 @@ def main(argv=None):
                    "the mesh before scoring (scripts/run_replica.py:45-46)")
     p.add_argument("--eval-2d", action="store_true", help="with --gt-mesh: also the 2-D metric (scripts/eval_recon.py calc_2d_metric), "
                    "'depth l1' in cm added to eval_recon_w{W:.1f}.txt")
+    p.add_argument("--eval-pr", action="store_true", help="with --gt-mesh: also precision, recall and F-score at 5 cm (the reference's "
+                   "external run_evaluation), the keys run_replica.py reads added to eval_recon_w{W:.1f}.txt")
+    p.add_argument("--eval-pr-scale", action="store_true", help="the alignment of --eval-pr also estimates a scale")
     p.add_argument("--gt-unseen", type=str, default=None, help="[N,3] .npy of GT points that no view of --eval-2d may see")
     p.add_argument("--n-imgs", type=int, default=10, help="views of --eval-2d (scripts/eval_recon.py:238)")
     p.add_argument("--eval-dense", action="store_true", help="score the keyframe depth maps against the GT depth maps of --gtdepthdir at the "
@@ -174,6 +178,10 @@ def main(argv=None):
         p.error("--mesh-min-faces must be >= 1")
     if args.eval_2d and not args.gt_mesh:
         p.error("--eval-2d needs --gt-mesh")
+    if args.eval_pr and not args.gt_mesh:
+        p.error("--eval-pr needs --gt-mesh")
+    if args.eval_pr_scale and not args.eval_pr:
+        p.error("--eval-pr-scale needs --eval-pr")
     if args.gt_unseen and not args.eval_2d:
         p.error("--gt-unseen needs --eval-2d")
     if args.n_imgs <= 0:
@@ -332,10 +340,14 @@ def main(argv=None):
                 import numpy as np
                 res.update(ER.calc_2d_metric(mesh, args.gt_mesh, n_imgs=args.n_imgs,
                                              unseen=np.load(args.gt_unseen) if args.gt_unseen else None))
+            if args.eval_pr:
+                res.update(ER.run_evaluation(mesh, args.gt_mesh, with_scaling=args.eval_pr_scale))
             with open(os.path.join(args.output, f"eval_recon_w{w:.1f}{tag}.txt"), "w") as fh:
                 fh.write(f"{res}")
             print(f"  vs {args.gt_mesh}: accuracy {res['accuracy']:.3f} cm, completion {res['completion']:.3f} cm, "
-                  f"completion ratio {res['completion_ratio']:.2f} %" + (f", depth L1 {res['depth l1']:.3f} cm" if args.eval_2d else ""))
+                  f"completion ratio {res['completion_ratio']:.2f} %" + (f", depth L1 {res['depth l1']:.3f} cm" if args.eval_2d else "")
+                  + (f", precision {res['precision']:.2f} %, recall {res['recall']:.2f} %, F-score {res['f-score']:.2f} %"
+                     if args.eval_pr else ""))
 
         for w in args.mesh_weight:
             t_ext = time.time()

@@ -704,6 +704,36 @@ long long cut3r_icp_moments_workspace_bytes(int Q);                   /* -1 when
 int cut3r_icp_moments(const float* src, int Q, const float* ref, int P, const float* T, const float* dist2, const int* idx, double* out,
                       void* workspace, long long workspace_bytes, void* stream);
 
+/* ---- Precision, recall, F-score (csrc/prstats.hip) ---------------------------------------------------------------------------------------
+ * The reductions behind evaluate_3d_reconstruction.run_evaluation (scripts/eval_recon.py:232-235; the Tanks-and-Temples evaluation) over
+ * the dist2 [Q] fp32 of cut3r_nn_query.  An entry s is BAD iff !(s >= 0) || s == +inf; it bumps counts[2] and nothing else.  A good entry
+ * has d = fabs(sqrt((double)s)) (fp64; the fabs turns the -0 of s = -0.0 into +0) and goes into
+ *   counts [3] int64   = (good entries, good entries with d < tau (strict), bad entries)
+ *   moments [4] fp64   = (sum d, sum (double)s, min d, max d); min = +inf and max = -inf without a good entry
+ *   hist [nbins] uint32: hist[k]++ for the largest integer k with (double)k * bin_width <= d, iff k < nbins -- np.histogram over
+ *                        np.arange(0, nbins + 1) * bin_width, except that d == nbins * bin_width is dropped (numpy's last edge is closed)
+ * nbins in 0..4096; hist may be NULL when nbins == 0.  The histogram is counted with integer atomics in LDS, then into hist; there is no
+ * floating-point atomic.  Order of the two sums: G = min(ceil(Q / 1024), 1024) workgroups of 256 threads; thread t of workgroup b adds the
+ * good ones among the entries 4 ((k G + b) 256 + t) + j, j = 0..3, k = 0, 1, ..., in increasing (k, j) from +0; the 256 thread sums fold
+ * by the halving tree s[t] += s[t + o], o = 128, ..., 1; the G workgroup sums are added in increasing b from +0.  Identical on every run
+ * and for every alignment of dist2.  One pass over dist2, nothing is read back.
+ * CUT3R_ERR_ARG before any launch (outputs untouched): a null dist2, counts, moments or workspace (hist with nbins > 0), Q <= 0, tau or
+ * bin_width <= 0 or NaN, nbins outside 0..4096, a workspace that is not 8-byte aligned or shorter than cut3r_dist_stats_workspace_bytes(Q). */
+long long cut3r_dist_stats_workspace_bytes(int Q);                    /* -1 when Q <= 0 */
+int cut3r_dist_stats(const float* dist2, int Q, double tau, double bin_width, int nbins, long long* counts, double* moments, unsigned* hist,
+                     void* workspace, long long workspace_bytes, void* stream);
+/* out [2] fp32 = the dist2 values of ascending ranks (n - 1) / 2 and n / 2 among the n good entries (-0.0 as +0.0), NaN when n == 0; n is
+ * counted on the device.  A radix select in four 8-bit passes over the bit pattern of the non-negative float, both ranks in the same
+ * passes (csrc/calib.hip's scheme); integer counts only, nothing is sorted.  Refusals as above. */
+long long cut3r_dist_median_workspace_bytes(int Q);                   /* -1 when Q <= 0 */
+int cut3r_dist_median(const float* dist2, int Q, float* out, void* workspace, long long workspace_bytes, void* stream);
+/* cut3r_icp_moments with the moment that a similarity update needs: out [18], out[0..16] bit for bit cut3r_icp_moments' (the same grid and
+ * order), out[17] = sum of ((double)x (double)x + (double)y (double)y) + (double)z (double)z of the fp32 source point under T, over the same
+ * correspondences in the same order.  workspace: cut3r_icp_moments_scaled_workspace_bytes(Q), 8-byte aligned. */
+long long cut3r_icp_moments_scaled_workspace_bytes(int Q);            /* -1 when Q <= 0 */
+int cut3r_icp_moments_scaled(const float* src, int Q, const float* ref, int P, const float* T, const float* dist2, const int* idx, double* out,
+                             void* workspace, long long workspace_bytes, void* stream);
+
 /* ---- Mesh depth rasteriser and the 2-D depth-L1 metric (csrc/raster.hip) -----------------------------------------------------------------
  * mesh_raster replaces the off-screen Open3D window of scripts/eval_recon.py:162-213 (capture_depth_float_buffer of a mesh drawn with
  * mesh_show_back_face and set_constant_z_far(20)).  verts [V,3] fp32, faces [F,3] int32 (a face with an index outside 0..V-1 is not
