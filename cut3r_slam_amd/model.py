@@ -16,6 +16,7 @@ head runs once per window over all views (it does not feed the recurrence), and 
 """
 from __future__ import annotations
 
+import contextlib
 import gc
 import math
 import os
@@ -146,6 +147,10 @@ class Cut3rModel:
         self._head_stream = None
         self._side = None
         self._head_side = None
+        # the encoder's static state (the `enc...` buffers, the static input / output of the captured "enc" and "win" graphs) belongs to one
+        # stream at a time: (stream, event) of the stream that ran the encoder last, and one reusable event per stream (_encoder_turn)
+        self._enc_last = None
+        self._enc_events: Dict[int, torch.cuda.Event] = {}
         self._prep(state_dict)
 
     # ------------------------------------------------------------------ reference-compatible constructors
@@ -396,8 +401,38 @@ class Cut3rModel:
         self._linear(h, p + ".fc2", out, res1=res, emit=emit)
 
     # ------------------------------------------------------------------ encoder
+    @contextlib.contextmanager
+    def _encoder_turn(self):
+        """One encoder pass at a time, whichever stream issues it: the pass that ran last left an event, and a pass on ANOTHER stream makes
+        its stream wait for that event before it touches the encoder's static state (eager: the `enc...` buffers; graphs: static input and
+        output of the "enc" / "win" replays, through the caller's copy of the output).  Stream-side waits only, no host synchronisation;
+        with one stream in use nothing is waited for, and nothing at all happens inside a capture (the guard sits around the replay).
+        Decoder passes are not ordered against it: a look-ahead encoder pass still runs beside the windows of the main stream
+        (`decode_window` / `decode_windows`, the trackers' path).  Two exceptions, both stated here: the graphed `forward_window` of IMAGES
+        is one replay of encoder + decoder + heads that cannot be split, so it takes its turn as a whole; and in graph mode `encode_image`
+        returns `pos` as the static output of the replay, read outside the turn -- every replay of a shape writes the same positions."""
+        if torch.cuda.is_current_stream_capturing():
+            yield
+            return
+        cur = torch.cuda.current_stream()
+        last = self._enc_last
+        if last is not None and last[0] != cur:
+            cur.wait_event(last[1])
+        try:
+            yield
+        finally:
+            ev = self._enc_events.get(cur.cuda_stream)
+            if ev is None:
+                ev = self._enc_events[cur.cuda_stream] = torch.cuda.Event()
+            ev.record(cur)
+            self._enc_last = (cur, ev)
+
     def _encode(self, img: torch.Tensor):
         """img [B,3,H,W] (fp32 normalised, or uint8 -> normalisation fused).  Returns fp32 feat [B,N,E], fp16 copy."""
+        with self._encoder_turn():
+            return self._encode_pass(img)
+
+    def _encode_pass(self, img: torch.Tensor):
         cfg = self.cfg
         B, _, H, W = img.shape
         P, E = cfg.patch_size, cfg.enc_embed_dim
@@ -479,8 +514,9 @@ class Cut3rModel:
         im_shape = view.get("true_shape", torch.tensor(img.shape[-2:])[None].repeat(B, 1))
         img = img.to(F32) if img.dtype != torch.uint8 else img
         if self.use_graphs:
-            feat, _, pos = self._graphed("enc", self._encode, img.contiguous())
-            feat = feat.clone()            # callers keep encoder features (keyframe store)
+            with self._encoder_turn():
+                feat, _, pos = self._graphed("enc", self._encode, img.contiguous())
+                feat = feat.clone()        # callers keep encoder features (keyframe store)
         else:
             feat, _, pos = self._encode(img)
         return feat, pos, im_shape
@@ -728,15 +764,17 @@ class Cut3rModel:
         """imgs [V,3,H,W] on the GPU (fp32 normalised or uint8).  Returns (list of V pred dicts, taps).
         With graphs enabled the prediction tensors are static buffers, valid until the next call."""
         if self.use_graphs and not return_taps:
-            return self._graphed("win", lambda x: self._forward_window(x, False), imgs.contiguous())
+            with self._encoder_turn():       # the window graph holds an encoder pass
+                return self._graphed("win", lambda x: self._forward_window(x, False), imgs.contiguous())
         return self._forward_window(imgs, return_taps)
 
     @torch.no_grad()
     def encode_batch(self, imgs: torch.Tensor) -> torch.Tensor:
         """encoder features fp32 [B,N,E] of B images (one batched pass; a fresh tensor the caller may keep)."""
         if self.use_graphs:
-            feat, _, _ = self._graphed("enc", self._encode, imgs.contiguous())
-            return feat.clone()
+            with self._encoder_turn():
+                feat, _, _ = self._graphed("enc", self._encode, imgs.contiguous())
+                return feat.clone()
         return self._encode(imgs)[0]
 
     @torch.no_grad()

@@ -106,15 +106,21 @@ class MotionFilter:
         the pass then runs BESIDE whatever the caller issues next on the current stream -- the previous chunk's tracking windows), with the
         decisions copied to pinned host memory behind an event.  `feat_last`: the features the chain starts from when they are not the
         store's last keyframe (the caller knows the last keyframe of the chunk still being consumed).  Returns the handle for
-        `prefetch_collect`; nothing of the filter's state changes until then."""
+        `prefetch_collect`; nothing of the filter's state changes until then.
+        Buffer lifetimes: the caller may drop `images_u8` and `feat_last` as soon as this returns -- device tensors it allocated on the current
+        stream are marked as in use on `stream` (record_stream), so the allocator hands their memory out again only once the pass has read it.
+        Host-resident images are uploaded on `stream` and must stay unchanged until `prefetch_collect`."""
         if self.kf_every > 0 or len(tstamps) == 0:
             return None
         kf = self.keyframes
         B = len(tstamps)
         cur = torch.cuda.current_stream()
         st = stream if stream is not None else cur
-        if st is not cur:
+        if st != cur:
             st.wait_stream(cur)                      # frames, keyframe store: everything issued so far
+            for t in (images_u8, feat_last):         # the caller's tensors, allocated on ITS stream and read on this one
+                if t is not None and t.is_cuda:
+                    t.record_stream(st)
         with torch.cuda.stream(st):
             imgs = images_u8.to(self.device, non_blocking=True)
             feats = self.model.encode_batch(imgs)                                         # [B,N,C] fp32, a fresh tensor
