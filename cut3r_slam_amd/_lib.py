@@ -224,6 +224,9 @@ SIGNATURES = {
     "cut3r_focal_median": [c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_ll, c_void_p],
     "cut3r_depth_consistency": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p] + [C.c_double] * 4
                                + [c_void_p] * 4,
+    "cut3r_gs_panel_ranges": [c_void_p, c_void_p, c_void_p, c_ll, c_void_p, c_void_p],
+    "cut3r_gs_panel": [c_void_p] * 8 + [c_float] * 4 + [c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "cut3r_gs_frame": [c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_float, c_void_p, c_void_p],
 }
 RESTYPES = {"cut3r_ba_workspace_floats": c_ll, "cut3r_gs_workspace_bytes": c_ll, "cut3r_schur_mono_prior_workspace_floats": c_ll,
             "cut3r_knn3_grid_workspace_bytes": c_ll, "cut3r_tsdf_mesh_workspace_bytes": c_ll, "cut3r_tsdf_sparse_assign_workspace_bytes": c_ll,

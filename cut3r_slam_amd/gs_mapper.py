@@ -17,10 +17,12 @@ rasteriser.  Mirrors, with the same names, argument meaning
 
 The reference's backend cannot run here (CUDA rasteriser, open3d, munch): PARITY UNPINNED, covered by functional tests on a
 synthetic scene (tests/test_gs_mapper_gpu.py).  The rasteriser and the 3-NN search are the HIP kernels of csrc/gs.hip; the loss
-terms and the Adam updates are plain torch tensor arithmetic on the GPU.  Not built: GUI and Gaussian ply export (PSNR / SSIM of the
+terms and the Adam updates are plain torch tensor arithmetic on the GPU.  Not built: the interactive GUI (PSNR / SSIM of the
 keyframes and -- eval_rendering -- of the whole sequence, LPIPS of both with the user's AlexNet weights -- cut3r_slam_amd/lpips.py,
 csrc/lpips.hip --, a safetensors checkpoint, -- cut3r_slam_amd/tsdf.py, fuse_mapper -- the TSDF mesh of the keyframe renders and
--- eval_recon.py -- its reconstruction metrics are).
+-- eval_recon.py -- its reconstruction metrics are; so are the reference's file products: finalize(out_dir=...) writes 3dgs_final.ply, the
+standard 3DGS file -- cut3r_slam_amd/gs_ply.py --, and gaussians_viz_{n}.ply, `viz` / `viz_dir` write the nine-cell panels composed by
+csrc/gs_panel.hip, and cut3r_slam_amd/gs_view.py renders a saved map along a trajectory).
 `gaussain_update` (the map correction after a loop closure, :701-774) composes rotations consistently by default; see its docstring."""
 from __future__ import annotations
 
@@ -98,6 +100,32 @@ class GaussianMap:
     @property
     def get_features(self):
         return self.theta[:, None, 3:6]                                   # [P,1,3]: SH degree 0, as the backend runs the model
+
+    # ---- the standard 3DGS file (gaussian_model.py:447-470 save_ply; cut3r_slam_amd/gs_ply.py)
+    def save_ply(self, path):
+        """a column dump of theta: x y z, zero normals, f_dc, opacity logit, log scales, the stored quaternion; no f_rest (SH degree 0)"""
+        from .gs_ply import write_gaussian_ply
+        th = self.theta.detach()
+        write_gaussian_ply(path, th[:, 0:3], th[:, 3:6], None, th[:, 6:7], th[:, 7:10], th[:, 10:14])
+
+    def load_ply(self, path):
+        """the map becomes the Gaussians of a degree-0 file; Adam moments, step count and densification statistics start over as for rows
+        that _append adds, and no Gaussian belongs to a keyframe (kf_id -1)"""
+        from .gs_ply import read_gaussian_ply
+        d = read_gaussian_ply(path)
+        if d["K"] != 1:
+            raise ValueError(f"{path}: {3 * (d['K'] - 1)} f_rest properties (SH degree > 0); the mapper's map runs at degree 0 -- read such a "
+                             "file with gs_ply.GaussianCloud.from_ply")
+        import numpy as np
+        rows = np.concatenate([d["xyz"], d["f_dc"], d["opacity"], d["scaling"], d["rotation"]], 1)
+        n = rows.shape[0]
+        z = lambda *s: torch.zeros(*s, device=self.device)
+        self.theta = torch.from_numpy(rows).to(self.device).requires_grad_(True)
+        self.m, self.v = z(n, 14), z(n, 14)
+        self.step_count, self.steps, self._steps_dev_stale = z(1), 0, False
+        self.kf_id = torch.full((n,), -1, dtype=torch.int32, device=self.device)
+        self.max_radii2D = z(n)
+        self.grad_accum, self.grad_accum_abs, self.denom = z(n, 1), z(n, 1), z(n, 1)
 
     # ---- growth
     def _append(self, new, kf_id):
@@ -474,6 +502,9 @@ class GSMapper:
         # pose_refine (tools/bench_fill.py measures both)
         self.pose_backward = "fused"
         self._trainer = None
+        # diagnostic panels (the reference's `verbose`): None = nothing is rendered or written; a directory = optimization() leaves
+        # <viz_dir>/rendering/ for the views of its window, finalize() <viz_dir>/rendering_final/ for every keyframe
+        self.viz_dir = None
 
     def _fused_trainer(self):
         if self._trainer is None:
@@ -634,6 +665,16 @@ class GSMapper:
         return idx
 
     def optimization(self, iters, optimize_pose=True, current_window=None, densify=False, graph=None):
+        """_optimization (below); with `viz_dir` set, the panels of the window's views go to <viz_dir>/rendering/ after the last iteration
+        (gs_backend_per_frame.py:588-593) -- outside the loop, so a captured iteration never contains them"""
+        last = self._optimization(iters, optimize_pose, current_window, densify, graph)
+        if self.viz_dir is not None:
+            import os
+            for k in current_window or ():
+                self.viz(self.viewpoints[k], os.path.join(self.viz_dir, "rendering"), k)
+        return last
+
+    def _optimization(self, iters, optimize_pose=True, current_window=None, densify=False, graph=None):
         """gs_backend_per_frame.py:451-587: L1 + SSIM colour, inverse-depth L1, depth-normal agreement with the keyframe depth, isotropy;
         Gaussians (and optionally the window's poses) step together; clone / split / prune at iters/4 and iters/2 when densifying.
         graph (default `self.use_graphs`): when the set of Gaussians stays fixed (no densification) and there are enough iterations,
@@ -802,10 +843,13 @@ class GSMapper:
         self.gaussians.zero_grad()
         return float(last) if last is not None else None
 
-    def finalize(self, iteration_total=None, path=None):
+    def finalize(self, iteration_total=None, path=None, out_dir=None):
         """gs_backend_per_frame.py:1067-1086: the closing global BA (the reference runs `max_steps` = position_lr_max_steps iterations),
         an optional checkpoint, and the keyframe poses camera->world [n,7] (t, q_xyzw) in keyframe order (the views added by
-        terminate() come after the tracker's keyframes, as in the reference's dict order)"""
+        terminate() come after the tracker's keyframes, as in the reference's dict order).  out_dir (default None: no file): after the
+        global BA, <out_dir>/gaussians_viz_{iteration_total}.ply (pcd_viz) and <out_dir>/3dgs_final.ply (the standard 3DGS file), the
+        reference's two products (:1071,1074); with `viz_dir` set also <viz_dir>/rendering_final/, one panel per keyframe."""
+        import os
         self.iteration_count = 0
         if iteration_total is None:
             iteration_total = int(self.config["opt_params"].get("position_lr_max_steps", 20000))
@@ -813,6 +857,13 @@ class GSMapper:
             self.global_BA(iteration_total=iteration_total)
         if path is not None:
             self.save(path)
+        if out_dir is not None:
+            os.makedirs(out_dir, exist_ok=True)
+            self.pcd_viz(os.path.join(out_dir, f"gaussians_viz_{iteration_total}.ply"))
+            self.gaussians.save_ply(os.path.join(out_dir, "3dgs_final.ply"))
+        if self.viz_dir is not None:
+            for k, v in self.viewpoints.items():
+                self.viz(v, os.path.join(self.viz_dir, "rendering_final"), k)
         with torch.no_grad():
             return torch.stack([SE3_from_matrix(torch.inverse(get_pose(v))) for v in self.viewpoints.values()])
 
@@ -949,6 +1000,41 @@ class GSMapper:
         depths = F.interpolate(torch.stack(depths)[None], size=size, mode="bilinear", align_corners=False)[0]
         return {"pointmaps": pms, "depths": depths, "poses": torch.stack(poses)}, list(current_window)
 
+
+    # ---- what a user looks at: the nine-cell panels of `viz` (gs_backend_per_frame.py:596-637) composed by csrc/gs_panel.hip, and the
+    #      coloured point cloud of `pcd_viz` (:639-647)
+    @torch.no_grad()
+    def panel(self, viewpoint):
+        """uint8 [3H,3W,3] on the device: gt | render | 10 |gt - exposure(render)| over turbo(gt depth) | turbo(depth) | turbo(|difference|)
+        over render normal | normal of the render depth | turbo(alpha > 0.5).  One render(), then two launches (ops.gs_panel; the
+        arithmetic is stated in include/cut3r_hip.h and restated by tests/gs_panel_oracle.py)."""
+        from . import ops
+        pkg = render(viewpoint, self.gaussians, self.background)
+        img = lambda t: t.detach().float().contiguous()
+        return ops.gs_panel(viewpoint.original_image, img(pkg["render"]), img(viewpoint.exposure_a), img(viewpoint.exposure_b), viewpoint.depth,
+                            img(pkg["depth"]), img(pkg["normal"]), img(pkg["mask"]), viewpoint.fx, viewpoint.fy, viewpoint.cx, viewpoint.cy)
+
+    def viz(self, viewpoint, dir, idx):
+        """the panel of one view as {dir}/{idx}_tstamp_{tstamp}.jpg (the reference's file name; PIL instead of torchvision.save_image)"""
+        import os
+
+        from PIL import Image
+        os.makedirs(dir, exist_ok=True)
+        path = os.path.join(dir, f"{idx}_tstamp_{viewpoint.tstamp}.jpg")
+        Image.fromarray(self.panel(viewpoint).cpu().numpy()).save(path)
+        return path
+
+    @torch.no_grad()
+    def pcd_viz(self, path):
+        """gs_backend_per_frame.py:639-647: the Gaussian centres as a coloured point cloud, colour = f_dc SH_C0 + 0.5 in fp32 clamped to
+        [0, 1], as bytes floor(c * 255 + 0.5) in fp64 (the panels' quantiser); a vertex-only PLY through tsdf.write_ply"""
+        import numpy as np
+
+        from .tsdf import Mesh, write_ply
+        th = self.gaussians.theta.detach()
+        col = (th[:, 3:6] * SH_C0 + 0.5).clamp(0.0, 1.0).double()
+        col = torch.floor(col * 255.0 + 0.5).to(torch.uint8)
+        write_ply(path, Mesh(th[:, 0:3].cpu().numpy(), col.cpu().numpy(), np.zeros((0, 3), np.int32)))
 
     # ---- checkpoint / evaluation (gs_backend_per_frame.py:1088-1096; gaussian/utils/eval_utils.py:110-150; LPIPS with an
     #      lpips.LPIPS object built from the user's weight files)

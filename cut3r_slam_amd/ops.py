@@ -1749,3 +1749,93 @@ def depth_consistency(depth, K, ref, src, fwd, bwd, depth_max, pix=1.0, rel=0.01
     check(_lib.load().cut3r_depth_consistency(_p(depth), _p(K), N, H, W, _p(ref_d), _p(src_d), R, S, _p(fwd_d), _p(bwd_d), depth_max, pix, rel,
                                               z_min, _p(support), _p(violation), _p(avg), _stream()), "cut3r_depth_consistency")
     return support, violation, avg
+
+
+# ------------------------------------------------------------------------------------------------ GS panels and frames
+PANEL_MAX_PIXELS = 2 ** 26
+FRAME_LAYERS = {"rgb": 0, "depth": 1, "normal": 2}
+
+
+def turbo_u8():
+    """the committed turbo byte table (csrc/turbo_u8.h, the kernels' own copy) as a numpy uint8 [256,3]"""
+    import re
+
+    import numpy as np
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "turbo_u8.h"), encoding="ascii") as fh:
+        body = "".join(ln for ln in fh if not ln.lstrip().startswith("//"))
+    t = np.array([int(v) for v in re.findall(r"\d+", body)], np.int64)
+    _req(t.size == 768 and int(t.max()) <= 255, "csrc/turbo_u8.h: 768 bytes expected")
+    return t.astype(np.uint8).reshape(256, 3)
+
+
+def _map(t, name, shape, dev=None):
+    _req(t.is_cuda and t.dtype == F32 and t.is_contiguous() and tuple(t.shape) == tuple(shape) and (dev is None or t.device == dev),
+         f"{name}: contiguous fp32 {list(shape)} on the GPU")
+
+
+def gs_panel_ranges(a=None, b=None, alpha=None):
+    """min / max of the maps a, b, |a - b| and (alpha > 0.5) in one launch (csrc/gs_panel.hip) -> the kernels' uint32 [8] device buffer
+    (include/cut3r_hip.h states its layout; gs_panel_ranges_decode gives floats).  The maps are fp32, equal in size, finite."""
+    maps = [t for t in (a, b, alpha) if t is not None]
+    _req(len(maps) > 0, "gs_panel_ranges: at least one map")
+    n = maps[0].numel()
+    _req(1 <= n < PANEL_MAX_PIXELS, f"gs_panel_ranges: 1 .. {PANEL_MAX_PIXELS - 1} elements")
+    for t in maps:
+        _map(t, "gs_panel_ranges", maps[0].shape, maps[0].device)
+    ranges = torch.empty(8, dtype=torch.int32, device=maps[0].device)
+    check(_lib.load().cut3r_gs_panel_ranges(_p(a), _p(b), _p(alpha), n, _p(ranges), _stream()), "cut3r_gs_panel_ranges")
+    return ranges
+
+
+def gs_panel_ranges_decode(ranges):
+    """the uint32 [8] buffer of gs_panel_ranges as host fp32 [4,2] = (min, max) of a, b, |a - b|, alpha > 0.5 (NaN for a map not given)"""
+    import numpy as np
+    k = ranges.cpu().numpy().view(np.uint32).reshape(4, 2).copy()
+    k[:, 0] = ~k[:, 0]
+    bits = np.where(k & np.uint32(0x80000000), k & np.uint32(0x7fffffff), ~k).astype(np.uint32)
+    return bits.view(np.float32)
+
+
+def gs_panel(gt, render, exposure_a, exposure_b, gt_depth, depth, normal, alpha, fx, fy, cx, cy):
+    """the nine-cell diagnostic panel uint8 [3H,3W,3] of one view in two launches (include/cut3r_hip.h states the cells and their arithmetic,
+    tests/gs_panel_oracle.py restates them): gt, render, normal fp32 [3,H,W]; gt_depth [H,W]; depth, alpha [1,H,W] or [H,W]; exposure_a
+    [3,3], exposure_b [3]; all on one GPU, contiguous, finite."""
+    _req(gt.dim() == 3 and gt.shape[0] == 3, "gt: [3,H,W]")
+    H, W = int(gt.shape[1]), int(gt.shape[2])
+    _req(H >= 1 and W >= 1 and H * W < PANEL_MAX_PIXELS, "gs_panel: H, W >= 1 and H W < 2^26")
+    dev = gt.device
+    depth, alpha, gt_depth = depth.reshape(H, W), alpha.reshape(H, W), gt_depth.reshape(H, W)
+    for t, name, shape in ((gt, "gt", (3, H, W)), (render, "render", (3, H, W)), (normal, "normal", (3, H, W)), (gt_depth, "gt_depth", (H, W)),
+                           (depth, "depth", (H, W)), (alpha, "alpha", (H, W)), (exposure_a, "exposure_a", (3, 3)), (exposure_b, "exposure_b", (3,))):
+        _map(t, name, shape, dev)
+    _req(float(fx) != 0.0 and float(fy) != 0.0, "gs_panel: fx, fy != 0")
+    ranges = gs_panel_ranges(gt_depth, depth, alpha)
+    out = torch.empty(3 * H, 3 * W, 3, dtype=torch.uint8, device=dev)
+    check(_lib.load().cut3r_gs_panel(_p(gt), _p(render), _p(exposure_a), _p(exposure_b), _p(gt_depth), _p(depth), _p(normal), _p(alpha), float(fx),
+                                     float(fy), float(cx), float(cy), H, W, _p(ranges), _p(out), _stream()), "cut3r_gs_panel")
+    return out
+
+
+def gs_frame(src, layer, depth_range=None):
+    """one layer of one image as uint8 [H,W,3] (csrc/gs_panel.hip, the panel's cell code): "rgb" and "normal" of src [3,H,W], "depth" of
+    src [H,W] or [1,H,W] in turbo over the map's own range (depth_range None: one more launch, no host read) or over a fixed (near, far)"""
+    _req(layer in FRAME_LAYERS, f"layer: one of {sorted(FRAME_LAYERS)}")
+    code = FRAME_LAYERS[layer]
+    if code == 1:
+        _req(src.dim() in (2, 3) and (src.dim() == 2 or src.shape[0] == 1), "depth: [H,W] or [1,H,W]")
+        src = src.reshape(src.shape[-2], src.shape[-1])
+    else:
+        _req(src.dim() == 3 and src.shape[0] == 3, f"{layer}: [3,H,W]")
+    H, W = int(src.shape[-2]), int(src.shape[-1])
+    _req(H >= 1 and W >= 1 and H * W < PANEL_MAX_PIXELS, "gs_frame: H, W >= 1 and H W < 2^26")
+    _map(src, layer, src.shape)
+    ranges, lo, hi = None, 0.0, 0.0
+    if code == 1 and depth_range is None:
+        ranges = gs_panel_ranges(src)
+    elif code == 1:
+        lo, hi = float(depth_range[0]), float(depth_range[1])
+        import math
+        _req(math.isfinite(lo) and math.isfinite(hi), "depth_range: finite (near, far)")
+    out = torch.empty(H, W, 3, dtype=torch.uint8, device=src.device)
+    check(_lib.load().cut3r_gs_frame(_p(src), code, H, W, _p(ranges), lo, hi, _p(out), _stream()), "cut3r_gs_frame")
+    return out

@@ -233,7 +233,8 @@ class Cut3rSlam:
         flush()
 
     @torch.no_grad()
-    def terminate(self, add_kf=False, gap=30, finalize_iters=None, gaussian_retrain=False, retrain_iters=10000, fill=False, fill_iters=100):
+    def terminate(self, add_kf=False, gap=30, finalize_iters=None, gaussian_retrain=False, retrain_iters=10000, fill=False, fill_iters=100,
+                  out_dir=None):
         """hi2.py:152-229.  With the Gaussian mapper attached (`self.mapper`) the extra views go to `mapper.add_new_view`, the mapper
         finalises (`GSMapper.finalize`: a global BA of `finalize_iters` iterations, default the configured position_lr_max_steps as the
         reference's `max_steps`; 0 skips it) and its poses are written back (hi2.py:214-216); `gaussian_retrain` rebuilds the map from all
@@ -245,7 +246,8 @@ class Cut3rSlam:
         pointmap [h,w,3], conf [h,w], submap).  Returns (keyframes.pose as numpy [buffer,7], new views).
         fill (hi2.py:218-221, needs the mapper and the kept frames): after the mapper has finalised, every frame from the first keyframe
         on gets a pose against the frozen map (trajectory_filler.PoseTrajectoryFiller, `fill_iters` iterations per frame); the result stays
-        in `self.traj_full` = (tstamps [n], poses [n,7] c2w) -- the return value does not change."""
+        in `self.traj_full` = (tstamps [n], poses [n,7] c2w) -- the return value does not change.
+        out_dir: handed to `GSMapper.finalize`, which then leaves 3dgs_final.ply and gaussians_viz_{n}.ply there (None: no file)."""
         kf = self.keyframes
         last = kf.counter.value
         views = []
@@ -280,7 +282,8 @@ class Cut3rSlam:
             with torch.enable_grad():
                 for v in views:                                           # hi2.py:203-211
                     self.mapper.add_new_view(v["image"], torch.as_tensor(v["pose"]), v["depth"], v["tstamp"], v["submap"])
-                poses = self.mapper.finalize(finalize_iters)
+                # (a mapper gets the keyword only when a directory is given: test doubles implement finalize(iters) alone)
+                poses = self.mapper.finalize(finalize_iters, **({"out_dir": out_dir} if out_dir is not None else {}))
             n = min(max(last - 1, 0), poses.shape[0])
             if n:
                 kf.set_poses_at(range(n), poses[:n].cpu().numpy())

@@ -19,7 +19,9 @@ the GT depth maps (scripts/eval7_scenes_dense.py, cut3r_slam_amd/eval_dense.py);
 --eval-dense are first cross-checked between neighbouring views (cut3r_slam_amd/depth_consistency.py; not in the reference); with --fill (implies --gs) also <output>/traj_full.txt,
 a pose for every frame from the first keyframe on (hislam2/util/trajectory_filler.py), and with --eval-render
 <output>/psnr/after_opt/final_result.json and <output>/renders/ (gaussian/utils/eval_utils.py:14-105; with --lpips-weights FILE... also
-mean_lpips, cut3r_slam_amd/lpips.py).  The viewers are out of scope:
+mean_lpips, cut3r_slam_amd/lpips.py).  With --gs also <output>/3dgs_final.ply (the standard 3DGS file) and <output>/gaussians_viz_{n}.ply, and with
+--gs-panels the mapper's diagnostic panels in <output>/rendering/ and <output>/rendering_final/ (python -m cut3r_slam_amd.gs_view renders
+the saved map along a trajectory).  The viewers are out of scope:
 --droidvis/--gsvis/--posedir/--weights are accepted and ignored, and so is --gtdepthdir without --eval-dense.  Without a checkpoint,
 `--synthetic-weights` runs the production-shape network with seeded random weights (throughput / plumbing runs only).
 """
@@ -89,6 +91,9 @@ def main(argv=None):
                    "position_lr_max_steps, as the reference; 0 skips it)")
     p.add_argument("--gs", action="store_true", help="attach the Gaussian-splatting mapper (hislam2/hi2.py:47-48 always does; needs the "
                    "Mapping / Training / opt_params sections of the config, config/scannet_config.yaml:44-79)")
+    p.add_argument("--gs-panels", action="store_true", help="with --gs: the mapper's nine-cell diagnostic panels (gt / render / error, depths in "
+                   "turbo, normals / mask; hislam2/gs_backend_per_frame.py:596-637) as JPEGs in <output>/rendering/ after every window and "
+                   "<output>/rendering_final/ for every keyframe at the end")
     p.add_argument("--fill", action="store_true", help="after the run, register every non-keyframe against the finished Gaussian map "
                    "(hislam2/util/trajectory_filler.py) -> <output>/traj_full.txt; implies --gs and keeps the frames on the device")
     p.add_argument("--fill-iters", type=int, default=100, help="pose iterations per filled frame (the reference: 100)")
@@ -152,6 +157,8 @@ def main(argv=None):
     if args.fill_iters <= 0:
         p.error("--fill-iters must be > 0")
     args.gs = args.gs or args.fill
+    if args.gs_panels and not args.gs:
+        p.error("--gs-panels needs --gs (the panels show the Gaussian map)")
     if args.lpips_weights and not args.gs:
         p.error("--lpips-weights needs --gs (LPIPS scores the renderings of the Gaussian map)")
     if args.undistort and not args.calib:
@@ -234,6 +241,14 @@ def main(argv=None):
             if "Training" not in cfg or "opt_params" not in cfg:
                 raise SystemExit("--gs needs the Training and opt_params sections in --config")
             s_.mapper_factory = lambda fx, fy, cx, cy: GSMapper(cfg, fx, fy, cx, cy, downsample_ratio=s_.downsample_ratio, device=args.device)
+            if args.gs_panels:                                            # (also for a mapper the tracker makes later, without --calib)
+                make = s_.mapper_factory
+
+                def with_panels(*K):
+                    m = make(*K)
+                    m.viz_dir = args.output
+                    return m
+                s_.mapper_factory = with_panels
             if intr_ds is not None:
                 s_.mapper = s_.mapper_factory(*[float(v) for v in intr_ds[0].reshape(-1)[:4]])
         return s_
@@ -281,7 +296,7 @@ def main(argv=None):
     if slam.mapper is not None and slam.mapper.viewpoints:
         fill = args.fill and getattr(slam.mapper, "initialized", False)
         # demo_s.py:171 (the keyframe trajectory above is the tracker's, as demo_s.py:168-169)
-        slam.terminate(add_kf=False, finalize_iters=args.gs_final_iters, fill=fill, fill_iters=args.fill_iters)
+        slam.terminate(add_kf=False, finalize_iters=args.gs_final_iters, fill=fill, fill_iters=args.fill_iters, out_dir=args.output)
         if fill:
             ts_full, poses_full = slam.traj_full
             stream.save_trajectory(slam, args.imagedir, args.output, start=args.start, traj_full=poses_full, traj_full_index=ts_full)

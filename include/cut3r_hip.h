@@ -920,6 +920,34 @@ int cut3r_depth_consistency(const float* depth, const float* K, int N, int H, in
                             const double* fwd, const double* bwd, double depth_max, double pix, double rel, double z_min,
                             unsigned char* support, unsigned char* violation, float* depth_avg, void* stream);
 
+/* ---- Diagnostic panels and frames of the Gaussian mapper (csrc/gs_panel.hip) ---------------------------------------------------------------
+ * hislam2/gs_backend_per_frame.py:596-637 `viz` (its nine cells) as two launches without a host round trip; cut3r_slam_amd/gs_view.py
+ * composes its frames with the same cell code.  All inputs device fp32, CHW, contiguous and FINITE (not checked); outputs uint8 HWC.
+ * Compiled without FMA contraction; tests/gs_panel_oracle.py restates the arithmetic and every byte is compared.
+ *   turbo cell   lo, hi = the map's fp32 min and max (apply_depth_colormap with near_plane = far_plane = None);
+ *                den = fp32(double(hi) - double(lo) + 1e-10); q = clip(fp32(x - lo) / den, 0, 1), the division correctly rounded;
+ *                idx = int(q * 255f) truncated; colour = TURBO_U8[idx] (csrc/turbo_u8.h: floor(T * 255 + 0.5) of matplotlib's table).
+ *   colour cell  v fp32 -> floor(clamp(double(v), 0, 1) * 255 + 0.5) in fp64 (torchvision save_image of the reference's float64 panel).
+ * ranges [8] uint32 (device) holds, for the four maps a, b, |a - b| and (alpha > 0.5 ? 1 : 0) in this order, the pair (~key(min), key(max)),
+ * key(f) = the order-preserving image of the float (bits ^ 0x80000000 for f >= +0, ~bits below): the kernel reduces with integer maxima,
+ * one atomicMax per value and workgroup, after a memset of the buffer on the stream (all zeros = nothing seen).  A NULL map leaves its
+ * slots (and a NULL a or b those of |a - b|) at zero.  Refused: NULL ranges, all three maps NULL, n < 1, n >= 2^26. */
+int cut3r_gs_panel_ranges(const float* a, const float* b, const float* alpha, long long n, unsigned int* ranges, void* stream);
+/* out [3H,3W,3]:   gt image               | render                         | abs(gt - e) * 10, e_c = ((r0 A[0,c] + r1 A[1,c]) + r2 A[2,c]) + b_c
+ *                  turbo(gt depth)        | turbo(render depth)            | turbo(abs(gt depth - render depth))
+ *                  (render normal + 1) / 2 | (normal of render depth + 1) / 2 | turbo(alpha > 0.5)
+ * ranges: cut3r_gs_panel_ranges(gt_depth, depth, alpha).  The normal of the render depth is gs_mapper.depth_to_normal:
+ * p = ((x - cx) / fx, (y - cy) / fy, 1) d, n = cross(p(x+1,y) - p(x-1,y), p(x,y+1) - p(x,y-1)) / max(sqrt((nx nx + ny ny) + nz nz), 1e-12),
+ * zero on the one-pixel border (byte 128); every product, sum, division and root rounded on its own.
+ * Refused: a NULL pointer, H or W < 1, H W >= 2^26, fx or fy == 0. */
+int cut3r_gs_panel(const float* gt, const float* render, const float* exposure_a, const float* exposure_b, const float* gt_depth,
+                   const float* depth, const float* normal, const float* alpha, float fx, float fy, float cx, float cy, int H, int W,
+                   const unsigned int* ranges, unsigned char* out, void* stream);
+/* out [H,W,3] of one layer: 0 = rgb (src [3,H,W], colour cell), 1 = depth (src [H,W], turbo cell; its range is slot 0 of `ranges`, i.e.
+ * cut3r_gs_panel_ranges(src, NULL, NULL), or with ranges == NULL the fixed lo, hi), 2 = normal (src [3,H,W], (n + 1) / 2 as a colour cell).
+ * Refused: NULL src / out, a layer outside 0..2, H or W < 1, H W >= 2^26. */
+int cut3r_gs_frame(const float* src, int layer, int H, int W, const unsigned int* ranges, float lo, float hi, unsigned char* out, void* stream);
+
 /* Measurement aid of bench.py's roofline (no reference counterpart; not on the product path): a bare MFMA loop (v_mfma_f32_16x16x32_f16,
  * 16 independent accumulator chains per wave, 8 waves per workgroup, `grid` workgroups, `iters` x 16 MFMAs per wave, operands = 16-byte
  * chunks of data[nhalf] fp16, nhalf a power of two >= 32768) with s_memtime / s_memrealtime stamps around the loop.  stamps [grid,2] u64 =
