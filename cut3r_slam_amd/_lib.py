@@ -171,6 +171,9 @@ SIGNATURES = {
     "cut3r_tsdf_sparse_mesh_workspace_bytes": [c_int],
     "cut3r_tsdf_sparse_mesh_count": [c_void_p] * 4 + [c_int] * 4 + [c_float, c_void_p, c_ll, c_void_p, c_void_p],
     "cut3r_tsdf_sparse_mesh_emit": [c_void_p] * 4 + [c_int] * 4 + [c_float] * 4 + [c_void_p, c_ll] + [c_void_p] * 3 + [c_ll, c_ll, c_void_p],
+    "cut3r_tsdf_live_integrate": [c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 4 + [c_float] * 4 + [c_void_p] * 3 + [c_int] * 6
+                                 + [c_float, c_void_p, c_void_p, C.c_uint, c_float, c_float, c_void_p],
+    "cut3r_tsdf_live_resolve": [c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 4,
     "cut3r_tsdf_ray_cast": [c_void_p] * 3 + [c_int] * 3 + [c_float] * 4 + [c_void_p, c_void_p] + [c_int] * 3 + [c_float] * 4 + [c_void_p] * 5,
     "cut3r_tsdf_sparse_ray_cast": [c_void_p] * 5 + [c_int] * 4 + [c_float] * 4 + [c_void_p, c_void_p] + [c_int] * 3 + [c_float] * 4
                                   + [c_void_p] * 5,

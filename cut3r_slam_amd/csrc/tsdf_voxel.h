@@ -168,6 +168,42 @@ DEVINL void tsdf_fuse_voxel(float* __restrict__ tsdf, float* __restrict__ weight
     }
 }
 
+// What ONE view contributes to the voxel at (px, py, pz), for the live volume (tsdf_live.hip), whose integer accumulators need the
+// sample and not the running average: the projection and every gate of tsdf_fuse_voxel above, restated in the same fixed order (z_c > 0,
+// the approximate-reciprocal early reject, the two correctly rounded divisions, floorf(u + 0.5f), the depth range, the confidence gate
+// at stride ds, sdf < -trunc).  v: the view's w2c rows [12], fx fy cx cy; depth [H,W] and conf [ch,cw] are the view's own planes.  False:
+// the view does not update the voxel; else t = fminf(1, sdf / trunc), in [-1, 1], and pix = vi * W + ui.  tests/test_tsdf_live_gpu.py
+// ties the two: a single view fused by either leaves the same voxels updated, with the same t.
+DEVINL bool tsdf_view_sample(float px, float py, float pz, const float* v, const float* __restrict__ depth, const float* __restrict__ conf,
+                             int H, int W, int ch, int cw, int ds, float conf_min, float trunc, float depth_max, float& t, int& pix) {
+    const float zc = ((v[8] * px + v[9] * py) + v[10] * pz) + v[11];
+    if (!(zc > 0.f)) return false;
+    const float xc = ((v[0] * px + v[1] * py) + v[2] * pz) + v[3];
+    const float yc = ((v[4] * px + v[5] * py) + v[6] * pz) + v[7];
+    if (zc > 1e-30f) {                                 // the early reject of tsdf_fuse_voxel: never drops what the exact test keeps
+        const float rz = __builtin_amdgcn_rcpf(zc);
+        const float ua = (v[12] * xc) * rz + v[14], va = (v[13] * yc) * rz + v[15];
+        const float mu = 1.f + 1e-6f * (fabsf(v[14]) + (float)W), mv = 1.f + 1e-6f * (fabsf(v[15]) + (float)H);
+        if (ua < -0.5f - mu || ua >= (float)W - 0.5f + mu || va < -0.5f - mv || va >= (float)H - 0.5f + mv) return false;
+    }
+    const float u = (v[12] * xc) / zc + v[14];
+    const float vv = (v[13] * yc) / zc + v[15];
+    const float uf = floorf(u + 0.5f), vf = floorf(vv + 0.5f);
+    if (!(uf >= 0.f && uf < (float)W && vf >= 0.f && vf < (float)H)) return false;
+    const int ui = (int)uf, vi = (int)vf;
+    pix = vi * W + ui;
+    const float d = depth[pix];
+    if (!(d > 0.f) || !(d <= depth_max)) return false;
+    if (conf) {
+        const int ci = min(vi / ds, ch - 1), cj = min(ui / ds, cw - 1);
+        if (conf[(long long)ci * cw + cj] < conf_min) return false;
+    }
+    const float sdf = d - zc;
+    if (sdf < -trunc) return false;
+    t = fminf(1.f, sdf / trunc);
+    return true;
+}
+
 // one triangle-mesh vertex on the edge from a voxel (tsdf t0, position p0, colours ca) to a neighbour (t1, p1, cb): s = t0 / (t0 - t1),
 // p = p0 + s (p1 - p0) per axis, colour ca + s (cb - ca) rounded floor(c + 0.5)
 DEVINL void mesh_vertex(float t0, float t1, const float* p0, const float* p1, const float* ca, const float* cb, float* __restrict__ vert,

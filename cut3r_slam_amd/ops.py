@@ -981,6 +981,68 @@ def tsdf_sparse_extract_mesh(tsdf, weight, color, table, bricks, dims, origin, v
         "tsdf_sparse", "sparse TSDF pool")
 
 
+# ------------------------------------------------------------------------------------------------ live TSDF volume
+TSDF_LIVE_Q = 32768                     # q = rint(t * 32768): the fixed point of a view's tsdf sample
+TSDF_LIVE_MAX_VIEWS = 65535             # views that may be in at once: 65535 * 32768 < 2^31
+
+
+def _tsdf_live_pool(acc, bricks, slots, T):
+    """acc int32 [5,nb,512] and bricks int32 [nb] on the GPU, slots int32 [ns] (ascending, distinct, in 0..nb-1: one read-back) or None
+    -> (nb, ns)"""
+    _cuda(acc, bricks, slots)
+    _req(acc.dim() == 3 and acc.shape[0] == 5 and acc.shape[2] == TSDF_BRICK_VOXELS and acc.dtype == torch.int32 and acc.is_contiguous(),
+         "acc: contiguous int32 [5,nb,512]")
+    nb = acc.shape[1]
+    _req(0 < nb <= T and nb * TSDF_BRICK_VOXELS < 2 ** 31, "live TSDF pool: 1 .. table entries bricks, fewer than 2^31 voxels")
+    _req(bricks.shape == (nb,) and bricks.dtype == torch.int32 and bricks.is_contiguous(), "bricks: contiguous int32 [nb]")
+    if slots is None:
+        return nb, 0
+    _req(slots.dim() == 1 and slots.dtype == torch.int32 and slots.is_contiguous(), "slots: contiguous int32 [ns]")
+    ns = slots.shape[0]
+    _req(1 <= ns <= nb, f"slots: 1..{nb} pool slots, got {ns}")
+    ok = (slots[0] >= 0) & (slots[-1] < nb) & (slots[1:] > slots[:-1]).all()
+    _req(bool(ok), f"slots: ascending distinct pool slots in 0..{nb - 1}")
+    return nb, ns
+
+
+def tsdf_live_integrate(acc, bricks, dims, origin, voxel, depth, w2c, K, trunc, depth_max, rgb=None, conf=None, conf_ds=1, conf_min=0.0,
+                        slots=None, subtract_mask=0):
+    """in place on the accumulators acc int32 [5,nb,512] (sum_q, count, sum_r, sum_g, sum_b) of a live volume: B <= 16 views put in -- or,
+    where bit b of subtract_mask is set, taken out -- in one launch, under the gates of tsdf_sparse_integrate.  slots: the pool slots to
+    visit (int32, ascending and distinct), None = all.  rgb None: the colour sums are left alone."""
+    X, Y, Z, T = _tsdf_sparse_grid(dims)
+    nb, ns = _tsdf_live_pool(acc, bricks, slots, T)
+    B, H, W, ch, cw = _tsdf_views("tsdf_live_integrate", depth, w2c, "w2c", K, voxel, trunc, TSDF_MAX_VIEWS, rgb, conf, conf_ds)
+    mask = int(subtract_mask)
+    _req(0 <= mask < (1 << B), f"subtract_mask {mask:#x}: a bit at or above the {B} views of the launch")
+    lib = _lib.load()
+    check(lib.cut3r_tsdf_live_integrate(_p(acc), _p(bricks), nb, _p(slots), ns, X, Y, Z, float(origin[0]), float(origin[1]), float(origin[2]),
+                                        float(voxel), _p(depth), _p(rgb), _p(conf), B, H, W, ch, cw, int(conf_ds), float(conf_min), _p(w2c),
+                                        _p(K), mask, float(trunc), float(depth_max), _stream()), "cut3r_tsdf_live_integrate")
+
+
+def tsdf_live_resolve(acc, tsdf, weight, color, slots=None):
+    """the accumulators as the fp32 pool planes of the sparse volume (tsdf [nb,512], weight [nb,512], color [3,nb,512], written in place on
+    the slots given, None = all): correctly rounded means; a voxel with count 0 reads tsdf 1, weight 0, colour 0"""
+    _cuda(acc, tsdf, weight, color, slots)
+    _req(acc.dim() == 3 and acc.shape[0] == 5 and acc.shape[2] == TSDF_BRICK_VOXELS and acc.dtype == torch.int32 and acc.is_contiguous(),
+         "acc: contiguous int32 [5,nb,512]")
+    nb = acc.shape[1]
+    _req(nb > 0 and nb * TSDF_BRICK_VOXELS < 2 ** 31, "live TSDF pool: at least one brick, fewer than 2^31 voxels")
+    _req(tsdf.shape == (nb, TSDF_BRICK_VOXELS) and tsdf.dtype == F32 and tsdf.is_contiguous(), "tsdf: contiguous fp32 [nb,512]")
+    _req(weight.shape == tsdf.shape and weight.dtype == F32 and weight.is_contiguous(), "weight: contiguous fp32 like tsdf")
+    _req(color.shape == (3, nb, TSDF_BRICK_VOXELS) and color.dtype == F32 and color.is_contiguous(), "color: contiguous fp32 [3,nb,512]")
+    _aligned(16, acc=acc, tsdf=tsdf, weight=weight, color=color)
+    ns = 0
+    if slots is not None:
+        _req(slots.dim() == 1 and slots.dtype == torch.int32 and slots.is_contiguous(), "slots: contiguous int32 [ns]")
+        ns = slots.shape[0]
+        _req(1 <= ns <= nb, f"slots: 1..{nb} pool slots, got {ns}")
+        _req(bool((slots[0] >= 0) & (slots[-1] < nb) & (slots[1:] > slots[:-1]).all()), f"slots: ascending distinct pool slots in 0..{nb - 1}")
+    lib = _lib.load()
+    check(lib.cut3r_tsdf_live_resolve(_p(acc), nb, _p(slots), ns, _p(tsdf), _p(weight), _p(color), _stream()), "cut3r_tsdf_live_resolve")
+
+
 # ------------------------------------------------------------------------------------------------ ray cast of the TSDF volumes
 def _tsdf_cast(what, dev, c2w, K, H, W, t_min, t_max, step, voxel, normals, colors, count):
     """the views and the outputs of a ray-cast launch: c2w [B,12], K [B,4] fp32 on the GPU, B <= 16 -> (B, H, W, depth [B,H,W], normal

@@ -66,6 +66,36 @@ class Cut3rSlam:
         # reference never changes keyframes.depth and later windows chain on the tracker's own depths.  Default = that effective
         # behaviour; True writes the mapper's scale-corrected depths back (what the line looks like it wants) -- a declared deviation
         self.gs_depth_writeback = False
+        # a dense model kept current during the run (tsdf.LiveTSDFVolume): None until start_live_volume() has been called and the first
+        # keyframes are there; then synced with the tracked keyframes at the end of every run() and of terminate()
+        self.live_volume = None
+        self._live_options = None
+
+    def start_live_volume(self, voxel_size, half_extent, depth_max=5.0, trunc_voxels=8.0, conf_min=None):
+        """keep a tsdf.LiveTSDFVolume of the tracked keyframes (the views of fuse(source="tracker")) while the run goes on: a cube of half
+        side `half_extent` around the first keyframe's camera, created at the first sync.  Loop closure, the Sim(3) correction and the
+        mapper's write-back rewrite poses and depths of keyframes that are already in; every sync re-poses exactly those, so
+        `live_volume` always equals a fresh fusion of the store as it stands (tsdf.LiveTSDFVolume.sync).  conf_min: the confidence gate
+        of fuse_keyframes.  Call it before the first frame; the trajectory does not depend on it."""
+        if not voxel_size > 0 or not half_extent > 0:
+            raise ValueError("voxel_size and half_extent must be > 0")
+        self._live_options = dict(voxel_size=float(voxel_size), half_extent=float(half_extent), depth_max=float(depth_max),
+                                  trunc_voxels=float(trunc_voxels), conf_min=conf_min)
+
+    def _sync_live(self):
+        """(added, updated) of the live volume's sync with the tracked keyframes; None while there is nothing to sync"""
+        opt = self._live_options
+        kf = self.keyframes
+        # the keyframes of fuse(source="tracker") that the tracker has been through: one registered by the motion filter and still waiting
+        # for its window has no pose yet.  The last frame flushes the tracker, so at the end of a run these are all of them.
+        n = min(run_views(self, "tracker")[1], self.tracker.t1)
+        if n <= 0 or not float(kf.intrinsic[0, 0]) > 0:                   # (no keyframe yet, or a run still waiting for its calibration)
+            return None
+        if self.live_volume is None:
+            from .tsdf import LiveTSDFVolume
+            self.live_volume = LiveTSDFVolume.around(kf.pose[0][:3].numpy().astype(np.float64), opt["half_extent"], opt["voxel_size"],
+                                                     trunc_voxels=opt["trunc_voxels"], depth_max=opt["depth_max"], device=self.device)
+        return self.live_volume.sync(kf, n, conf_min=opt["conf_min"])
 
     def _on_calibrated(self, fx, fy, cx, cy):
         self.calibration = {"intrinsics": (fx, fy, cx, cy), "per_view": self.tracker.calibration.per_view.copy()}
@@ -141,6 +171,8 @@ class Cut3rSlam:
                 self.freeze_counter += 1
         if viz_idx is not None and self.mapper is not None:
             self.call_gs(viz_idx, submap_idx, self.gs_iter_num, intrinsics_ds)
+        if self._live_options is not None:
+            self._sync_live()
         return viz_idx, submap_idx, lc_did
 
     @torch.no_grad()
@@ -290,6 +322,8 @@ class Cut3rSlam:
             if fill:
                 from .trajectory_filler import PoseTrajectoryFiller
                 self.traj_full = PoseTrajectoryFiller(self).run(self.images, iters=fill_iters)
+        if self._live_options is not None:                                # after the final pose write-back
+            self._sync_live()
         return kf.pose.numpy().copy(), views
 
     def trajectory(self):

@@ -10,7 +10,9 @@ of the Gaussian map go into an Open3D VoxelBlockGrid and `tsdf_mesh_w{w:.1f}.ply
   fuse_keyframes   the tracker's keyframe store (depth, image, w2c, intrinsics, optional confidence gate) -> TSDFVolume
   fuse_mapper      the reference's source: every mapper keyframe rendered at its refined pose, quantised as the reference's files are
                    (hislam2/gaussian/utils/eval_utils.py:124-134: depth uint16 at 6553.5 per metre, colour (x*255) truncated to u8)
-  ray_cast         (both volumes) depth, normal and colour images of the fused model at given poses, marched through the voxels
+  LiveTSDFVolume   the sparse volume's lattice and bricks with integer accumulators (csrc/tsdf_live.hip): views are added, removed and
+                   re-posed exactly while a run goes on, and the volume always equals a fresh fusion of the views that are in
+  ray_cast         (all volumes) depth, normal and colour images of the fused model at given poses, marched through the voxels
                    (csrc/tsdf_raycast.hip: Open3D's VoxelBlockGrid.ray_cast); shade / write_previews turn them into PNGs
   write_ply / read_ply   binary little-endian PLY (x y z float, red green blue uchar, vertex_indices uchar count + int32)
 
@@ -300,15 +302,302 @@ class SparseTSDFVolume(_Volume):
     def to_dense(self):
         """(tsdf [Z,Y,X], weight [Z,Y,X], color [3,Z,Y,X]) of the virtual grid, 1 / 0 / 0 where nothing is allocated (raises above the
         dense limit of 2^31 - 1 voxels)"""
-        X, Y, Z = self._dense_dims()
-        BX, BY, BZ = self.brick_dims
-        t = self.bricks.long()
-        bx, by, bz = t % BX, (t // BX) % BY, t // (BX * BY)
-        out = []
-        for pool, init in ((self.tsdf, 1.0), (self.weight, 0.0), (self.color[0], 0.0), (self.color[1], 0.0), (self.color[2], 0.0)):
-            d = torch.full((BZ, 8, BY, 8, BX, 8), init, dtype=torch.float32, device=self.device)
-            d[bz, :, by, :, bx, :] = pool.reshape(-1, 8, 8, 8)
-            out.append(d.reshape(BZ * 8, BY * 8, BX * 8)[:Z, :Y, :X].contiguous())
+        out = _dense_from_bricks(self.bricks, self.brick_dims, self._dense_dims(), (self.tsdf, self.weight, *self.color), (1.0, 0.0, 0.0, 0.0, 0.0))
+        return out[0], out[1], torch.stack(out[2:])
+
+
+def _dense_from_bricks(bricks, brick_dims, dims, pools, inits):
+    """per pool plane [nb,512] of a brick volume: the plane [Z,Y,X] of the virtual grid, `init` where no brick is allocated"""
+    X, Y, Z = dims
+    BX, BY, BZ = brick_dims
+    t = bricks.long()
+    bx, by, bz = t % BX, (t // BX) % BY, t // (BX * BY)
+    out = []
+    for pool, init in zip(pools, inits):
+        d = torch.full((BZ, 8, BY, 8, BX, 8), init, dtype=pool.dtype, device=pool.device)
+        d[bz, :, by, :, bx, :] = pool.reshape(-1, 8, 8, 8)
+        out.append(d.reshape(BZ * 8, BY * 8, BX * 8)[:Z, :Y, :X].contiguous())
+    return out
+
+
+class LiveRecord(NamedTuple):
+    """a view that is in a LiveTSDFVolume, as the volume's own device copies: exactly the bits that put it in, so that taking it out
+    replays them (the keyframe store rewrites poses and depths in place)"""
+    depth: torch.Tensor         # float32 [H,W]
+    w2c: torch.Tensor           # float32 [12]
+    K: torch.Tensor             # float32 [4]
+    rgb: torch.Tensor           # uint8 [3,H,W], None in a colourless volume
+    conf: torch.Tensor          # float32 [h,w] at stride conf_ds, None without a gate
+    conf_ds: int
+    conf_min: float
+
+    @property
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in (self.depth, self.w2c, self.K, self.rgb, self.conf) if t is not None)
+
+    def launch_key(self):
+        """views that can share a launch: one image size and one confidence gate"""
+        return (tuple(self.depth.shape), None if self.conf is None else (tuple(self.conf.shape), self.conf_ds, self.conf_min))
+
+
+class LiveTSDFVolume(_Volume):
+    """A TSDF volume that is kept current while a run goes on: views are added, removed and re-posed EXACTLY.  The lattice, the brick
+    table (flags, table, bricks; mark and assign), the mesh extraction and the ray cast are SparseTSDFVolume's; the pool holds integer
+    accumulators (csrc/tsdf_live.hip) instead of a running fp32 average:
+
+        acc int32 [5,nb,512]   sum_q, count, sum_r, sum_g, sum_b      q = rint(32768 * min(1, sdf / trunc)) per view, exact
+
+    Integer sums commute and a subtraction undoes an addition, so acc depends on the SET of views that are in and on nothing else: after
+    any history of add / remove / update it equals, bit for bit, a fresh volume given the final views (on the bricks that one allocates;
+    bricks are never freed, so this one may hold more).  A brick allocated late catches up on every view already in -- the volume keeps
+    its own copy of each (LiveRecord), keyed by an integer id.  The mesh and the ray cast read fp32 planes resolved from acc as correctly
+    rounded means: they are NOT the bits of SparseTSDFVolume, whose running average rounds at every view; the tsdf differs by at most
+    2^-16 + 3 n 2^-24 after n views.
+
+    color: whether colour is accumulated, fixed for the volume's life; every view then comes with rgb, or none does.
+    Limits: SparseTSDFVolume's, and at most 65535 views in at once (65535 * 32768 < 2^31)."""
+
+    def __init__(self, origin, voxel_size, dims, trunc_voxels=8.0, depth_max=5.0, device="cuda:0", color=True):
+        X, Y, Z = (int(d) for d in dims)
+        if min(X, Y, Z) <= 0 or max(X, Y, Z) > ops.TSDF_SPARSE_MAX_DIM:
+            raise ValueError(f"live TSDF grid {X}x{Y}x{Z}: dims must be in 1..{ops.TSDF_SPARSE_MAX_DIM} per axis")
+        BX, BY, BZ = ops.tsdf_brick_dims((X, Y, Z))
+        if BX * BY * BZ > ops.TSDF_SPARSE_MAX_TABLE:
+            raise ValueError(f"live TSDF grid {X}x{Y}x{Z}: {BX * BY * BZ} bricks exceed the table limit of {ops.TSDF_SPARSE_MAX_TABLE} entries")
+        super().__init__(origin, voxel_size, (X, Y, Z), trunc_voxels, depth_max, device)
+        self.brick_dims = (BX, BY, BZ)
+        self.colored = bool(color)
+        self.flags = torch.zeros(BZ, BY, BX, dtype=torch.uint8, device=self.device)
+        self.table = torch.full((BZ, BY, BX), -1, dtype=torch.int32, device=self.device)
+        self.bricks = torch.zeros(0, dtype=torch.int32, device=self.device)
+        self.acc = torch.zeros(5, 0, ops.TSDF_BRICK_VOXELS, dtype=torch.int32, device=self.device)
+        self.records = {}                       # id -> LiveRecord of every view that is in
+        self._planes = None                     # (tsdf, weight, color) resolved from acc; None after any change
+
+    grid_for = staticmethod(SparseTSDFVolume.grid_for)
+
+    @classmethod
+    def from_bounds(cls, lo, hi, voxel_size, pad=None, max_bricks=ops.TSDF_SPARSE_MAX_TABLE, trunc_voxels=8.0, depth_max=5.0, device="cuda:0",
+                    color=True):
+        """the virtual grid covering the box [lo, hi] padded by `pad` (default: the truncation distance); nothing is allocated yet"""
+        pad = trunc_voxels * voxel_size if pad is None else pad
+        origin, dims = cls.grid_for(lo, hi, voxel_size, pad, max_bricks)
+        return cls(origin, voxel_size, dims, trunc_voxels=trunc_voxels, depth_max=depth_max, device=device, color=color)
+
+    @classmethod
+    def around(cls, center, half_extent, voxel_size, trunc_voxels=8.0, depth_max=5.0, device="cuda:0", color=True):
+        """the virtual grid as a cube of half side `half_extent` around `center` -- a run does not know its bounds up front.  Raises, with
+        the table's size, past the table limits; views that reach outside the cube are clipped to it."""
+        if not float(half_extent) > 0:
+            raise ValueError("half_extent must be > 0")
+        c = np.asarray(center, np.float64).reshape(3)
+        return cls.from_bounds(c - float(half_extent), c + float(half_extent), voxel_size, pad=0.0, trunc_voxels=trunc_voxels,
+                               depth_max=depth_max, device=device, color=color)
+
+    @property
+    def n_bricks(self):
+        return int(self.bricks.shape[0])
+
+    @property
+    def nbytes(self):
+        """accumulators (20 B per allocated voxel) + brick list + table and flags (5 B per brick of the virtual grid) + the records + the
+        resolved planes when they exist (another 20 B per allocated voxel)"""
+        n = (20 * ops.TSDF_BRICK_VOXELS + 4) * self.n_bricks + 5 * self.table.numel() + sum(r.nbytes for r in self.records.values())
+        return n + (20 * ops.TSDF_BRICK_VOXELS * self.n_bricks if self._planes is not None else 0)
+
+    # ------------------------------------------------------------------------------------------------------------------ the pool
+    def _allocate(self, depth, w2c, K):
+        """SparseTSDFVolume.allocate on the accumulators; returns the pool slots that are new (int32, ascending), None when there is none"""
+        c2w = torch.from_numpy(c2w_rows(w2c.cpu().numpy())).to(self.device)
+        ops.tsdf_sparse_mark(self.flags, self.dims, self.origin, self.voxel_size, depth, c2w, K, self.trunc, self.depth_max)
+        old = self.bricks
+        n = ops.tsdf_sparse_assign(self.flags, self.table, self.dims)
+        if n == old.shape[0]:
+            return None
+        if n * ops.TSDF_BRICK_VOXELS >= 2 ** 31:
+            raise ValueError(f"live TSDF pool of {n} bricks: 2^31 voxels or more ({n * ops.TSDF_BRICK_VOXELS * 20 / 1e9:.1f} GB)")
+        self.bricks = torch.nonzero(self.flags.reshape(-1)).reshape(-1).to(torch.int32)
+        self._planes = None
+        return self._regrow(old, n)
+
+    def _regrow(self, old, n):
+        """the pool of n bricks with the accumulators of the bricks `old` moved to their new slots (a copy of the whole pool); returns the
+        other slots (int32, ascending), which start at zero"""
+        acc = torch.zeros(5, n, ops.TSDF_BRICK_VOXELS, dtype=torch.int32, device=self.device)
+        fresh = torch.ones(n, dtype=torch.bool, device=self.device)
+        if old.shape[0]:
+            slot = self.table.reshape(-1)[old.long()].long()           # where the bricks that were there have moved
+            acc[:, slot] = self.acc
+            fresh[slot] = False
+        self.acc = acc
+        return torch.nonzero(fresh).reshape(-1).to(torch.int32)
+
+    def _apply(self, items, slots=None):
+        """items: (LiveRecord, subtract) pairs -> launches of <= 16 views that share an image size and a gate, over `slots` (None: all)"""
+        if self.n_bricks == 0 or not items:
+            return
+        groups = {}
+        for rec, sub in items:
+            groups.setdefault(rec.launch_key(), []).append((rec, sub))
+        for group in groups.values():
+            for a in range(0, len(group), ops.TSDF_MAX_VIEWS):
+                part = group[a:a + ops.TSDF_MAX_VIEWS]
+                recs = [r for r, _ in part]
+                r0 = recs[0]
+                ops.tsdf_live_integrate(
+                    self.acc, self.bricks, self.dims, self.origin, self.voxel_size, torch.stack([r.depth for r in recs]),
+                    torch.stack([r.w2c for r in recs]), torch.stack([r.K for r in recs]), self.trunc, self.depth_max,
+                    rgb=torch.stack([r.rgb for r in recs]) if self.colored else None,
+                    conf=None if r0.conf is None else torch.stack([r.conf for r in recs]), conf_ds=r0.conf_ds, conf_min=r0.conf_min,
+                    slots=slots, subtract_mask=sum(1 << b for b, (_, sub) in enumerate(part) if sub))
+        self._planes = None
+
+    def _ids(self, ids, present):
+        ids = [int(i) for i in (ids.tolist() if hasattr(ids, "tolist") else ids)]
+        if len(set(ids)) != len(ids):
+            raise ValueError(f"view ids {ids}: an id is given twice")
+        for i in ids:
+            if (i in self.records) != present:
+                raise ValueError(f"view id {i} is {'not in' if present else 'already in'} the live volume")
+        return ids
+
+    # ----------------------------------------------------------------------------------------------------------------- the views
+    @torch.no_grad()
+    def add(self, ids, depth, w2c, K, rgb=None, conf=None, conf_ds=1, conf_min=None):
+        """put B views in under the ids given (integers not in use): the arguments of TSDFVolume.integrate.  The bricks these views need
+        are allocated, the ones that are new catch up on every view already in, then the new views go into all bricks."""
+        ids = self._ids(ids, present=False)
+        if (rgb is not None) != self.colored:
+            raise ValueError("a coloured live volume takes every view with rgb, a colourless one takes none with it")
+        if len(self.records) + len(ids) > ops.TSDF_LIVE_MAX_VIEWS:
+            raise ValueError(f"more than {ops.TSDF_LIVE_MAX_VIEWS} views in a live volume: the int32 accumulators could overflow")
+        depth, w2c, K, rgb, conf = _stack(self.device, depth, w2c, K, rgb, conf, conf_min)
+        if depth.shape[0] != len(ids):
+            raise ValueError(f"{len(ids)} ids, {depth.shape[0]} depth maps")
+        depth, w2c, K = depth.clone(), w2c.clone(), K.clone()            # the volume's own copies
+        rgb, conf = (None if t is None else t.clone() for t in (rgb, conf))
+        ops._tsdf_views("LiveTSDFVolume.add", depth, w2c, "w2c", K, self.voxel_size, self.trunc, None, rgb, conf, conf_ds)
+        gate = (int(conf_ds), float(conf_min)) if conf is not None else (1, 0.0)
+        new = [LiveRecord(depth[b], w2c[b], K[b], None if rgb is None else rgb[b], None if conf is None else conf[b], *gate)
+               for b in range(len(ids))]
+        fresh = self._allocate(depth, w2c, K)
+        if fresh is not None:
+            self._apply([(r, False) for r in self.records.values()], slots=fresh)
+        self._apply([(r, False) for r in new])
+        self.records.update(zip(ids, new))
+        return self
+
+    @torch.no_grad()
+    def remove(self, ids):
+        """take the views out: one subtracting launch per 16, the exact inverse of what put them in.  Bricks are never freed."""
+        ids = self._ids(ids, present=True)
+        self._apply([(self.records[i], True) for i in ids])
+        for i in ids:
+            del self.records[i]
+        return self
+
+    @torch.no_grad()
+    def update(self, ids, w2c=None, depth=None):
+        """re-pose views that are in and / or replace their depth maps (None keeps what is recorded): w2c [B,12] (or [B,3,4] / [B,4,4]),
+        depth [B,H,W] of the recorded size.  The bricks the new versions need are allocated and catch up on every record as it stands --
+        the old versions of these views included, since the launches that follow take those out of every brick; old (subtracted) and new
+        (added) versions then share launches, so a voxel both see is read and written once."""
+        ids = self._ids(ids, present=True)
+        if not ids or (w2c is None and depth is None):
+            return self
+        old = [self.records[i] for i in ids]
+        B = len(ids)
+        if w2c is not None:
+            w2c = views.pose_rows(w2c, torch.float32, single=True).reshape(-1, 12).to(self.device).clone()
+            if w2c.shape[0] != B:
+                raise ValueError(f"{B} ids, {w2c.shape[0]} poses")
+        if depth is not None:
+            depth = torch.as_tensor(depth).to(self.device, torch.float32)
+            depth = (depth[None] if depth.dim() == 2 else depth).clone()
+            if depth.shape[0] != B or any(tuple(depth.shape[1:]) != tuple(r.depth.shape) for r in old):
+                raise ValueError(f"depth {tuple(depth.shape)}: {B} maps of the recorded size are expected")
+        new = [r._replace(w2c=r.w2c if w2c is None else w2c[b], depth=r.depth if depth is None else depth[b]) for b, r in enumerate(old)]
+        for key in {r.launch_key() for r in new}:                        # mark takes views of one size at a time
+            part = [r for r in new if r.launch_key() == key]
+            fresh = self._allocate(torch.stack([r.depth for r in part]), torch.stack([r.w2c for r in part]), torch.stack([r.K for r in part]))
+            if fresh is not None:
+                self._apply([(r, False) for r in self.records.values()], slots=fresh)
+        self._apply([pair for o, n in zip(old, new) for pair in ((o, True), (n, False))])
+        self.records.update(zip(ids, new))
+        return self
+
+    @torch.no_grad()
+    def sync(self, keyframes, n, conf_min=None):
+        """bring the volume up to the tracker's keyframe store, keyframe i under id i: keyframes len(records) .. n-1 are added (depth,
+        image when the volume is coloured, w2c, intrinsics and, with conf_min, the stored confidence gate, as fuse_keyframes takes them),
+        and the keyframes already in whose stored w2c row or depth plane no longer has the recorded bits are updated -- one batched
+        comparison on the device and one read-back.  Returns (added, updated); with nothing changed no integrate is launched."""
+        kf = keyframes
+        n, m = int(n), len(self.records)
+        if sorted(self.records) != list(range(m)):
+            raise ValueError("sync needs the views in to be keyframes 0 .. m-1")
+        if n < m:
+            raise ValueError(f"{m} keyframes are in the volume, the store has {n}")
+        changed = []
+        if m:
+            recs = [self.records[i] for i in range(m)]
+            dw = (torch.stack([r.w2c for r in recs]).view(torch.int32) != kf.w2c[:m].view(torch.int32)).any(1)
+            dd = (torch.stack([r.depth for r in recs]).view(torch.int32) != kf.depth[:m].view(torch.int32)).flatten(1).any(1)
+            changed = torch.nonzero(dw | dd).reshape(-1).cpu().tolist()
+        if changed:
+            idx = torch.as_tensor(changed, device=kf.w2c.device)
+            self.update(changed, w2c=kf.w2c[idx], depth=kf.depth[idx])
+        if n > m:
+            idx = torch.arange(m, n, device=kf.device)
+            conf = kf.conf_ds[idx // 5, idx % 5] if conf_min is not None else None
+            self.add(range(m, n), kf.depth[m:n], kf.w2c[m:n], kf.intrinsic[m:n].to(kf.device, torch.float32),
+                     rgb=kf.image[m:n] if self.colored else None, conf=conf, conf_ds=kf.downsample_ratio, conf_min=conf_min)
+        return n - m, len(changed)
+
+    # ------------------------------------------------------------------------------------------------------------ what is read
+    @torch.no_grad()
+    def resolve(self):
+        """(tsdf [nb,512], weight [nb,512], color [3,nb,512]) fp32: the accumulators as the pool planes of SparseTSDFVolume, kept until the
+        next add, remove or update"""
+        if self._planes is None:
+            nb = self.n_bricks
+            planes = (torch.empty(nb, ops.TSDF_BRICK_VOXELS, dtype=torch.float32, device=self.device),
+                      torch.empty(nb, ops.TSDF_BRICK_VOXELS, dtype=torch.float32, device=self.device),
+                      torch.empty(3, nb, ops.TSDF_BRICK_VOXELS, dtype=torch.float32, device=self.device))
+            if nb:
+                ops.tsdf_live_resolve(self.acc, *planes)
+            self._planes = planes
+        return self._planes
+
+    def _extract(self, weight_threshold):
+        if self.n_bricks == 0:
+            return torch.zeros(0, 3, dtype=torch.float32), torch.zeros(0, 3, dtype=torch.uint8), torch.zeros(0, 3, dtype=torch.int32)
+        return ops.tsdf_sparse_extract_mesh(*self.resolve(), self.table, self.bricks, self.dims, self.origin, self.voxel_size, weight_threshold)
+
+    def _ray_cast_batch(self, c2w, K, H, W, t_min, t_max, step, weight_threshold=1.0, normals=True, colors=True, count=False):
+        if self.n_bricks == 0:                                          # nothing stored: every ray misses
+            B, dev = c2w.shape[0], self.device
+            return (torch.zeros(B, H, W, dtype=torch.float32, device=dev),
+                    torch.zeros(B, H, W, 3, dtype=torch.float32, device=dev) if normals else None,
+                    torch.zeros(B, 3, H, W, dtype=torch.uint8, device=dev) if colors else None,
+                    torch.zeros(B, H, W, dtype=torch.int32, device=dev) if count else None)
+        return ops.tsdf_sparse_ray_cast(*self.resolve(), self.table, self.bricks, self.dims, self.origin, self.voxel_size, c2w, K, H, W, t_min,
+                                        t_max, step, weight_threshold=weight_threshold, normals=normals, colors=colors, count=count)
+
+    allocated_mask = SparseTSDFVolume.allocated_mask
+    _dense_dims = SparseTSDFVolume._dense_dims
+
+    @torch.no_grad()
+    def to_dense_acc(self):
+        """int32 [5,Z,Y,X]: the accumulators over the virtual grid, zeros where nothing is allocated (raises above the dense limit)"""
+        return torch.stack(_dense_from_bricks(self.bricks, self.brick_dims, self._dense_dims(), tuple(self.acc), (0,) * 5))
+
+    @torch.no_grad()
+    def to_dense(self):
+        """the resolved planes as SparseTSDFVolume.to_dense lays them out: (tsdf [Z,Y,X], weight [Z,Y,X], color [3,Z,Y,X]), 1 / 0 / 0 where
+        nothing is allocated"""
+        tsdf, weight, color = self.resolve()
+        out = _dense_from_bricks(self.bricks, self.brick_dims, self._dense_dims(), (tsdf, weight, *color), (1.0, 0.0, 0.0, 0.0, 0.0))
         return out[0], out[1], torch.stack(out[2:])
 
 
@@ -327,10 +616,10 @@ def shade(normal, w2c):
 
 
 @torch.no_grad()
-def write_previews(volume, w2c, K, H, W, outdir, every=1, **cast):
+def write_previews(volume, w2c, K, H, W, outdir, every=1, first=0, **cast):
     """ray-cast every `every`-th view and write <outdir>/{i:05d}_depth.png (16 bits at DEPTH_SCALE per metre, 0 = no surface),
-    {i:05d}_normal.png (shade) and {i:05d}_color.png; i is the view's index in w2c.  cast: the options of ray_cast.  Returns the indices
-    written and the RayCast of those views."""
+    {i:05d}_normal.png (shade) and {i:05d}_color.png; i is `first` + the view's index in w2c.  cast: the options of ray_cast.  Returns the
+    indices (into w2c) written and the RayCast of those views."""
     import os
     from PIL import Image
     if int(every) < 1:
@@ -344,9 +633,9 @@ def write_previews(volume, w2c, K, H, W, outdir, every=1, **cast):
     col = rc.color.permute(0, 2, 3, 1).contiguous().cpu().numpy()
     os.makedirs(outdir, exist_ok=True)
     for n, i in enumerate(idx):
-        Image.fromarray(raw[n]).save(os.path.join(outdir, f"{i:05d}_depth.png"))
-        Image.fromarray(nrm[n]).save(os.path.join(outdir, f"{i:05d}_normal.png"))
-        Image.fromarray(col[n]).save(os.path.join(outdir, f"{i:05d}_color.png"))
+        Image.fromarray(raw[n]).save(os.path.join(outdir, f"{first + i:05d}_depth.png"))
+        Image.fromarray(nrm[n]).save(os.path.join(outdir, f"{first + i:05d}_normal.png"))
+        Image.fromarray(col[n]).save(os.path.join(outdir, f"{first + i:05d}_color.png"))
     return idx, rc
 
 

@@ -8,7 +8,8 @@
 the image centre) and <output>/calib_estimated.txt holds it for the input frames, in the format --calib and --gt-calib read.
 
 Writes <output>/traj_kf.txt and <output>/intrinsics.npy exactly as the reference does (evo-compatible TUM rows); with --mesh also
-<output>/tsdf_mesh_w{W:.1f}.ply per --mesh-weight, the reference's post-run mesh (TSDF fusion on the GPU, cut3r_slam_amd/tsdf.py), and with
+<output>/tsdf_mesh_w{W:.1f}.ply per --mesh-weight, the reference's post-run mesh (TSDF fusion on the GPU, cut3r_slam_amd/tsdf.py), with
+--mesh-live <output>/tsdf_mesh_live_w{W:.1f}.ply from a volume kept current during the run (no fuse pass at the end), and with
 --mesh-simplify CELL and / or --mesh-min-faces N next to each of them tsdf_mesh_w{W:.1f}_clean.ply, that mesh after vertex clustering and
 small-component removal (cut3r_slam_amd/mesh_clean.py; scored into eval_recon_w{W:.1f}_clean.txt with --gt-mesh; --eval-pr adds
 precision, recall and F-score, the keys scripts/run_replica.py reads, to those files), and with
@@ -114,6 +115,14 @@ def main(argv=None):
                    "surfaces only: the same mesh, memory by surface area, no 2^31-voxel limit)")
     p.add_argument("--mesh-preview", type=int, default=None, metavar="N", help="with --mesh: ray-cast the fused volume at every N-th keyframe "
                    "and write <output>/tsdf_preview/{kf:05d}_{depth,normal,color}.png (depth: 16 bits at 6553.5 per metre, 0 = no surface)")
+    p.add_argument("--mesh-live", action="store_true", help="keep a live TSDF volume of the tracked keyframes current DURING the run "
+                   "(cut3r_slam_amd/tsdf.py LiveTSDFVolume: keyframes are added as they come and re-posed exactly when loop closure or the "
+                   "mapper rewrites them) and write <output>/tsdf_mesh_live_w{W:.1f}.ply per --mesh-weight at the end, without a fuse pass; "
+                   "uses --voxel-size and --depth-max, independent of --mesh")
+    p.add_argument("--mesh-live-extent", type=float, default=8.0, metavar="M", help="with --mesh-live: half the side of the cube around the "
+                   "first keyframe's camera that the live volume covers, in scene units")
+    p.add_argument("--mesh-live-preview", type=int, default=None, metavar="N", help="with --mesh-live: every N keyframes, ray-cast the live "
+                   "volume at the newest keyframe and write <output>/tsdf_live_preview/{kf:05d}_{depth,normal,color}.png")
     p.add_argument("--mesh-simplify", type=float, default=None, metavar="CELL", help="with --mesh: also write tsdf_mesh_w{W:.1f}_clean.ply, "
                    "the mesh after vertex clustering at this cell size (cut3r_slam_amd/mesh_clean.py)")
     p.add_argument("--mesh-min-faces", type=int, default=None, metavar="N", help="with --mesh: also write tsdf_mesh_w{W:.1f}_clean.ply, the "
@@ -177,6 +186,10 @@ def main(argv=None):
         p.error("--mesh-sparse needs --mesh")
     if args.mesh_preview is not None and (not args.mesh or args.mesh_preview < 1):
         p.error("--mesh-preview N needs --mesh and N >= 1")
+    if args.mesh_live_preview is not None and (not args.mesh_live or args.mesh_live_preview < 1):
+        p.error("--mesh-live-preview N needs --mesh-live and N >= 1")
+    if args.mesh_live and not (0 < args.mesh_live_extent < float("inf")):
+        p.error("--mesh-live-extent must be > 0 and finite")
     if (args.mesh_simplify is not None or args.mesh_min_faces is not None) and not args.mesh:
         p.error("--mesh-simplify and --mesh-min-faces need --mesh")
     if args.mesh_simplify is not None and not (0 < args.mesh_simplify < float("inf")):
@@ -251,7 +264,24 @@ def main(argv=None):
                 s_.mapper_factory = with_panels
             if intr_ds is not None:
                 s_.mapper = s_.mapper_factory(*[float(v) for v in intr_ds[0].reshape(-1)[:4]])
+        if args.mesh_live:
+            s_.start_live_volume(args.voxel_size, args.mesh_live_extent, depth_max=args.depth_max)
         return s_
+
+    live_previews = []
+
+    def live_preview():
+        """--mesh-live-preview N: once the live volume holds another N keyframes, its ray cast at the newest of them"""
+        vol = slam.live_volume
+        if args.mesh_live_preview is None or vol is None:
+            return
+        n = len(vol.records)
+        if n // args.mesh_live_preview > len(live_previews):
+            from cut3r_slam_amd.tsdf import write_previews
+            kf = slam.keyframes
+            write_previews(vol, kf.w2c[n - 1:n].cpu(), kf.intrinsic[n - 1:n], kf.ht, kf.wd, os.path.join(args.output, "tsdf_live_preview"),
+                           first=n - 1, weight_threshold=args.mesh_weight[0])
+            live_previews.extend([n - 1] * (n // args.mesh_live_preview - len(live_previews)))
 
     def items():
         # demo_s.py:158-159: a --length cut does NOT flush the tail window (the flags look at the directory, not at the cut)
@@ -269,7 +299,7 @@ def main(argv=None):
             def chain():
                 yield first
                 yield from it
-            slam.run_stream(chain(), lookahead=args.lookahead, on_frame=lambda t_, out_: counted.append(t_))
+            slam.run_stream(chain(), lookahead=args.lookahead, on_frame=lambda t_, out_: (counted.append(t_), live_preview()))
             nframes = len(counted)
     else:
         for item in items():
@@ -277,6 +307,7 @@ def main(argv=None):
                 slam = make_slam(item[3], item[4][None] if item[4] is not None else None)
             slam.run(item[0], item[1], item[2], item[3], item[4], second_last_frame=item[5], last_frame=item[6])
             nframes += 1
+            live_preview()
     if slam is None:
         raise SystemExit(f"{args.imagedir}: no frames")
     torch.cuda.synchronize()
@@ -318,6 +349,22 @@ def main(argv=None):
         from cut3r_slam_amd.depth_consistency import ConsistencyOptions
         consistency = ConsistencyOptions(window=args.consistency_window, min_support=args.consistency_min_support, pix=args.consistency_pix,
                                          rel=args.consistency_rel, average=args.consistency_average)
+    if args.mesh_live:
+        from cut3r_slam_amd.tsdf import write_ply
+        live = slam.live_volume
+        if live is None:
+            raise SystemExit("--mesh-live: the run ended before its first keyframe was tracked")
+        X, Y, Z = live.dims
+        print(f"live TSDF: {len(live.records)} keyframes in {X}x{Y}x{Z} voxels of {live.voxel_size:g}, {live.n_bricks} of {live.table.numel()} "
+              f"bricks allocated ({live.nbytes / 1e9:.3f} GB)" + (f", {len(set(live_previews))} previews -> {args.output}/tsdf_live_preview"
+                                                                 if args.mesh_live_preview is not None else ""))
+        for w in args.mesh_weight:
+            t_ext = time.time()
+            mesh = live.extract_mesh(w)
+            path = os.path.join(args.output, f"tsdf_mesh_live_w{w:.1f}.ply")
+            write_ply(path, mesh)
+            print(f"live mesh w >= {w:g}: {len(mesh.vertices)} vertices, {len(mesh.faces)} faces, extracted in {1e3 * (time.time() - t_ext):.1f} ms "
+                  f"-> {path}")
     vol = None
     if args.mesh:
         from cut3r_slam_amd.tsdf import write_ply

@@ -653,6 +653,32 @@ int cut3r_tsdf_sparse_mesh_emit(const float* tsdf, const float* color, const int
                                 float ox, float oy, float oz, float voxel, const void* workspace, long long workspace_bytes, float* verts,
                                 unsigned char* colors, int* faces, long long nv, long long nf, void* stream);
 
+/* ---- Live TSDF volume (csrc/tsdf_live.hip) -------------------------------------------------------------------------------------------
+ * The sparse brick volume above (its lattice, flags, table and bricks; mark and assign as they are) with integer accumulators, so that
+ * views are added, removed and re-posed exactly while a run goes on:
+ *   acc int32 [5][nb*512]   sum_q, count, sum_r, sum_g, sum_b of pool voxel slot * 512 + (lk*8 + lj)*8 + li; all zero at the start
+ * A view that updates a voxel under the gates of cut3r_tsdf_integrate, with t = min(1, sdf / trunc), adds q = (int)rintf(t * 32768.f)
+ * (|q| <= 32768, exact), 1 and its three u8 colour values (colour only with rgb != NULL: a volume is coloured or not for its whole life).
+ * The sums depend on the set of views that are in, not on their order, the batch split or the history; at most 65535 views may be in
+ * (65535 * 32768 < 2^31).
+ *
+ * integrate: B <= 16 views in one launch over the pool slots listed in `slots` (int32 [ns] on the device, 1 <= ns <= nb, each in
+ * 0..nb-1 and listed once: the caller's contract) or over all nb when slots == NULL -- the bricks allocated after earlier views went in
+ * catch up through it.  Bit b of subtract_mask takes view b out (its contribution is negated); bits at or above B are an error.  One
+ * workgroup per slot, one thread per voxel, the sparse integrate's brick-versus-frustum view mask; a voxel no view touches is neither read
+ * nor written, no atomics.
+ *
+ * resolve: the accumulators of the listed slots (or all) as the fp32 pool planes that cut3r_tsdf_sparse_mesh_* and
+ * cut3r_tsdf_sparse_ray_cast read (all four pointers 16-byte aligned): count == 0 gives tsdf 1, weight 0, colour 0; else
+ * tsdf = (float)((double)sum_q / ((double)count * 32768.0)), weight = (float)count, color[c] = (float)((double)sum_c / (double)count) --
+ * correctly rounded means.
+ * CUT3R_ERR_ARG: a null pointer, B outside 1..16, bad dims or nb, ns outside 1..nb with slots given, a subtract_mask bit >= B. */
+int cut3r_tsdf_live_integrate(int* acc, const int* bricks, int nb, const int* slots, int ns, int X, int Y, int Z, float ox, float oy,
+                              float oz, float voxel, const float* depth, const unsigned char* rgb, const float* conf, int B, int H, int W,
+                              int ch, int cw, int ds, float conf_min, const float* w2c, const float* K, unsigned subtract_mask, float trunc,
+                              float depth_max, void* stream);
+int cut3r_tsdf_live_resolve(const int* acc, int nb, const int* slots, int ns, float* tsdf, float* weight, float* color, void* stream);
+
 /* ---- Ray cast of the TSDF volumes (csrc/tsdf_raycast.hip) ----------------------------------------------------------------------------
  * Replaces Open3D VoxelBlockGrid.ray_cast, the third operation of the grid that tsdf_integrate.py:34 builds: depth, normal and colour
  * images of the fused model.  The planes / the pool with its table and brick list are those of the two families above.  c2w [B,12]
